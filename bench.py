@@ -8,8 +8,9 @@ triangles). The target depth is the mesh rendered under a smooth ground-truth mo
 A step = restore a stored mid-motion node state (half the ground-truth motion: non-identity R/t, a deformed mesh) by a
 device copy + one full GN iteration through the general kernels (warp, rasterize, residuals, Jacobians, JtJ / Jt r, LM
 block solve, Rodrigues update); --graph-steps (default 10, C2's GN iterations per frame) steps are captured as one
-hipGraph and replayed as one launch, the way FitToImage replays its iteration loop (the timed step count is rounded up
-to a whole number of launches). Every step does the same work, with nothing cached between steps. The reference's own
+hipGraph and replayed as one launch, the way FitToImage replays its iteration loop (--steps N times exactly N steps:
+N // graph-steps whole launches and one shorter launch of the rest). Every step does the same work, with nothing cached
+between steps. The reference's own
 C2 trajectory cannot be timed as a 10-iteration loop: its block-diagonal GN (A17) raises potrf at iteration 2 on C2, on
 the GPU and in the oracle alike (tests/test_gpu_parity.py TRAJECTORIES). --step frame (whole frame fits from the
 identity warp, for configs whose trajectory survives, e.g. C2_ARAP) and --step identity (the first iteration of a frame)
@@ -21,7 +22,12 @@ end-of-run all-gather of per-rank results. --replicas R: R inde
 its own fitter, warp field and stream on the one device (seeds rank * R + r); a step launches every replica's iteration
 on its stream; value = all sequences' iterations / the slowest rank's time.
 
-Also reported: the dominant kernel's roofline (k_fit_pixels_fused: both pixel passes in one launch, timed in its real
+A plain run sets up, warms up, times the steps, writes --dump-outputs and prints the result line. --dump-outputs DIR
+writes what the last timed step left with its caller (node rotations and translations, the GN update, residuals, residual
+mask, rasterized faces) as DIR/<name>.npy; the inputs are the same from run to run, so two builds compare output for
+output.
+
+With --full also reported: the dominant kernel's roofline (k_fit_pixels_fused: both pixel passes in one launch, timed in its real
 context by nnrt_fitter_time_kernels -- graph-captured prefix sequences of iterations between HIP events on the fitter's
 stream, so the figure matches the rocprofv3 kernel trace; every other kernel of the iteration under "kernels"), the once-per-frame setup time, and the CPU baseline (the oracle/ C++
 restatement with the reference's binned rasterizer, OpenMP, on a bounded sample of the same workload, rank 0, N = 1: one
@@ -65,10 +71,10 @@ def max_over_ranks(value: float, device=None) -> float:
 MIN_WARM_S = 0.05   # seconds of untimed back-to-back GPU work before the timed region (clock ramp-up)
 
 
-def timed_region(step, launches: int, per_launch: int, world: int, sync, dist_on=None, group=None) -> tuple:
-    """The timed protocol: barrier + device sync, `launches` x step(per_launch), device sync, barrier. Returns (OR of
-    the step return codes, this rank's elapsed seconds). dist_on: barriers on (default: world > 1); group: the process
-    group the barriers run on (default: the world group)."""
+def timed_region(step, launches: int, per_launch: int, world: int, sync, dist_on=None, group=None, tail: int = 0) -> tuple:
+    """The timed protocol: barrier + device sync, `launches` x step(per_launch) and, if tail > 0, one step(tail), device
+    sync, barrier. Returns (OR of the step return codes, this rank's elapsed seconds). dist_on: barriers on (default:
+    world > 1); group: the process group the barriers run on (default: the world group)."""
     import torch.distributed as dist
     dist_on = world > 1 if dist_on is None else dist_on
     if dist_on:
@@ -78,6 +84,8 @@ def timed_region(step, launches: int, per_launch: int, world: int, sync, dist_on
     bad = 0
     for _ in range(launches):
         bad |= step(per_launch)
+    if tail > 0:
+        bad |= step(tail)
     sync()
     elapsed = time.perf_counter() - t0
     if dist_on:
@@ -95,6 +103,25 @@ def exchange_per_rank(steps: int, elapsed: float, update_norm: float, device=Non
     got = [torch.empty_like(mine) for _ in range(dist.get_world_size())]
     dist.all_gather(got, mine)
     return [dict(rank=i, iters_per_s=float(g[0]), seconds=float(g[1]), update_norm=float(g[2])) for i, g in enumerate(got)]
+
+
+DUMP_BYTES = 64 << 20   # --dump-outputs writes at most this much, all ranks and replicas together
+
+
+def dump_outputs(directory: str, prefix: str, budget: int, arrays: dict) -> None:
+    """Write each array as directory/<prefix><name>.npy: floating-point arrays as they are (float32 / float64), integer
+    and boolean ones as float64 (exact). An array over its equal share of `budget` bytes is cut to a fixed sample of its
+    flattened elements (seed 0, ascending indices), the same from run to run."""
+    os.makedirs(directory, exist_ok=True)
+    share = budget // max(1, len(arrays)) - 128   # 128: the .npy header
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a)
+        if a.dtype not in (np.float32, np.float64):
+            a = a.astype(np.float64)
+        if a.nbytes > share:
+            keep = np.sort(np.random.default_rng(0).choice(a.size, share // a.itemsize, replace=False))
+            a = a.reshape(-1)[keep]
+        np.save(os.path.join(directory, prefix + name + ".npy"), a)
 
 
 def aggregate(steps: int, elapsed_s: float, world: int) -> dict:
@@ -179,6 +206,12 @@ def parse_args(argv=None):
                          "--graph-steps-iteration frame fits from the identity warp (FitToImage's loop; raises potrf on C2, "
                          "as the reference does); identity: the first iteration of a frame per step")
     ap.add_argument("--replicas", type=int, default=1, help="independent sequences per GPU, one stream each (C4's per-rank work)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last step's outputs as DIR/<name>.npy (float32 / float64)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: per-kernel and per-stage times, rooflines, the "
+                         "once-per-frame setup time and the CPU baseline (--timed-steps, --kernel-*, --cpu-*, --no-cpu-baseline "
+                         "and --traffic-file act only with --full)")
     ap.add_argument("--timed-steps", type=int, default=10, help="eager per-stage HIP-event timing steps (association counts, stage_ms)")
     ap.add_argument("--kernel-reps", type=int, default=20, help="iterations per graph of the per-kernel timing (nnrt_fitter_time_kernels)")
     ap.add_argument("--kernel-trials", type=int, default=9, help="interleaved trials of the per-kernel timing (median)")
@@ -193,7 +226,10 @@ def parse_args(argv=None):
     ap.add_argument("--cpu-no-warm", action="store_true", help="CPU baseline without the untimed first call (large configs: C3)")
     ap.add_argument("--traffic-file", default=None,
                     help="PMC-derived HBM bytes per launch of the roofline kernel (tools/pmc_traffic.py output)")
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 def log(*a):
@@ -466,9 +502,12 @@ def main(argv=None):
     # warmup (graphs are captured on first use: use_hip_graph = 2): the requested W steps, and at least MIN_WARM_S of
     # back-to-back GPU work -- the GPU's clocks ramp up from idle: a 20-step timed region after 10 warmup steps measured
     # 14,300 GN it/s at C2, after 200 warmup steps 15,500 (round-3 A/B r3_warm, in git history)
+    launches, tail = divmod(args.steps, per_launch)   # --steps N: whole graphs and one shorter launch of the rest
     for _ in range(max(1, args.warmup // per_launch)):
         if step(per_launch):
             NV.check(1)
+    if tail and step(tail):   # the shorter launch is a graph of its own: captured here, not in the timed region
+        NV.check(1)
     torch.cuda.synchronize(dev)
     t_warm = time.perf_counter()
     while time.perf_counter() - t_warm < MIN_WARM_S:
@@ -479,9 +518,8 @@ def main(argv=None):
     for rp in reps:
         rp["ft"].check(stream=rp["stream"])
 
-    launches = -(-args.steps // per_launch)
-    args.steps = launches * per_launch   # whole graphs only: the timed step count is rounded up to a multiple
-    bad, elapsed = timed_region(step, launches, per_launch, world, lambda: torch.cuda.synchronize(dev), dist_on=use_dist, group=ctrl_group)
+    bad, elapsed = timed_region(step, launches, per_launch, world, lambda: torch.cuda.synchronize(dev), dist_on=use_dist, group=ctrl_group,
+                                tail=tail)
     if bad:
         NV.check(bad)
     per_replica = []
@@ -490,11 +528,57 @@ def main(argv=None):
         final_t = rp["wf"].get_node_translations()
         if not np.isfinite(final_t).all():
             raise SystemExit(f"non-finite node motion after the timed steps (replica {r})")
-        per_replica.append(dict(replica=r, seed=rank * R + r,
-                                update_norm=float(np.linalg.norm(rp["ft"].diagnostics(stream=rp["stream"])["updates"]))))
+        dg_r = rp["ft"].diagnostics(stream=rp["stream"])
+        per_replica.append(dict(replica=r, seed=rank * R + r, update_norm=float(np.linalg.norm(dg_r["updates"]))))
+        if args.dump_outputs:
+            prefix = (f"rank{rank}_" if world > 1 else "") + (f"replica{r}_" if R > 1 else "")
+            dump_outputs(args.dump_outputs, prefix, DUMP_BYTES // (world * R),
+                         dict(node_rotations=rp["wf"].get_node_rotations(), node_translations=final_t, **dg_r))
     elapsed_max = max_over_ranks(elapsed, coll_dev)
     agg = aggregate(args.steps * R, elapsed_max, world)
     agg["ms_per_step"] = 1000.0 * elapsed_max / args.steps   # one step = every replica's iteration
+    update_norm = per_replica[0]["update_norm"]
+
+    out = {
+        "metric": "GN iters/sec (640x480, 1.5k-node graph)" if args.config == "C2" else f"GN iters/sec ({args.config})",
+        "value": agg["value"],
+        "unit": "GN iters/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": agg["ms_per_step"],
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": "f32",
+        "data": "synthetic (smooth grid mesh + GT node motion rendered to depth; seed = rank)",
+        "config": {"workload": workload, "config": args.config, "frame": [sc.H, sc.W], "nodes": Nn, "vertices": V, "triangles": F,
+                   "anchors": 4, "iteration_mode": "ALL", "lm_damping": 0.001, "hip_graph": True, "steps_per_graph": per_launch, "step": args.step,
+                   "parallelism": f"replicas{world * R}" if world * R > 1 else "single", "replicas_per_gpu": R,
+                   **({"collectives": "rccl (max-over-ranks, per-rank all-gather; timed-region barriers on a gloo group)" if backend == "nccl" else f"{backend} (rehearsal: {world} ranks on "
+                                                                       f"{torch.cuda.device_count()} visible GPU(s))"}
+                      if use_dist else {})},
+        "full": args.full,
+        "per_replica": per_replica if R > 1 else None,
+    }
+    if args.full:
+        full, update_norm = full_measurements(args, torch, dev, A, sc, wf, ft, mesh, depth, workload, per_launch, agg, R1, t1, rank, world)
+        out.update(full)
+    # end-of-run exchange of per-rank results (SURVEY.md 8(e)): iterations/s, seconds, final |update|
+    out["per_rank"] = exchange_per_rank(args.steps * R, elapsed, update_norm, coll_dev)
+    if rank == 0:
+        print(json.dumps(out), flush=True)
+    if use_dist:
+        dist.barrier()
+        dist.destroy_process_group()
+
+
+def full_measurements(args, torch, dev, A, sc, wf, ft, mesh, depth, workload, per_launch, agg, R1, t1, rank, world):
+    """--full: what the run measures beside its headline figure, after the timed steps: per-kernel and per-stage times,
+    rooflines, the once-per-frame setup time and the CPU baseline. Returns (the result line's extra fields, |update| of
+    the last iteration it ran)."""
+    arap = sc.layer_count > 1
+    P, F, V, Nn = sc.H * sc.W, len(sc.faces), len(sc.points), len(sc.nodes)
 
     # per-kernel device time, each kernel in its real context: prefix sequences of graph-captured iterations from the
     # snapshot state, replayed between HIP events on the fitter's stream (nnrt_fitter_time_kernels); these are the
@@ -596,29 +680,8 @@ def main(argv=None):
     torch.cuda.synchronize(dev)
     setup_ms = (time.perf_counter() - t_setup) * 1000.0
 
-    # end-of-run exchange of per-rank results (SURVEY.md 8(e)): iterations/s, seconds, final |update|
-    per_rank = exchange_per_rank(args.steps * R, elapsed, float(np.linalg.norm(dg["updates"])), coll_dev)
-
     out = {
-        "metric": "GN iters/sec (640x480, 1.5k-node graph)" if args.config == "C2" else f"GN iters/sec ({args.config})",
-        "value": agg["value"],
-        "unit": "GN iters/s",
-        "n_gpus": world,
-        "steps": args.steps,
-        "warmup": args.warmup,
-        "ms_per_step": agg["ms_per_step"],
         "ms_per_solve": ktimes["solve"],
-        "higher_is_better": True,
-        "scaling": "weak",
-        "vs_baseline": None,
-        "dtype": "f32",
-        "data": "synthetic (smooth grid mesh + GT node motion rendered to depth; seed = rank)",
-        "config": {"workload": workload, "config": args.config, "frame": [sc.H, sc.W], "nodes": Nn, "vertices": V, "triangles": F,
-                   "anchors": 4, "iteration_mode": "ALL", "lm_damping": 0.001, "hip_graph": True, "steps_per_graph": per_launch, "step": args.step,
-                   "parallelism": f"replicas{world * R}" if world * R > 1 else "single", "replicas_per_gpu": R,
-                   **({"collectives": "rccl (max-over-ranks, per-rank all-gather; timed-region barriers on a gloo group)" if backend == "nccl" else f"{backend} (rehearsal: {world} ranks on "
-                                                                       f"{torch.cuda.device_count()} visible GPU(s))"}
-                      if use_dist else {})},
         "setup_ms": round(setup_ms, 3),
         "kernel_ms": {k: (round(v, 5) if v else None) for k, v in ktimes.items()},
         "kernel_ms_note": f"nnrt_fitter_time_kernels: per-iteration device time of each kernel in its real context, by differences "
@@ -647,8 +710,6 @@ def main(argv=None):
                      "iteration_frac": it_bytes / (agg["ms_per_step"] * 1e-3) / 1e9 / HBM_PEAK_GBS},
         "kernels": kernels,
         "hbm_roofline": None,
-        "per_rank": per_rank,
-        "per_replica": per_replica if R > 1 else None,
         "cpu_baseline": None,
     }
     if corner is not None and pmc:   # the solve stage's kernels as the PMC passes measured them (bytes per launch)
@@ -674,11 +735,7 @@ def main(argv=None):
                                            share_only=args.cpu_share_only, warm=not args.cpu_no_warm)
         out["cpu_baseline"]["host"]["sched_affinity"] = len(os.sched_getaffinity(0))
         out["cpu_baseline"]["host"]["omp_num_threads_env"] = os.environ.get("OMP_NUM_THREADS")
-    if rank == 0:
-        print(json.dumps(out), flush=True)
-    if use_dist:
-        dist.barrier()
-        dist.destroy_process_group()
+    return out, float(np.linalg.norm(dg["updates"]))
 
 
 if __name__ == "__main__":

@@ -116,6 +116,35 @@ def test_single_process_helpers():
     assert agg["value"] == pytest.approx(20.0) and agg["ms_per_step"] == pytest.approx(50.0)
 
 
+def test_timed_region_runs_exactly_the_requested_steps():
+    """--steps N = N // per_launch whole launches and one shorter launch of the rest: 23 steps at 10 per launch."""
+    calls = []
+    launches, tail = divmod(23, 10)
+    bad, _ = bench.timed_region(lambda n: calls.append(n) or 0, launches, 10, 1, lambda: None, tail=tail)
+    assert bad == 0 and calls == [10, 10, 3] and sum(calls) == 23
+    calls.clear()
+    bench.timed_region(lambda n: calls.append(n) or 0, 2, 10, 1, lambda: None)
+    assert calls == [10, 10]
+
+
+def test_dump_outputs(tmp_path):
+    """--dump-outputs: float32 / float64 .npy files, integers and masks exact as float64, a fixed sample of an array over
+    its share of the byte budget, identical from call to call."""
+    import numpy as np
+    arrays = dict(t=np.arange(12, dtype=np.float32).reshape(4, 3), faces=np.array([-1, 5, 1 << 30], np.int32),
+                  mask=np.array([True, False]), big=np.arange(100000, dtype=np.float32))
+    bench.dump_outputs(str(tmp_path / "a"), "", 4 * 10000, arrays)
+    bench.dump_outputs(str(tmp_path / "b"), "replica1_", 4 * 10000, arrays)
+    got = {n: np.load(tmp_path / "a" / f"{n}.npy") for n in arrays}
+    assert got["t"].dtype == np.float32 and np.array_equal(got["t"], arrays["t"])
+    assert got["faces"].dtype == np.float64 and np.array_equal(got["faces"], arrays["faces"])
+    assert got["mask"].dtype == np.float64 and np.array_equal(got["mask"], [1.0, 0.0])
+    assert got["big"].dtype == np.float32 and 0 < got["big"].nbytes <= 10000 and np.all(np.diff(got["big"]) > 0)
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in os.listdir(tmp_path / "a")) <= 4 * 10000
+    for n in arrays:
+        assert np.array_equal(got[n], np.load(tmp_path / "b" / f"replica1_{n}.npy"))
+
+
 def test_algorithmic_bytes_c2():
     # SURVEY.md 8(d) worked example: C2 (P = 307,200, V = 77,361, F = 153,600, K = 4, E ~ 1.4 M, N = 1500) ~ 374 MB
     sb = bench.stage_bytes(640 * 480, 153600, 77361, 1500, 4, 1_400_000)

@@ -10,7 +10,7 @@ cd /tmp && export TMPDIR=/tmp && cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 line() {
 	local name=$1 t=$2; shift 2
 	echo "== $name"
-	timeout -k 10 "$t" python3 -u bench.py "$@" > "$OUT/line_$name.log" 2>&1
+	timeout -k 10 "$t" python3 -u bench.py --full "$@" > "$OUT/line_$name.log" 2>&1
 	local rc=$?
 	echo "== $name rc=$rc"
 	[ $rc -eq 0 ] || { tail -n 5 "$OUT/line_$name.log"; return $rc; }

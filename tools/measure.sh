@@ -11,10 +11,10 @@ OUT=gpurun_out/$TAG
 mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp && cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 step() { local name=$1 t=$2; shift 2; echo "== $name"; timeout -k 10 "$t" "$@" > "$OUT/$name.log" 2>&1; local rc=$?; echo "== $name rc=$rc"; tail -n 2 "$OUT/$name.log" | cut -c1-300; return $rc; }
-B="python3 bench.py --config $CONFIG ${BENCH_ARGS:-}"   # (BENCH_ARGS: e.g. --step frame --graph-steps 10)
+B="python3 bench.py --full --config $CONFIG ${BENCH_ARGS:-}"   # (BENCH_ARGS: e.g. --step frame --graph-steps 10)
 for s in $STAGES; do
 	case $s in
-		bench) step bench_$CONFIG 400 python3 -u bench.py --config $CONFIG ${BENCH_ARGS:-} || exit 1
+		bench) step bench_$CONFIG 400 python3 -u bench.py --full --config $CONFIG ${BENCH_ARGS:-} || exit 1
 		       grep '^{' $OUT/bench_$CONFIG.log > $OUT/bench_$CONFIG.json ;;
 		prof) step prof_$CONFIG 400 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_$CONFIG -o run -- $B --steps 300 --warmup 30 --no-cpu-baseline || exit 1 ;;
 		pmc) step pmc_fetch_$CONFIG 300 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $OUT/pmc_fetch_$CONFIG -o run -- $B --steps 20 --warmup 5 --kernel-trials 1 --no-cpu-baseline || exit 1
