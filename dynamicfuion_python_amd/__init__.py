@@ -5,6 +5,7 @@ Layout:
   _native.py       ctypes binding of the C-ABI (fails loudly when the extension or a GPU is missing)
   nnrt/            mirror of the reference's `nnrt` Python module names on the hot path
   alignment/       mirror of alignment/render_based/RenderingAlignmentOptimizer (the reference's Python API slot)
+  warp_field/      mirror of warp_field/graph_warp_field.py: the motion graph from a mesh (erosion + node sampling on the GPU)
   synthetic.py     synthetic scenes for the BASELINE configs (C1-C5)
 """
 __all__ = ["nnrt", "alignment", "synthetic"]

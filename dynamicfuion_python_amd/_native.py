@@ -111,6 +111,8 @@ _SIGNATURES = {
     "nnrt_backproject_depth_float": (c_int32, [c_void_p, c_int32, c_int32, c_float, c_float, c_float, c_float, c_void_p, c_void_p]),
     "nnrt_matmul3d": (c_int32, [c_void_p, c_void_p, c_int64, c_int32, c_int32, c_int32, c_void_p, c_void_p]),
     "nnrt_median_grid_subsample_3d_points": (c_int32, [c_void_p, c_int64, c_float, c_void_p, c_void_p, c_void_p]),
+    "nnrt_get_vertex_erosion_mask": (c_int32, [c_int64, c_void_p, c_int64, c_int32, c_int32, c_void_p, c_void_p]),
+    "nnrt_sample_nodes": (c_int32, [c_void_p, c_int64, c_void_p, c_void_p, c_float, c_void_p, c_int64, c_void_p, c_void_p, c_void_p]),
     "nnrt_axis_angle_to_matrices_rodrigues": (c_int32, [c_void_p, c_int32, c_void_p, c_void_p]),
     "nnrt_compute_triangle_normals": (c_int32, [c_void_p, c_int64, c_void_p, c_int64, c_int32, c_void_p, c_void_p]),
     "nnrt_compute_vertex_normals": (c_int32, [c_void_p, c_int64, c_void_p, c_int64, c_int32, c_void_p, c_void_p]),

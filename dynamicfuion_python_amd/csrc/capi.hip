@@ -1710,6 +1710,47 @@ nnrt_status with_device_flag(hipStream_t s, nnrt_status code, const char* messag
 }
 } // extern "C++"
 
+nnrt_status nnrt_get_vertex_erosion_mask(int64_t vertex_count, const int64_t* d_face_indices, int64_t face_count, int32_t iteration_count,
+                                         int32_t min_neighbors, uint8_t* d_out_mask, void* stream) {
+	NNRT_CHECK_ARG(vertex_count >= 0 && vertex_count < (int64_t(1) << 31), "vertex count out of range");
+	NNRT_CHECK_ARG(face_count >= 0 && face_count < (int64_t(1) << 31) / 3, "face count out of range");
+	NNRT_CHECK_ARG(iteration_count >= 0, "negative iteration_count");
+	NNRT_CHECK_ARG(face_count == 0 || d_face_indices, "null face indices");
+	NNRT_CHECK_ARG(vertex_count == 0 || d_out_mask, "null output mask");
+	NNRT_CHECK_ARG(vertex_count == 0 || face_count == 0 ||
+	                   !ranges_overlap(d_out_mask, static_cast<size_t>(vertex_count), d_face_indices, sizeof(int64_t) * 3 * static_cast<size_t>(face_count)),
+	               "d_out_mask must not overlap d_face_indices");
+	hipStream_t s = static_cast<hipStream_t>(stream);
+	if (vertex_count == 0 && face_count == 0) return NNRT_OK;
+	if (face_count == 0) {
+		NNRT_HIP(hipMemsetAsync(d_out_mask, 0, static_cast<size_t>(vertex_count), s));
+		return NNRT_OK;
+	}
+	return with_device_flag(s, NNRT_ERROR_ARGUMENT, "face index outside [0, vertex_count) in get_vertex_erosion_mask", [&](int* flag) {
+		return launch_vertex_erosion_mask(vertex_count, d_face_indices, face_count, iteration_count, min_neighbors, d_out_mask, flag, s);
+	});
+}
+
+nnrt_status nnrt_sample_nodes(const float* d_points, int64_t point_count, const uint8_t* d_mask, const int64_t* d_order, float node_coverage,
+                              int64_t* d_out_indices, int64_t out_capacity, int64_t* h_out_count, int32_t* h_out_rounds, void* stream) {
+	NNRT_CHECK_ARG(h_out_count, "null h_out_count");
+	NNRT_CHECK_ARG(point_count >= 0 && point_count < (int64_t(1) << 31) / 3, "point count out of range");
+	NNRT_CHECK_ARG(point_count == 0 || (d_points && d_out_indices), "null pointer");
+	NNRT_CHECK_ARG(node_coverage > 0.f && std::isfinite(node_coverage), "node_coverage must be positive and finite");
+	NNRT_CHECK_ARG(std::isnormal(node_coverage * node_coverage), "node_coverage squared must be a finite normal float");
+	NNRT_CHECK_ARG(out_capacity >= point_count, "out_capacity must be at least point_count");
+	const size_t n = static_cast<size_t>(point_count), out_bytes = sizeof(int64_t) * n;
+	NNRT_CHECK_ARG(point_count == 0 || !(ranges_overlap(d_out_indices, out_bytes, d_points, sizeof(float) * 3 * n) ||
+	                                     (d_mask && ranges_overlap(d_out_indices, out_bytes, d_mask, n)) ||
+	                                     (d_order && ranges_overlap(d_out_indices, out_bytes, d_order, sizeof(int64_t) * n))),
+	               "d_out_indices must not overlap an input");
+	*h_out_count = 0;
+	if (h_out_rounds) *h_out_rounds = 0;
+	if (point_count == 0) return NNRT_OK;
+	return launch_sample_nodes(d_points, point_count, d_mask, d_order, node_coverage, d_out_indices, h_out_count, h_out_rounds,
+	                           static_cast<hipStream_t>(stream));
+}
+
 nnrt_status nnrt_matmul_block_sparse_row_wise(const float* d_a_blocks, int32_t a_block_count, const float* d_b_blocks,
                                               const int32_t* d_b_coordinates, int32_t b_block_count, int32_t block_size, float* d_c_blocks,
                                               uint8_t* d_c_mask, void* stream) {

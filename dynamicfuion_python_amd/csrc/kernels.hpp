@@ -106,6 +106,11 @@ nnrt_status launch_warp_points(const float* points, const float* normals, int64_
                                hipStream_t stream);
 nnrt_status launch_matmul3d(const float* A, const float* B, int64_t batch, int m, int k, int n, float* C, hipStream_t stream);
 nnrt_status launch_median_grid_subsample(const float* pts, int n, float cell, int64_t* out, int64_t* h_count, hipStream_t s);
+// graph_sampling.hip: motion-graph node selection (cpp/cpu/graph_proc.cpp:27-155)
+nnrt_status launch_vertex_erosion_mask(int64_t V, const int64_t* faces, int64_t F, int iteration_count, int min_neighbors, uint8_t* mask,
+                                       int* error_flag, hipStream_t s);
+nnrt_status launch_sample_nodes(const float* pts, int64_t V, const uint8_t* mask, const int64_t* order, float coverage, int64_t* out,
+                                int64_t* h_count, int32_t* h_rounds, hipStream_t s);
 nnrt_status launch_point_to_plane(const float* n1, const float* v1, const float* v2, int64_t count, float* out, hipStream_t stream);
 nnrt_status launch_interpolate(const int64_t* pixel_faces, const float* bary, int64_t P, int Kf, const float* attrs, int C, float* out,
                                hipStream_t stream);

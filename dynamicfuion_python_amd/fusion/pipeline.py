@@ -9,10 +9,11 @@ switch `FusionParameters.tracking_method` selects
 * `TrackingMethod.NEURAL` -- the reference's DeformNet path, which this build does not provide (raises).
 
 Per frame, everything stays on the GPU: depth/colour upload, back-projection, ordered-point-cloud normals, the GN fit,
-truncation-region block search, non-rigid TSDF integration and marching cubes. Graph generation uses the DeepDeformGraph
-file of the first frame (`GraphGenerationMode.FIRST_FRAME_LOADED_GRAPH`) or nodes supplied by the caller; the
-reference's mesh/depth-based graph builders and its rigid odometry (Open3D `rgbd_odometry_multi_scale`) are out of scope
-(the camera is static, identity extrinsics, as in the DeepDeform sequences).
+truncation-region block search, non-rigid TSDF integration and marching cubes. Graph generation samples the nodes from
+the first frame's extracted mesh on the GPU (`GraphGenerationMode.FIRST_FRAME_EXTRACTED_MESH`, the only mode that needs
+nothing but depth frames), uses the DeepDeformGraph file of the first frame (`FIRST_FRAME_LOADED_GRAPH`) or nodes supplied
+by the caller; the reference's depth-image graph builder and its rigid odometry (Open3D `rgbd_odometry_multi_scale`) are
+out of scope (the camera is static, identity extrinsics, as in the DeepDeform sequences).
 
 Deviations: the mesh-extraction ramp counts processed frames, not frame-index differences (DeepDeform test
 sequences ship sparse frames 300, 600, ...); the data and ARAP penalties default to SQUARE because the reference fitter's
@@ -36,6 +37,7 @@ from ..data.frame import FrameSequenceDataset
 from ..nnrt import geometry as G
 from ..nnrt import image_proc
 from ..nnrt.alignment import NDC_CONSISTENT
+from ..warp_field.graph_warp_field import sample_graph_nodes_from_mesh
 
 
 class TrackingMethod(enum.Enum):
@@ -51,7 +53,7 @@ class TrackingSpanMode(enum.Enum):
 
 
 class GraphGenerationMode(enum.Enum):
-    FIRST_FRAME_EXTRACTED_MESH = 0   # reference: build_deformation_graph_from_mesh -- not provided here
+    FIRST_FRAME_EXTRACTED_MESH = 0   # nodes sampled from the first frame's extracted mesh (build_deformation_graph_from_mesh)
     FIRST_FRAME_DEPTH_IMAGE = 1      # reference: graph_proc from the depth image -- not provided here
     FIRST_FRAME_LOADED_GRAPH = 2     # DeepDeformGraph .bin files of the first frame
     PROVIDED_NODES = 3               # nodes handed to FusionPipeline(nodes=...)
@@ -86,6 +88,8 @@ class FusionParameters:
     anchor_node_count: int = 4
     fusion_minimum_valid_anchor_count: int = 3
     graph_layer_count: int = 2   # the fitter's ARAP arrowhead configuration with reference parity (quirk A3)
+    graph_erosion_iteration_count: int = 10    # FIRST_FRAME_EXTRACTED_MESH (pipeline.py:518)
+    graph_erosion_min_neighbor_count: int = 4  # build_deformation_graph_from_mesh's default
     alignment: RenderingAlignmentParameters = field(default_factory=_default_alignment)
 
 
@@ -106,7 +110,7 @@ class FusionPipeline:
         self.parameters = p = parameters or FusionParameters()
         if p.tracking_method == TrackingMethod.NEURAL:
             raise NotImplementedError("TrackingMethod.NEURAL (DeformNet) is not part of this build; use TrackingMethod.RENDERING")
-        if p.graph_generation_mode in (GraphGenerationMode.FIRST_FRAME_EXTRACTED_MESH, GraphGenerationMode.FIRST_FRAME_DEPTH_IMAGE):
+        if p.graph_generation_mode == GraphGenerationMode.FIRST_FRAME_DEPTH_IMAGE:
             raise NotImplementedError(f"graph generation mode {p.graph_generation_mode.name} is not part of this build")
         if p.graph_generation_mode == GraphGenerationMode.PROVIDED_NODES and nodes is None:
             raise ValueError("GraphGenerationMode.PROVIDED_NODES needs nodes=")
@@ -124,6 +128,11 @@ class FusionPipeline:
         self.truncation_voxel_multiplier = p.sdf_truncation_distance / p.voxel_size
         self._provided_nodes = nodes
         self.active_graph: Optional[G.HierarchicalGraphWarpField] = None
+        # FIRST_FRAME_EXTRACTED_MESH: the mesh the nodes were sampled from and the nodes in sampling order (before
+        # make_warp_field's re-ordering), device tensors
+        self.graph_source_mesh = None
+        self.sampled_node_positions = None
+        self.sampled_node_vertex_indices = None
         self.optimizer = RenderingAlignmentOptimizer((self.intrinsics.height, self.intrinsics.width), self.device, self.K, p.alignment)
         self.canonical_mesh = None
         self.warped_mesh = None
@@ -165,6 +174,14 @@ class FusionPipeline:
             if name is None:
                 raise ValueError("no DeepDeformGraph file starts at the first frame")
             nodes = self.sequence.load_graph_data(name)[0]
+        elif p.graph_generation_mode == GraphGenerationMode.FIRST_FRAME_EXTRACTED_MESH:
+            # pipeline.py:514-520: the mesh at weight threshold 0, erosion_iteration_count = 10
+            self.graph_source_mesh = self.volume.extract_triangle_mesh(0.0, -1)
+            self.sampled_node_positions, self.sampled_node_vertex_indices = sample_graph_nodes_from_mesh(
+                self.graph_source_mesh, p.node_coverage, p.graph_erosion_iteration_count, p.graph_erosion_min_neighbor_count)
+            if self.sampled_node_positions.shape[0] == 0:
+                raise ValueError("no graph node was sampled from the first frame's mesh (empty or fully eroded)")
+            nodes = self.sampled_node_positions.cpu().numpy()
         else:
             nodes = np.asarray(self._provided_nodes, np.float32)
         self.active_graph = self.make_warp_field(nodes)

@@ -27,7 +27,8 @@ enum {
 	NNRT_ERROR_HIP = 2,
 	NNRT_ERROR_NOT_POSITIVE_DEFINITE = 3,   /* reference: NNRT_LAPACK_CHECK potrf failure -> RuntimeError */
 	NNRT_ERROR_UNSUPPORTED = 4,
-	NNRT_ERROR_CAPACITY = 5
+	NNRT_ERROR_CAPACITY = 5,
+	NNRT_ERROR_INTERNAL = 6                 /* an algorithm's own invariant failed (never expected; reported, not spun on) */
 };
 
 /* iteration modes: cpp/alignment/IterationMode.h:24-28 */
@@ -320,6 +321,28 @@ nnrt_status nnrt_matmul3d(const float* d_a, const float* d_b, int64_t batch, int
  * *h_sample_count receives the number written. Synchronizes `stream`. */
 nnrt_status nnrt_median_grid_subsample_3d_points(const float* d_points, int64_t point_count, float grid_cell_size, int64_t* d_out_indices,
                                                  int64_t* h_sample_count, void* stream);
+/* nnrt.get_vertex_erosion_mask(vertex_positions, face_indices, iteration_count, min_neighbors) (nnrt_pybind.cpp:121-123 ->
+ * cpp/cpu/graph_proc.cpp:27-90): faces start alive; iteration_count times, every alive face with a vertex touched by fewer
+ * than min_neighbors alive faces dies. d_out_mask [vertex_count] uint8 = 1 where an alive face touches the vertex.
+ * d_face_indices [face_count, 3] int64. A face index outside [0, vertex_count) gives NNRT_ERROR_ARGUMENT (the reference
+ * reads out of range); such a face is never dereferenced. vertex_count == 0 or face_count == 0 with nothing to write
+ * launches nothing; face_count == 0 zeroes the mask. Synchronizes `stream`. */
+nnrt_status nnrt_get_vertex_erosion_mask(int64_t vertex_count, const int64_t* d_face_indices, int64_t face_count, int32_t iteration_count,
+                                         int32_t min_neighbors, uint8_t* d_out_mask, void* stream);
+/* nnrt.sample_nodes(vertex_positions_in, vertex_erosion_mask_in, node_coverage, use_only_non_eroded_indices,
+ * random_shuffle) (nnrt_pybind.cpp:124-126 -> cpp/cpu/graph_proc.cpp:92-155): the greedy node set -- in priority order, a
+ * vertex becomes a node iff no earlier node q has ((dx*dx + dy*dy) + dz*dz) <= node_coverage * node_coverage (unfused
+ * f32) -- computed in parallel rounds, bit for bit the sequential result. d_points [point_count, 3] float32; d_mask
+ * [point_count] uint8 or NULL (use_only_non_eroded_indices = false); d_order [point_count] int64 permutation giving the
+ * priority order (the reference's shuffle) or NULL for ascending index; an entry outside [0, point_count) gives
+ * NNRT_ERROR_ARGUMENT. d_out_indices (capacity out_capacity >= point_count int64) receives the node vertex indices in
+ * acceptance order, *h_out_count their number, *h_out_rounds (nullable) the number of rounds taken. node_coverage must be
+ * positive and finite with a finite, normal square. Vertices with a non-finite coordinate are never candidates (in the
+ * reference such a vertex always becomes a node). NNRT_ERROR_ARGUMENT if the candidates span more than 2^21 - 3 cells of
+ * node_coverage along an axis; NNRT_ERROR_INTERNAL if a round decides nothing (never expected). Memory is
+ * O(point_count). Synchronizes `stream`. */
+nnrt_status nnrt_sample_nodes(const float* d_points, int64_t point_count, const uint8_t* d_mask, const int64_t* d_order, float node_coverage,
+                              int64_t* d_out_indices, int64_t out_capacity, int64_t* h_out_count, int32_t* h_out_rounds, void* stream);
 /* nnrt.core.linalg AxisAngleVectorsToMatricesRodrigues (cpp/core/linalg/RodriguesImpl.h:66-88) */
 nnrt_status nnrt_axis_angle_to_matrices_rodrigues(const float* d_vectors, int32_t count, float* d_matrices, void* stream);
 /* SolveBlockDiagonalCholesky (cpp/core/linalg/SolveBlockDiagonalCholesky.cpp): x_i = A_i^-1 b_i, block size 3 or 6 */
