@@ -6,6 +6,7 @@ Layout:
   nnrt/            mirror of the reference's `nnrt` Python module names on the hot path
   alignment/       mirror of alignment/render_based/RenderingAlignmentOptimizer (the reference's Python API slot)
   warp_field/      mirror of warp_field/graph_warp_field.py: the motion graph from a mesh (erosion + node sampling on the GPU)
+                   and from a masked depth image (depth mesh, geodesic edges, clean-up, clusters)
   synthetic.py     synthetic scenes for the BASELINE configs (C1-C5)
 """
 __all__ = ["nnrt", "alignment", "synthetic"]

@@ -113,6 +113,12 @@ _SIGNATURES = {
     "nnrt_median_grid_subsample_3d_points": (c_int32, [c_void_p, c_int64, c_float, c_void_p, c_void_p, c_void_p]),
     "nnrt_get_vertex_erosion_mask": (c_int32, [c_int64, c_void_p, c_int64, c_int32, c_int32, c_void_p, c_void_p]),
     "nnrt_sample_nodes": (c_int32, [c_void_p, c_int64, c_void_p, c_void_p, c_float, c_void_p, c_int64, c_void_p, c_void_p, c_void_p]),
+    "nnrt_compute_mesh_from_depth": (c_int32, [c_void_p, c_int32, c_int32, c_float, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_void_p,
+                                               c_void_p, c_void_p]),
+    "nnrt_compute_edges_shortest_path": (c_int32, [c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_int32, c_int32, c_float, c_int32,
+                                                   c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "nnrt_node_and_edge_clean_up": (c_int32, [c_void_p, c_int64, c_int32, c_void_p]),
+    "nnrt_compute_clusters": (c_int32, [c_void_p, c_int64, c_int32, c_void_p, c_void_p, c_void_p]),
     "nnrt_axis_angle_to_matrices_rodrigues": (c_int32, [c_void_p, c_int32, c_void_p, c_void_p]),
     "nnrt_compute_triangle_normals": (c_int32, [c_void_p, c_int64, c_void_p, c_int64, c_int32, c_void_p, c_void_p]),
     "nnrt_compute_vertex_normals": (c_int32, [c_void_p, c_int64, c_void_p, c_int64, c_int32, c_void_p, c_void_p]),

@@ -1751,6 +1751,68 @@ nnrt_status nnrt_sample_nodes(const float* d_points, int64_t point_count, const 
 	                           static_cast<hipStream_t>(stream));
 }
 
+nnrt_status nnrt_compute_mesh_from_depth(const float* d_point_image, int32_t height, int32_t width, float max_triangle_edge_distance,
+                                         float* d_out_vertices, int32_t* d_out_vertex_pixels, int64_t vertex_capacity, int32_t* d_out_faces,
+                                         int64_t face_capacity, int64_t* h_out_vertex_count, int64_t* h_out_face_count, void* stream) {
+	NNRT_CHECK_ARG(h_out_vertex_count && h_out_face_count, "null h_out_vertex_count or h_out_face_count");
+	NNRT_CHECK_ARG(height >= 0 && width >= 0, "negative image size");
+	NNRT_CHECK_ARG(static_cast<int64_t>(height) * width < (int64_t(1) << 29), "image size out of range");
+	NNRT_CHECK_ARG(vertex_capacity >= 0 && face_capacity >= 0, "negative vertex_capacity or face_capacity");
+	NNRT_CHECK_ARG(height == 0 || width == 0 || d_point_image, "null point image");
+	NNRT_CHECK_ARG(vertex_capacity == 0 || (d_out_vertices && d_out_vertex_pixels), "null vertex output");
+	NNRT_CHECK_ARG(face_capacity == 0 || d_out_faces, "null face output");
+	const size_t in_bytes = sizeof(float) * 3 * static_cast<size_t>(height) * static_cast<size_t>(width), nv = static_cast<size_t>(vertex_capacity),
+	             nf = static_cast<size_t>(face_capacity);
+	NNRT_CHECK_ARG(!(ranges_overlap(d_out_vertices, sizeof(float) * 3 * nv, d_point_image, in_bytes) ||
+	                 ranges_overlap(d_out_vertex_pixels, sizeof(int32_t) * 2 * nv, d_point_image, in_bytes) ||
+	                 ranges_overlap(d_out_faces, sizeof(int32_t) * 3 * nf, d_point_image, in_bytes)),
+	               "an output must not overlap d_point_image");
+	*h_out_vertex_count = 0;
+	*h_out_face_count = 0;
+	if (height < 2 || width < 2) return NNRT_OK;
+	return launch_mesh_from_depth(d_point_image, height, width, max_triangle_edge_distance, d_out_vertices, d_out_vertex_pixels, vertex_capacity,
+	                              d_out_faces, face_capacity, h_out_vertex_count, h_out_face_count, static_cast<hipStream_t>(stream));
+}
+
+nnrt_status nnrt_compute_edges_shortest_path(const float* d_vertices, int64_t vertex_count, const uint8_t* d_vertex_mask, const int32_t* d_faces,
+                                             int64_t face_count, const int32_t* d_node_vertex_indices, int32_t node_count,
+                                             int32_t max_neighbor_count, float node_coverage, int32_t enforce_total_num_neighbors,
+                                             int32_t* d_out_edges, float* d_out_weights, float* d_out_distances, int32_t* h_out_passes,
+                                             void* stream) {
+	NNRT_CHECK_ARG(vertex_count >= 0 && vertex_count < (int64_t(1) << 31) / 3, "vertex count out of range");
+	NNRT_CHECK_ARG(face_count >= 0 && face_count < (int64_t(1) << 31) / 6, "face count out of range");
+	NNRT_CHECK_ARG(node_count >= 0, "negative node count");
+	NNRT_CHECK_ARG(max_neighbor_count >= 1 && max_neighbor_count <= 1024, "max_neighbor_count must be in [1, 1024]");
+	NNRT_CHECK_ARG(static_cast<int64_t>(node_count) * max_neighbor_count < (int64_t(1) << 31), "node_count * max_neighbor_count out of range");
+	NNRT_CHECK_ARG(node_coverage > 0.f && std::isfinite(node_coverage), "node_coverage must be positive and finite");
+	NNRT_CHECK_ARG(vertex_count == 0 || d_vertices, "null vertices");
+	NNRT_CHECK_ARG(face_count == 0 || d_faces, "null faces");
+	NNRT_CHECK_ARG(node_count == 0 || (d_node_vertex_indices && d_out_edges && d_out_weights && d_out_distances), "null node indices or output");
+	if (h_out_passes) *h_out_passes = 0;
+	if (node_count == 0) return NNRT_OK;
+	return launch_edges_shortest_path(d_vertices, vertex_count, d_vertex_mask, d_faces, face_count, d_node_vertex_indices, node_count,
+	                                  max_neighbor_count, node_coverage, enforce_total_num_neighbors != 0, d_out_edges, d_out_weights,
+	                                  d_out_distances, h_out_passes, static_cast<hipStream_t>(stream));
+}
+
+nnrt_status nnrt_node_and_edge_clean_up(const int32_t* h_graph_edges, int64_t node_count, int32_t max_neighbor_count, uint8_t* h_valid_nodes_mask) {
+	NNRT_CHECK_ARG(node_count >= 0 && node_count < (int64_t(1) << 31), "node count out of range");
+	NNRT_CHECK_ARG(max_neighbor_count >= 0, "negative max_neighbor_count");
+	NNRT_CHECK_ARG(node_count == 0 || h_valid_nodes_mask, "null valid nodes mask");
+	NNRT_CHECK_ARG(node_count == 0 || max_neighbor_count == 0 || h_graph_edges, "null graph edges");
+	return node_and_edge_clean_up_host(h_graph_edges, node_count, max_neighbor_count, h_valid_nodes_mask);
+}
+
+nnrt_status nnrt_compute_clusters(const int32_t* h_graph_edges, int64_t node_count, int32_t max_neighbor_count, int32_t* h_out_clusters,
+                                  int32_t* h_out_cluster_sizes, int64_t* h_out_cluster_count) {
+	NNRT_CHECK_ARG(h_out_cluster_count, "null h_out_cluster_count");
+	NNRT_CHECK_ARG(node_count >= 0 && node_count < (int64_t(1) << 31), "node count out of range");
+	NNRT_CHECK_ARG(max_neighbor_count >= 0, "negative max_neighbor_count");
+	NNRT_CHECK_ARG(node_count == 0 || (h_out_clusters && h_out_cluster_sizes), "null cluster output");
+	NNRT_CHECK_ARG(node_count == 0 || max_neighbor_count == 0 || h_graph_edges, "null graph edges");
+	return compute_clusters_host(h_graph_edges, node_count, max_neighbor_count, h_out_clusters, h_out_cluster_sizes, h_out_cluster_count);
+}
+
 nnrt_status nnrt_matmul_block_sparse_row_wise(const float* d_a_blocks, int32_t a_block_count, const float* d_b_blocks,
                                               const int32_t* d_b_coordinates, int32_t b_block_count, int32_t block_size, float* d_c_blocks,
                                               uint8_t* d_c_mask, void* stream) {

@@ -111,6 +111,14 @@ nnrt_status launch_vertex_erosion_mask(int64_t V, const int64_t* faces, int64_t 
                                        int* error_flag, hipStream_t s);
 nnrt_status launch_sample_nodes(const float* pts, int64_t V, const uint8_t* mask, const int64_t* order, float coverage, int64_t* out,
                                 int64_t* h_count, int32_t* h_rounds, hipStream_t s);
+// depth_graph.hip: the motion graph from a depth image (cpp/cpu/image_proc.cpp:341-482, cpp/cpu/graph_proc.cpp:181-338, :540-636)
+nnrt_status launch_mesh_from_depth(const float* pts, int H, int W, float limit, float* vertices, int32_t* pixels, int64_t vertex_cap, int32_t* faces,
+                                   int64_t face_cap, int64_t* h_vertex_count, int64_t* h_face_count, hipStream_t s);
+nnrt_status launch_edges_shortest_path(const float* vertices, int64_t V, const uint8_t* mask, const int32_t* faces, int64_t F, const int32_t* node_vertex,
+                                       int N, int K, float coverage, bool enforce, int32_t* edges, float* weights, float* distances,
+                                       int32_t* h_passes, hipStream_t s);
+nnrt_status node_and_edge_clean_up_host(const int32_t* edges, int64_t N, int K, uint8_t* valid);
+nnrt_status compute_clusters_host(const int32_t* edges, int64_t N, int K, int32_t* clusters, int32_t* sizes, int64_t* cluster_count);
 nnrt_status launch_point_to_plane(const float* n1, const float* v1, const float* v2, int64_t count, float* out, hipStream_t stream);
 nnrt_status launch_interpolate(const int64_t* pixel_faces, const float* bary, int64_t P, int Kf, const float* attrs, int C, float* out,
                                hipStream_t stream);

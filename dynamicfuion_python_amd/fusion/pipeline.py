@@ -10,10 +10,12 @@ switch `FusionParameters.tracking_method` selects
 
 Per frame, everything stays on the GPU: depth/colour upload, back-projection, ordered-point-cloud normals, the GN fit,
 truncation-region block search, non-rigid TSDF integration and marching cubes. Graph generation samples the nodes from
-the first frame's extracted mesh on the GPU (`GraphGenerationMode.FIRST_FRAME_EXTRACTED_MESH`, the only mode that needs
-nothing but depth frames), uses the DeepDeformGraph file of the first frame (`FIRST_FRAME_LOADED_GRAPH`) or nodes supplied
-by the caller; the reference's depth-image graph builder and its rigid odometry (Open3D `rgbd_odometry_multi_scale`) are
-out of scope (the camera is static, identity extrinsics, as in the DeepDeform sequences).
+the first frame's extracted mesh on the GPU (`GraphGenerationMode.FIRST_FRAME_EXTRACTED_MESH`), builds the reference's
+default graph from the first masked depth image on the GPU (`FIRST_FRAME_DEPTH_IMAGE` together with
+`FusionParameters.graph_from_depth_image=True`: pixel-connected mesh, erosion, node sampling, geodesic edges, clean-up,
+clusters) -- both need nothing but depth frames --, uses the DeepDeformGraph file of the
+first frame (`FIRST_FRAME_LOADED_GRAPH`) or nodes supplied by the caller; the reference's rigid odometry (Open3D
+`rgbd_odometry_multi_scale`) is out of scope (the camera is static, identity extrinsics, as in the DeepDeform sequences).
 
 Deviations: the mesh-extraction ramp counts processed frames, not frame-index differences (DeepDeform test
 sequences ship sparse frames 300, 600, ...); the data and ARAP penalties default to SQUARE because the reference fitter's
@@ -37,7 +39,7 @@ from ..data.frame import FrameSequenceDataset
 from ..nnrt import geometry as G
 from ..nnrt import image_proc
 from ..nnrt.alignment import NDC_CONSISTENT
-from ..warp_field.graph_warp_field import sample_graph_nodes_from_mesh
+from ..warp_field.graph_warp_field import build_graph_nodes_from_depth_image, sample_graph_nodes_from_mesh
 
 
 class TrackingMethod(enum.Enum):
@@ -54,7 +56,8 @@ class TrackingSpanMode(enum.Enum):
 
 class GraphGenerationMode(enum.Enum):
     FIRST_FRAME_EXTRACTED_MESH = 0   # nodes sampled from the first frame's extracted mesh (build_deformation_graph_from_mesh)
-    FIRST_FRAME_DEPTH_IMAGE = 1      # reference: graph_proc from the depth image -- not provided here
+    FIRST_FRAME_DEPTH_IMAGE = 1      # the reference's default: the graph of the first masked depth image (create_graph_data.py:27-296);
+                                     # needs FusionParameters.graph_from_depth_image=True
     FIRST_FRAME_LOADED_GRAPH = 2     # DeepDeformGraph .bin files of the first frame
     PROVIDED_NODES = 3               # nodes handed to FusionPipeline(nodes=...)
 
@@ -90,6 +93,17 @@ class FusionParameters:
     graph_layer_count: int = 2   # the fitter's ARAP arrowhead configuration with reference parity (quirk A3)
     graph_erosion_iteration_count: int = 10    # FIRST_FRAME_EXTRACTED_MESH (pipeline.py:518)
     graph_erosion_min_neighbor_count: int = 4  # build_deformation_graph_from_mesh's default
+    # FIRST_FRAME_DEPTH_IMAGE (settings/graph.py). The mode is opt-in: without graph_from_depth_image=True the pipeline
+    # refuses it at construction, as it did before the depth-image builder existed.
+    graph_from_depth_image: bool = False
+    graph_max_triangle_distance: float = 0.05
+    graph_depth_image_erosion_iteration_count: int = 4
+    graph_depth_image_erosion_min_neighbor_count: int = 4
+    graph_neighbor_count: int = 8
+    graph_enforce_neighbor_count: bool = False
+    graph_remove_nodes_with_too_few_neighbors: bool = True
+    graph_use_only_valid_vertices: bool = True
+    graph_sample_random_shuffle: bool = False
     alignment: RenderingAlignmentParameters = field(default_factory=_default_alignment)
 
 
@@ -110,8 +124,9 @@ class FusionPipeline:
         self.parameters = p = parameters or FusionParameters()
         if p.tracking_method == TrackingMethod.NEURAL:
             raise NotImplementedError("TrackingMethod.NEURAL (DeformNet) is not part of this build; use TrackingMethod.RENDERING")
-        if p.graph_generation_mode == GraphGenerationMode.FIRST_FRAME_DEPTH_IMAGE:
-            raise NotImplementedError(f"graph generation mode {p.graph_generation_mode.name} is not part of this build")
+        if p.graph_generation_mode == GraphGenerationMode.FIRST_FRAME_DEPTH_IMAGE and not p.graph_from_depth_image:
+            raise NotImplementedError(f"graph generation mode {p.graph_generation_mode.name} runs only with "
+                                      "FusionParameters.graph_from_depth_image=True (the depth-image graph builder on the GPU)")
         if p.graph_generation_mode == GraphGenerationMode.PROVIDED_NODES and nodes is None:
             raise ValueError("GraphGenerationMode.PROVIDED_NODES needs nodes=")
         self.sequence = sequence if sequence._loaded else sequence.load()
@@ -128,11 +143,15 @@ class FusionPipeline:
         self.truncation_voxel_multiplier = p.sdf_truncation_distance / p.voxel_size
         self._provided_nodes = nodes
         self.active_graph: Optional[G.HierarchicalGraphWarpField] = None
-        # FIRST_FRAME_EXTRACTED_MESH: the mesh the nodes were sampled from and the nodes in sampling order (before
-        # make_warp_field's re-ordering), device tensors
+        # FIRST_FRAME_EXTRACTED_MESH / FIRST_FRAME_DEPTH_IMAGE: the mesh the nodes were sampled from and the nodes in
+        # sampling order (before make_warp_field's re-ordering; DEPTH_IMAGE: after the clean-up), device tensors
         self.graph_source_mesh = None
         self.sampled_node_positions = None
         self.sampled_node_vertex_indices = None
+        # FIRST_FRAME_DEPTH_IMAGE: the DepthImageGraph, its edges / weights / distances and its clusters
+        self.depth_image_graph = None
+        self.geodesic_edges = None
+        self.graph_clusters = None
         self.optimizer = RenderingAlignmentOptimizer((self.intrinsics.height, self.intrinsics.width), self.device, self.K, p.alignment)
         self.canonical_mesh = None
         self.warped_mesh = None
@@ -167,7 +186,8 @@ class FusionPipeline:
             return p.mesh_extraction_weight_threshold
         return min(self.processed_frames - 1, p.mesh_extraction_weight_threshold)
 
-    def _initialize_graph(self):
+    def _initialize_graph(self, depth=None):
+        """`depth`: the first frame's depth on the device, masked and clipped (FIRST_FRAME_DEPTH_IMAGE)."""
         p = self.parameters
         if p.graph_generation_mode == GraphGenerationMode.FIRST_FRAME_LOADED_GRAPH:
             name = self.sequence.get_current_graph_name()
@@ -182,6 +202,20 @@ class FusionPipeline:
             if self.sampled_node_positions.shape[0] == 0:
                 raise ValueError("no graph node was sampled from the first frame's mesh (empty or fully eroded)")
             nodes = self.sampled_node_positions.cpu().numpy()
+        elif p.graph_generation_mode == GraphGenerationMode.FIRST_FRAME_DEPTH_IMAGE:
+            # pipeline.py:522-540 with settings/graph.py; the warp field's own edges come from the hierarchy
+            g = build_graph_nodes_from_depth_image(
+                depth, None, self.K, max_triangle_distance=p.graph_max_triangle_distance, depth_scale_reciprocal=p.depth_scale,
+                erosion_num_iterations=p.graph_depth_image_erosion_iteration_count,
+                erosion_min_neighbors=p.graph_depth_image_erosion_min_neighbor_count,
+                remove_nodes_with_too_few_neighbors=p.graph_remove_nodes_with_too_few_neighbors,
+                use_only_valid_vertices=p.graph_use_only_valid_vertices, sample_random_shuffle=p.graph_sample_random_shuffle,
+                neighbor_count=p.graph_neighbor_count, enforce_neighbor_count=p.graph_enforce_neighbor_count, node_coverage=p.node_coverage)
+            self.depth_image_graph = g
+            self.graph_source_mesh = G.TriangleMesh(g.vertices, None, g.faces.to(torch.int64))
+            self.sampled_node_positions, self.sampled_node_vertex_indices = g.node_positions, g.node_vertex_indices
+            self.geodesic_edges, self.graph_clusters = g.edges, g.clusters
+            nodes = g.node_positions.cpu().numpy()
         else:
             nodes = np.asarray(self._provided_nodes, np.float32)
         self.active_graph = self.make_warp_field(nodes)
@@ -224,7 +258,7 @@ class FusionPipeline:
                                                                   self.truncation_voxel_multiplier)
             self.volume.integrate(blocks, depth, color, self.K, self.K, self.extrinsics, p.depth_scale, depth_max,
                                   self.truncation_voxel_multiplier)
-            self._initialize_graph()
+            self._initialize_graph(depth)
             res.new_block_count = int(blocks.shape[0])
         else:
             # track: fit the canonical mesh extracted at the end of the previous frame to this frame's depth (the

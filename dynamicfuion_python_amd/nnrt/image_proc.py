@@ -56,6 +56,41 @@ def backproject_depth_float(image_in, fx: float, fy: float, cx: float, cy: float
     return out
 
 
+def compute_mesh_from_depth(point_image, max_triangle_edge_distance):
+    """compute_mesh_from_depth (nnrt_pybind.cpp:79-80 -> image_proc.cpp:341-482; csrc/depth_graph.hip): the pixel-connected
+    mesh of an [H, W, 3] float32 point image as (vertices (V, 3) float32, vertex_pixels (V, 2) int32 as (x, y), faces (F, 3)
+    int32), device tensors, equal to the reference's sequential loop bit for bit (vertex numbering and face order included).
+    An image with H < 2 or W < 2, or without a valid triangle, gives empty tensors (the reference leaves its outputs
+    unsized). Input that is not [H, W, 3] float32 is refused."""
+    N.require_gpu()
+    dev = device_of(N.current_device())
+    if isinstance(point_image, np.ndarray):
+        if point_image.dtype != np.float32:
+            raise ValueError(f"point image must be float32, got {point_image.dtype}")
+        p = torch.from_numpy(np.ascontiguousarray(point_image))
+    elif isinstance(point_image, torch.Tensor):
+        if point_image.dtype != torch.float32:
+            raise ValueError(f"point image must be float32, got {point_image.dtype}")
+        p = point_image
+    else:
+        raise ValueError("point image must be a numpy array or a torch tensor")
+    if p.dim() != 3 or p.shape[2] != 3:
+        raise ValueError(f"point image must be [H, W, 3], got {tuple(p.shape)}")
+    p = p.to(dev).contiguous()
+    H, W = int(p.shape[0]), int(p.shape[1])
+    vertex_capacity = H * W if H >= 2 and W >= 2 else 0
+    face_capacity = 2 * (H - 1) * (W - 1) if vertex_capacity else 0
+    vertices = torch.empty((vertex_capacity, 3), dtype=torch.float32, device=dev)
+    pixels = torch.empty((vertex_capacity, 2), dtype=torch.int32, device=dev)
+    faces = torch.empty((face_capacity, 3), dtype=torch.int32, device=dev)
+    counts = np.zeros(2, np.int64)
+    N.check(N.lib().nnrt_compute_mesh_from_depth(N.ptr(p), H, W, float(max_triangle_edge_distance), N.ptr(vertices), N.ptr(pixels),
+                                                 vertex_capacity, N.ptr(faces), face_capacity, N.ptr(counts[0:1]), N.ptr(counts[1:2]),
+                                                 N.stream_ptr()))
+    nv, nf = int(counts[0]), int(counts[1])
+    return vertices[:nv].clone(), pixels[:nv].clone(), faces[:nf].clone()
+
+
 def backproject_depth(depth_image, fx, fy, cx, cy, depth_scale: float = 1000.0) -> torch.Tensor:
     """image_processing/__init__.py:333-344: float32 depth is taken as metres, anything else as integer units / depth_scale."""
     is_float = (isinstance(depth_image, np.ndarray) and depth_image.dtype == np.float32) or \

@@ -1,11 +1,15 @@
 """Motion graph from a mesh (reference warp_field/graph_warp_field.py:24-42): erode the mesh's border vertices, sample the
 graph nodes greedily from the remaining vertices, build the warp field over them -- all on the GPU
-(csrc/graph_sampling.hip, csrc/hierarchy.hip).
+(csrc/graph_sampling.hip, csrc/hierarchy.hip); and the graph from a masked depth image (reference
+apps/create_graph_data.py:27-296): pixel-connected mesh, erosion, node sampling, geodesic edges, clean-up and clusters
+(csrc/depth_graph.hip).
 """
 from __future__ import annotations
 
-from typing import Optional, Tuple
+from dataclasses import dataclass
+from typing import List, Optional, Tuple
 
+import numpy as np
 import torch
 
 from .. import nnrt
@@ -39,3 +43,95 @@ def build_deformation_graph_from_mesh(mesh: G.TriangleMesh, node_coverage: float
                          f"({erosion_iteration_count} iterations, min_neighbors {erosion_min_neighbor_count})")
     return G.HierarchicalGraphWarpField(nodes, node_coverage=node_coverage, anchor_count=anchor_count,
                                         minimum_valid_anchor_count=minimum_valid_anchor_count, layer_count=layer_count, device=device)
+
+
+@dataclass
+class DepthImageGraph:
+    """What build_graph_nodes_from_depth_image computes; device tensors, nodes in sampling order with the removed ones
+    dropped."""
+    vertices: torch.Tensor              # (V, 3) float32: the depth mesh
+    vertex_pixels: torch.Tensor         # (V, 2) int32 as (x, y)
+    faces: torch.Tensor                 # (F, 3) int32
+    non_eroded_vertices: torch.Tensor   # (V, 1) bool
+    node_positions: torch.Tensor        # (N, 3) float32
+    node_vertex_indices: torch.Tensor   # (N, 1) int32
+    edges: torch.Tensor                 # (N, K) int32, -1 in unused slots
+    edge_weights: torch.Tensor          # (N, K) float32
+    edge_distances: torch.Tensor        # (N, K) float32
+    clusters: torch.Tensor              # (N, 1) int32
+    cluster_sizes: List[int]
+
+
+def build_graph_nodes_from_depth_image(depth, mask, intrinsic_matrix, max_triangle_distance: float = 0.05,
+                                       depth_scale_reciprocal: float = 1000.0, erosion_num_iterations: int = 10,
+                                       erosion_min_neighbors: int = 4, remove_nodes_with_too_few_neighbors: bool = True,
+                                       use_only_valid_vertices: bool = True, sample_random_shuffle: bool = False, neighbor_count: int = 8,
+                                       enforce_neighbor_count: bool = True, node_coverage: float = 0.05, **unsupported) -> DepthImageGraph:
+    """build_graph_warp_field_from_depth_image (apps/create_graph_data.py:27-296) up to the graph itself, with the
+    reference's keyword arguments and defaults (`scene_flow_path` is refused, `enable_visual_debugging` does not exist;
+    `node_coverage` is honoured -- the reference overwrites it with its global setting). `depth` is an (H, W) integer depth
+    image in 1 / depth_scale_reciprocal metres or a float32 one in metres, `mask` an (H, W) image that is non-zero on the
+    object or None for a depth image that is masked already; numpy arrays or tensors. Steps :60-285: mask the depth,
+    back-project, pixel-connected mesh, erosion mask, node sampling, geodesic edges over every vertex, clean-up of nodes
+    with at most one neighbour, compaction and re-indexing of the rows (removed neighbours dropped, entries shifted left,
+    weights renormalized), clusters. The pixel anchors (:183-187) are not computed. Raises ValueError for an empty mesh, a
+    graph without nodes or a cluster of at most two nodes (the reference asserts, calls exit() or raises)."""
+    if unsupported:
+        if "scene_flow_path" in unsupported:
+            raise ValueError("scene_flow_path is not supported: the graph is built from depth alone")
+        raise TypeError(f"unexpected keyword arguments {sorted(unsupported)}")
+    K = np.asarray(intrinsic_matrix, np.float64)
+    fx, fy, cx, cy = K[0, 0], K[1, 1], K[0, 2], K[1, 2]
+    if mask is not None:
+        if isinstance(depth, torch.Tensor):
+            keep = torch.as_tensor(mask, device=depth.device) > 0
+            bits = depth.view(torch.int16) if depth.dtype == torch.uint16 else depth
+            depth = torch.where(keep, bits, torch.zeros_like(bits)).view(depth.dtype)
+        else:
+            keep = (mask.detach().cpu().numpy() if isinstance(mask, torch.Tensor) else np.asarray(mask)) > 0
+            depth = np.where(keep, depth, np.zeros_like(depth))
+    point_image = nnrt.image_proc.backproject_depth(depth, fx, fy, cx, cy, depth_scale_reciprocal)
+    vertices, vertex_pixels, faces = nnrt.compute_mesh_from_depth(point_image, max_triangle_distance)
+    if vertices.shape[0] == 0:
+        raise ValueError("the depth image yields no mesh: no triangle with three valid depths and edges within max_triangle_distance")
+    non_eroded = nnrt.get_vertex_erosion_mask(vertices, faces, erosion_num_iterations, erosion_min_neighbors)
+    node_positions, node_indices = nnrt.sample_nodes(vertices, non_eroded, node_coverage, use_only_valid_vertices, sample_random_shuffle)
+    node_count = node_positions.shape[0]
+    if node_count == 0:
+        raise ValueError("no graph node was sampled from the depth image (the mesh erodes to nothing)")
+    # :154-160: every vertex is visible
+    edges, weights, distances, _ = nnrt.compute_edges_shortest_path(vertices, faces, node_indices, neighbor_count, node_coverage,
+                                                                    enforce_neighbor_count)
+    valid = torch.ones((node_count, 1), dtype=torch.bool, device=edges.device)
+    if remove_nodes_with_too_few_neighbors:
+        nnrt.node_and_edge_clean_up(edges, valid)
+    keep = valid.reshape(-1)
+    if not bool(keep.any()):
+        raise ValueError("no graph node is left after removing the nodes with at most one neighbour")
+    if not bool(keep.all()):
+        # :221-272: rows of the kept nodes; entries naming a removed node dropped, the rest shifted left (a stable sort
+        # on "dropped"), ids re-mapped, weights divided by their row sum
+        new_id = torch.where(keep, torch.cumsum(keep.to(torch.int64), 0) - 1, torch.full_like(keep, -1, dtype=torch.int64))
+        edges, weights, distances = edges[keep], weights[keep], distances[keep]
+        named = edges >= 0
+        dropped = named & ~keep[edges.clamp(min=0).to(torch.int64)]
+        order = torch.sort(dropped.to(torch.int8), dim=1, stable=True).indices
+        mapped = torch.where(named, new_id[edges.clamp(min=0).to(torch.int64)], torch.full_like(edges, -1, dtype=torch.int64))
+        mapped = torch.where(dropped, torch.full_like(mapped, -1), mapped).to(torch.int32)
+        weights = torch.where(dropped, torch.zeros_like(weights), weights)
+        distances = torch.where(dropped, torch.zeros_like(distances), distances)
+        edges = torch.gather(mapped, 1, order)
+        weights = torch.gather(weights, 1, order)
+        distances = torch.gather(distances, 1, order)
+        sums = weights.sum(dim=1, keepdim=True)
+        if not bool((sums > 0).all()):
+            raise ValueError("weight sum for node anchors is not positive after removing nodes")
+        weights = weights / sums
+        node_positions, node_indices = node_positions[keep], node_indices[keep]
+    cluster_sizes, clusters = nnrt.compute_clusters(edges)
+    for i, size in enumerate(cluster_sizes):
+        if size <= 2:
+            members = torch.nonzero(clusters.reshape(-1) == i).reshape(-1).tolist()
+            raise ValueError(f"cluster is too small: {size}, it only has nodes {members}")
+    return DepthImageGraph(vertices, vertex_pixels, faces, non_eroded, node_positions, node_indices, edges, weights, distances, clusters,
+                           cluster_sizes)

@@ -343,6 +343,53 @@ nnrt_status nnrt_get_vertex_erosion_mask(int64_t vertex_count, const int64_t* d_
  * O(point_count). Synchronizes `stream`. */
 nnrt_status nnrt_sample_nodes(const float* d_points, int64_t point_count, const uint8_t* d_mask, const int64_t* d_order, float node_coverage,
                               int64_t* d_out_indices, int64_t out_capacity, int64_t* h_out_count, int32_t* h_out_rounds, void* stream);
+/* nnrt.compute_mesh_from_depth(point_image, max_triangle_edge_distance) (nnrt_pybind.cpp:79-80 -> cpp/cpu/image_proc.cpp:341-482):
+ * the pixel-connected mesh of d_point_image [height, width, 3] float32. The 2x2 pixel cell at (x, y) emits triangle
+ * (00, 01, 10) if all three points have z > 0 (NaN is invalid) and all three edges have
+ * sqrtf((dx*dx + dy*dy) + dz*dz) <= max_triangle_edge_distance (unfused f32), then triangle (11, 10, 01) under the same
+ * test; a vertex is numbered the first time a valid triangle touches its pixel, cells in row-major order -- computed with
+ * two scans, bit for bit the sequential result, numbering and face order included. d_out_vertices [vertex_capacity, 3]
+ * float32, d_out_vertex_pixels [vertex_capacity, 2] int32 as (x, y), d_out_faces [face_capacity, 3] int32;
+ * *h_out_vertex_count and *h_out_face_count receive the numbers written. height * width vertices and
+ * 2 (height - 1)(width - 1) faces always suffice; a capacity the mesh exceeds gives NNRT_ERROR_ARGUMENT and nothing is
+ * written. height < 2, width < 2 or no valid triangle gives two zero counts and launches nothing that indexes the outputs
+ * (the reference leaves its output arrays unsized then). Synchronizes `stream`. */
+nnrt_status nnrt_compute_mesh_from_depth(const float* d_point_image, int32_t height, int32_t width, float max_triangle_edge_distance,
+                                         float* d_out_vertices, int32_t* d_out_vertex_pixels, int64_t vertex_capacity, int32_t* d_out_faces,
+                                         int64_t face_capacity, int64_t* h_out_vertex_count, int64_t* h_out_face_count, void* stream);
+/* nnrt.compute_edges_shortest_path(vertex_positions_in, [vertex_mask_in,] face_indices_in, node_indices_in, max_neighbor_count,
+ * node_coverage, enforce_total_num_neighbors) (nnrt_pybind.cpp:143-153 -> cpp/cpu/graph_proc.cpp:181-338): per node i with
+ * vertex d_node_vertex_indices[i], D_i(v) is the float32 shortest-path length over the mesh edges, every relaxation
+ * d_u + sqrtf((dx*dx + dy*dy) + dz*dz) in unfused f32 -- the values of the reference's Dijkstra, found by parallel relaxation
+ * to the same fixed point. A vertex with d_vertex_mask[v] == 0 is never entered (NULL mask: every vertex; the node's own
+ * vertex is the start whatever its mask). enforce_total_num_neighbors == 0: a vertex is entered only at
+ * D <= 2 * node_coverage; otherwise the radius doubles for the nodes that have fewer than max_neighbor_count neighbours
+ * and were stopped by it, until none is left. Row i of d_out_edges [node_count, max_neighbor_count] int32 holds the other
+ * nodes whose vertex was reached, by ascending D (equal D: by ascending node index; the reference orders ties by its
+ * heap's state), unused slots -1; d_out_distances their D, unused 0; d_out_weights exp(-(D*D) / (2 c c)) divided by the
+ * row's left-to-right sum (by the count if the sum is 0), unused 0. A negative node vertex index gives an all-default
+ * row. The reference's dense node_count x vertex_count distance matrix is not produced. d_faces [face_count, 3] int32; a
+ * face index outside [0, vertex_count), a node vertex index >= vertex_count or two nodes on one vertex give
+ * NNRT_ERROR_ARGUMENT (the reference reads out of range / keeps the later node). max_neighbor_count in [1, 1024].
+ * *h_out_passes (nullable) receives the number of radius passes. Scratch: 20 bytes per vertex per concurrently processed
+ * node, at most 1 GiB. Synchronizes `stream`. */
+nnrt_status nnrt_compute_edges_shortest_path(const float* d_vertices, int64_t vertex_count, const uint8_t* d_vertex_mask, const int32_t* d_faces,
+                                             int64_t face_count, const int32_t* d_node_vertex_indices, int32_t node_count,
+                                             int32_t max_neighbor_count, float node_coverage, int32_t enforce_total_num_neighbors,
+                                             int32_t* d_out_edges, float* d_out_weights, float* d_out_distances, int32_t* h_out_passes,
+                                             void* stream);
+/* nnrt.node_and_edge_clean_up(graph_edges, valid_nodes_mask) (nnrt_pybind.cpp:219-220 -> graph_proc.cpp:540-590), host code on
+ * host arrays: h_valid_nodes_mask [node_count] uint8 is cleared for every valid node of which at most one entry before its
+ * row's first -1 names a node not removed by this call, repeated to the fixed point (which does not depend on the visiting
+ * order). h_graph_edges [node_count, max_neighbor_count] int32; an entry outside [-1, node_count) gives
+ * NNRT_ERROR_ARGUMENT. */
+nnrt_status nnrt_node_and_edge_clean_up(const int32_t* h_graph_edges, int64_t node_count, int32_t max_neighbor_count, uint8_t* h_valid_nodes_mask);
+/* nnrt.compute_clusters(graph_edges_in) (nnrt_pybind.cpp:222-225 -> graph_proc.cpp:510-636), host code on host arrays: the
+ * connected components of the undirected graph over each row's entries up to its first -1, numbered by ascending lowest
+ * member. h_out_clusters [node_count] int32, h_out_cluster_sizes (room for node_count int32), *h_out_cluster_count. An entry
+ * outside [-1, node_count) before a row's first -1 gives NNRT_ERROR_ARGUMENT. */
+nnrt_status nnrt_compute_clusters(const int32_t* h_graph_edges, int64_t node_count, int32_t max_neighbor_count, int32_t* h_out_clusters,
+                                  int32_t* h_out_cluster_sizes, int64_t* h_out_cluster_count);
 /* nnrt.core.linalg AxisAngleVectorsToMatricesRodrigues (cpp/core/linalg/RodriguesImpl.h:66-88) */
 nnrt_status nnrt_axis_angle_to_matrices_rodrigues(const float* d_vectors, int32_t count, float* d_matrices, void* stream);
 /* SolveBlockDiagonalCholesky (cpp/core/linalg/SolveBlockDiagonalCholesky.cpp): x_i = A_i^-1 b_i, block size 3 or 6 */
