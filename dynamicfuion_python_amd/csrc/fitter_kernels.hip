@@ -43,8 +43,6 @@ __device__ inline int pix_quadrant(const FitPixelArgs& a) {
 	return ((b % 8) * per_xcd + b / 8) * PIX_WAVES + static_cast<int>(threadIdx.x >> 6);
 }
 
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-
 template <int MODE>
 struct ModeTraits;
 template <>
@@ -762,16 +760,11 @@ __device__ __forceinline__ void node_body(const FitPixelArgs& a, float* slots0, 
 		for (int j = 0; j < SEG; j += NG_BATCH) {
 			// every LDS read of the batch is issued before the dependent double adds
 			const float* base = slots + grp * SEG + j;
-			// the products two slots at a time (v_pk_mul_f32: the same correctly rounded float products)
+			// one v_mul_f32 per slot: the launch is bound by instruction issue, and a v_pk_mul_f32 of two slots measured
+			// slower than the two scalar multiplies (the same correctly rounded float products)
 			float prod[NG_BATCH];
 #pragma unroll
-			for (int q = 0; q < NG_BATCH; q += 2) {
-				const f32x2 x = {base[c0 * NG_STRIDE + q], base[c0 * NG_STRIDE + q + 1]};
-				const f32x2 y = {base[c1 * NG_STRIDE + q], base[c1 * NG_STRIDE + q + 1]};
-				const f32x2 pr = x * y;
-				prod[q] = pr.x;
-				prod[q + 1] = pr.y;
-			}
+			for (int q = 0; q < NG_BATCH; q++) prod[q] = base[c0 * NG_STRIDE + q] * base[c1 * NG_STRIDE + q];
 			// every node of a chunk forms ONE contiguous run (grouping files all of a node's pending associations at once;
 			// only a chunk's capacity splits it, into the next chunk), so a batch is a single node iff its first and last
 			// slots are: two node reads instead of one per slot. A single-node batch whose node differs from `cur` (a
@@ -840,7 +833,9 @@ __device__ __forceinline__ void node_body(const FitPixelArgs& a, float* slots0, 
 		jacobians(cur_slots, count);
 		wave_sync();
 		PHASE_ADD(1);
+#ifndef NNRT_DEV_SKIP_SUMS   // timing build only: pass 2 without (3) (instruction counts per phase by difference)
 		sums(cur_slots, count);
+#endif
 		wave_sync();
 		PHASE_ADD(2);
 #ifdef NNRT_FIT_STAMPS
