@@ -66,6 +66,8 @@ _SIGNATURES = {
                                            c_int32, c_int32, c_void_p, c_void_p, c_float, c_void_p]),
     "nnrt_fitter_prepare": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p,
                                       c_int32, c_int32, c_void_p, c_void_p, c_float, c_void_p]),
+    "nnrt_fit_quad_order_blocks": (c_int32, [c_int32]),
+    "nnrt_fit_quad_order_table": (c_int32, [c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p]),
     "nnrt_fitter_prepare_point_cloud": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p,
                                                   c_int32, c_int32, c_void_p, c_void_p, c_void_p]),
     "nnrt_fitter_fit_to_point_cloud": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p,

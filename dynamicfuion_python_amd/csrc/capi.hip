@@ -384,6 +384,9 @@ struct nnrt_fitter {
 	DeviceBuffer<float4> ref_points;   // [P] reference point (x, y, z, valid)
 	DeviceBuffer<int> tile_flags, tile_order;   // the pixel launch's per-frame workgroup -> tile table (launch_tile_order)
 	bool use_tile_order = false;
+	DeviceBuffer<int> quad_scratch, quad_order;   // the same per 8 x 8 quadrant, one entry per wave (launch_quad_order)
+	bool use_quad_order = false;
+	int quad_slots = 0;   // the pixel launch's wave slots at four waves per SIMD (launch_quad_order's overflow bound)
 	bool pix_low_occupancy = false;   // the pixel launch's 4-waves-per-SIMD build (launches of several residency rounds)
 	DeviceBuffer<float4> records;      // [P, 4] pixel Jacobian records
 	DeviceBuffer<uint64_t> keys;
@@ -530,7 +533,10 @@ nnrt_status enqueue_iteration(nnrt_fitter* ft, const nnrt_warp_field* wf, int mo
 	fa.cmesh_n = ft->mesh_n4.ptr;
 	fa.weights = ft->weights.ptr;
 	fa.ref_points = ft->ref_points.ptr;
-	if (ft->use_tile_order) {
+	if (ft->use_quad_order) {
+		fa.quad_order = ft->quad_order.ptr;
+		fa.order_blocks = quad_order_blocks(4 * fa.tiles_x * fa.tiles_y);
+	} else if (ft->use_tile_order) {
 		fa.tile_order = ft->tile_order.ptr;
 		fa.order_blocks = tile_order_blocks(fa.tiles_x * fa.tiles_y);
 	}
@@ -650,6 +656,8 @@ void nnrt_fitter_destroy(nnrt_fitter* ft) {
 	ft->ref_points.release();
 	ft->tile_flags.release();
 	ft->tile_order.release();
+	ft->quad_scratch.release();
+	ft->quad_order.release();
 	ft->records.release();
 	for (auto* b : {&ft->mesh_p, &ft->mesh_n, &ft->weights, &ft->residuals, &ft->edge_jr, &ft->updates, &ft->gradient,
 	                &ft->hessian, &ft->wing, &ft->edge_residuals, &ft->a_diag, &ft->a_dinv, &ft->a_dinvb, &ft->a_rhs, &ft->a_x, &ft->a_res, &ft->a_dx})
@@ -719,7 +727,7 @@ nnrt_status prepare_frame(nnrt_fitter* ft, nnrt_warp_field* wf, const float* d_v
 	}
 	// (re)allocate; any reallocation invalidates captured graphs
 	const auto before = std::make_tuple(ft->mesh_p.ptr, ft->faces4.ptr, ft->anchors.ptr, ft->keys.ptr, ft->acc.ptr, ft->wing.ptr, ft->corner.generation,
-	                                    ft->face_nodes.ptr, ft->wpos.ptr, ft->mesh_p4.ptr, ft->tile_order.ptr, ft->anchors16.ptr);
+	                                    ft->face_nodes.ptr, ft->wpos.ptr, ft->mesh_p4.ptr, ft->tile_order.ptr, ft->quad_order.ptr, ft->anchors16.ptr);
 	nnrt_status st;
 	if ((st = ft->mesh_p.ensure(3 * V)) || (st = ft->mesh_n.ensure(3 * V)) || (st = ft->faces4.ensure(F)) ||
 	    (st = ft->anchors.ensure(static_cast<size_t>(V) * K)) || (st = ft->weights.ensure(static_cast<size_t>(V) * K)) ||
@@ -735,13 +743,14 @@ nnrt_status prepare_frame(nnrt_fitter* ft, nnrt_warp_field* wf, const float* d_v
 		return st;
 	// the pixel launch's per-frame tile order, for launches of more than one residency round (5 waves per SIMD): their
 	// last round's workgroups decide the tail, and the order gives those the tiles without reference pixels (C3 fused
-	// launch 214 -> 197 us). In one round every wave starts at once and the table load only delays it (C2 40.2 -> 41.8).
+	// launch 214 -> 197 us). In one round every wave starts at once and whole tiles are too coarse to change which SIMDs
+	// carry the most working waves (C2 40.2 -> 41.8 with the tile table): those launches take the quadrant table below.
 	// NNRT_TILE_ORDER=0: never, =2: always.
 	const size_t tiles = static_cast<size_t>(ceil_div(W, 16)) * static_cast<size_t>(ceil_div(H, 16));
 	int cus = 0;
 	if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, ft->device) != hipSuccess || cus <= 0) cus = 256;
 	const bool multi_round = 4 * tiles > static_cast<size_t>(5 * 4 * cus);
-	const bool tile_order = fit_pixels_tile_order_supported() && [&] {
+	const bool tile_order_wanted = fit_pixels_tile_order_supported() && [&] {
 		const char* v = std::getenv("NNRT_TILE_ORDER");
 		if (v && *v == '0') return false;
 		if (v && *v == '2') return true;
@@ -755,7 +764,23 @@ nnrt_status prepare_frame(nnrt_fitter* ft, nnrt_warp_field* wf, const float* d_v
 		if (v) return *v == '1';
 		return multi_round;
 	}();
+	// launches of one residency round take the quadrant-granular table instead: their length follows the SIMDs that
+	// hold five working waves while others hold three and idle ones, and the table deals each XCD band's working
+	// quadrants out first (launch_quad_order; C2 fused launch 38.5 -> 35.3 us with the 5-wave build, 36.3 with the 4-wave
+	// build). NNRT_QUAD_ORDER=0: never, =1: always; a forced tile table (NNRT_TILE_ORDER=2) keeps it off.
+	const int quad_slots = 4 * 4 * cus;
+	const bool quad_order = fit_pixels_tile_order_supported() && [&] {
+		const char* v = std::getenv("NNRT_QUAD_ORDER");
+		if (v && *v == '0') return false;
+		if (v && *v == '1') return true;
+		const char* t = std::getenv("NNRT_TILE_ORDER");
+		return !multi_round && !(t && *t == '2');
+	}();
+	const bool tile_order = tile_order_wanted && !quad_order;   // one table per launch
 	{
+		if (quad_order && ((st = ft->quad_scratch.ensure(quad_order_scratch(static_cast<int>(4 * tiles)))) ||
+		                   (st = ft->quad_order.ensure(4 * static_cast<size_t>(quad_order_blocks(static_cast<int>(4 * tiles)))))))
+			return st;
 		if (tile_order && ((st = ft->tile_flags.ensure(tiles)) || (st = ft->tile_order.ensure(static_cast<size_t>(tile_order_blocks(static_cast<int>(tiles)))))))
 			return st;
 	}
@@ -846,7 +871,7 @@ nnrt_status prepare_frame(nnrt_fitter* ft, nnrt_warp_field* wf, const float* d_v
 		ft->aw.edge_list = ft->a_list.ptr;
 	}
 	const auto after = std::make_tuple(ft->mesh_p.ptr, ft->faces4.ptr, ft->anchors.ptr, ft->keys.ptr, ft->acc.ptr, ft->wing.ptr, ft->corner.generation,
-	                                   ft->face_nodes.ptr, ft->wpos.ptr, ft->mesh_p4.ptr, ft->tile_order.ptr, ft->anchors16.ptr);
+	                                   ft->face_nodes.ptr, ft->wpos.ptr, ft->mesh_p4.ptr, ft->tile_order.ptr, ft->quad_order.ptr, ft->anchors16.ptr);
 	// Captured graphs bake every buffer pointer and the per-frame constants (NDC setup, pixel camera, extrinsics) into
 	// their kernel arguments: any change drops them. The warp field is recognised by its unique id, not its address.
 	const NdcSetup nndc = make_ndc_setup(h_K, H, W, ft->p.ndc_convention == NNRT_NDC_CONSISTENT);
@@ -857,11 +882,13 @@ nnrt_status prepare_frame(nnrt_fitter* ft, nnrt_warp_field* wf, const float* d_v
 		const char* v = std::getenv("NNRT_ANCHORS16");   // development switch: 0 = the int32 anchors
 		return !(v && *v == '0');
 	}();
-	if (before != after || ft->use_tile_order != tile_order || ft->pix_low_occupancy != pix_low || ft->use_anchors16 != anchors16 || ft->wf != wf || ft->wf_id != wf->id || ft->V != V || ft->F != F || ft->H != H || ft->W != W || ft->N != N ||
+	if (before != after || ft->use_tile_order != tile_order || ft->use_quad_order != quad_order || ft->quad_slots != quad_slots || ft->pix_low_occupancy != pix_low || ft->use_anchors16 != anchors16 || ft->wf != wf || ft->wf_id != wf->id || ft->V != V || ft->F != F || ft->H != H || ft->W != W || ft->N != N ||
 	    ft->K != K || std::memcmp(&nndc, &ft->ndc, sizeof(nndc)) != 0 || std::memcmp(&npix, &ft->pix, sizeof(npix)) != 0 ||
 	    std::memcmp(&ne, &ft->extr, sizeof(ne)) != 0)
 		ft->drop_graphs();
 	ft->use_tile_order = tile_order;
+	ft->use_quad_order = quad_order;
+	ft->quad_slots = quad_slots;
 	ft->pix_low_occupancy = pix_low;
 	ft->use_anchors16 = anchors16;
 	ft->V = V;
@@ -907,6 +934,10 @@ nnrt_status prepare_frame(nnrt_fitter* ft, nnrt_warp_field* wf, const float* d_v
 	    (st = launch_tile_order(ft->ref_points.ptr, H, W, static_cast<int>(ceil_div(W, 16)), static_cast<int>(ceil_div(H, 16)), ft->tile_flags.ptr,
 	                            ft->tile_order.ptr, s)))
 		return st;
+	if (ft->use_quad_order &&
+	    (st = launch_quad_order(ft->ref_points.ptr, H, W, static_cast<int>(ceil_div(W, 16)), static_cast<int>(ceil_div(H, 16)), ft->quad_slots,
+	                            ft->quad_scratch.ptr, ft->quad_order.ptr, s)))
+		return st;
 	NNRT_HIP(hipMemsetAsync(ft->keys.ptr, 0xff, sizeof(uint64_t) * P, s));
 	NNRT_HIP(hipMemsetAsync(ft->acc.ptr, 0, sizeof(double) * N * ACC_STRIDE, s));
 	NNRT_HIP(hipEventRecord(ft->ev_out, s));
@@ -925,6 +956,32 @@ nnrt_status nnrt_fitter_prepare(nnrt_fitter* ft, nnrt_warp_field* wf, const floa
 	ref.depth_scale = depth_scale;
 	NNRT_CHECK_ARG(d_depth, "null depth image");
 	return prepare_frame(ft, wf, d_vertices, d_normals, V, d_faces, F, ref, H, W, h_K, h_E, stream);
+}
+
+int32_t nnrt_fit_quad_order_blocks(int32_t quadrants) { return quadrants > 0 ? quad_order_blocks(quadrants) : 0; }
+
+nnrt_status nnrt_fit_quad_order_table(const uint8_t* h_valid, int32_t H, int32_t W, int32_t slots, int32_t* h_counts, int32_t* h_table) {
+	NNRT_CHECK_ARG(h_valid && h_counts && h_table, "null pointer");
+	NNRT_CHECK_ARG(H > 0 && W > 0 && slots >= 0, "empty image or negative slot count");
+	const int tiles_x = static_cast<int>(ceil_div(W, 16)), tiles_y = static_cast<int>(ceil_div(H, 16)), quadrants = 4 * tiles_x * tiles_y;
+	const size_t P = static_cast<size_t>(H) * W, entries = 4 * static_cast<size_t>(quad_order_blocks(quadrants));
+	std::vector<float4> ref(P);
+	for (size_t p = 0; p < P; p++) ref[p] = make_float4(0.f, 0.f, 1.f, h_valid[p] ? 1.f : 0.f);
+	DeviceBuffer<float4> d_ref;
+	DeviceBuffer<int> d_scratch, d_order;
+	nnrt_status st = NNRT_OK;
+	if (!(st = upload(d_ref, ref)) && !(st = d_scratch.ensure(quad_order_scratch(quadrants))) && !(st = d_order.ensure(entries)) &&
+	    !(st = launch_quad_order(d_ref.ptr, H, W, tiles_x, tiles_y, slots, d_scratch.ptr, d_order.ptr, nullptr))) {
+		if (hipMemcpy(h_counts, d_scratch.ptr, sizeof(int) * quadrants, hipMemcpyDeviceToHost) != hipSuccess ||
+		    hipMemcpy(h_table, d_order.ptr, sizeof(int) * entries, hipMemcpyDeviceToHost) != hipSuccess) {
+			set_error("hipMemcpy failed");
+			st = NNRT_ERROR_HIP;
+		}
+	}
+	d_ref.release();
+	d_scratch.release();
+	d_order.release();
+	return st;
 }
 
 nnrt_status nnrt_fitter_prepare_point_cloud(nnrt_fitter* ft, nnrt_warp_field* wf, const float* d_vertices, const float* d_normals,

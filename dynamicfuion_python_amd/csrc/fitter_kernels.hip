@@ -31,6 +31,14 @@ static_assert(PIX_WAVES == 1 || PIX_WAVES == 2 || PIX_WAVES == 4, "waves per wor
 // round-robin over the 8 XCDs, so each XCD gets a contiguous band of quadrants (neighbouring pixels share vertices,
 // anchors and nodes -> L2 reuse within the XCD).
 __device__ inline int pix_quadrant(const FitPixelArgs& a) {
+	if (PIX_WAVES == 4 && a.quad_order) {
+		// the per-frame quadrant table (k_quad_order): same band layout as the tile table below, four entries per
+		// workgroup, one per wave; an entry is the quadrant id (tile * 4 + quad) or the sentinel 4 * tiles (no pixels);
+		// one scalar load
+		const int b = static_cast<int>(blockIdx.x), per_band = a.order_blocks >> 3;
+		const int wave = __builtin_amdgcn_readfirstlane(static_cast<int>(threadIdx.x >> 6));
+		return a.quad_order[((b & 7) * per_band + (b >> 3)) * 4 + wave];
+	}
 	if (PIX_WAVES == 4 && a.tile_order) {
 		// the per-frame table holds XCD band x (the workgroups b = x + 8 k, dispatched round-robin over the XCDs) at
 		// [x * per_band, (x + 1) * per_band), in k order (k_tile_order); one scalar load
@@ -1025,11 +1033,143 @@ nnrt_status launch_tile_order(const float4* ref_points, int H, int W, int tiles_
 	return NNRT_OK;
 }
 
+// ---- per-frame quadrant order of the pixel launch (launch_quad_order) ----
+// The tile table's quadrant-granular form, for launches of one residency round: what decides their length is how many
+// waves with pixels to fit share a SIMD, and whole 16 x 16 tiles are too coarse to even that out.
+// Table layout: XCD band x holds per_band workgroups of four entries at [4 x per_band, 4 (x + 1) per_band): its
+// eighth of the working quadrants (a valid reference pixel) in tile-major order -- the quadrant id order --, then its
+// eighth of the idle ones, then the sentinel `quadrants`. A band with more working quadrants than its share of `slots`
+// (the launch's wave slots at four waves per SIMD) moves the excess, its lightest working quadrants (fewest valid
+// pixels, ties by id), to the end of its working run, ascending by (pixels, id); the others keep their order.
+__host__ __device__ inline int quad_blocks_per_band(int quadrants) { return ((quadrants + 7) / 8 + 1 + 3) / 4; }   // 4 * this >= ceil(w / 8) + ceil(i / 8)
+int quad_order_blocks(int quadrants) { return 8 * quad_blocks_per_band(quadrants); }
+
+// per 8 x 8 quadrant (one wave; one tile per workgroup): the number of pixels holding a valid reference point
+__global__ __launch_bounds__(256) void k_quad_flags(const float4* __restrict__ ref, int H, int W, int tiles_x, int* __restrict__ counts) {
+	const int tile = static_cast<int>(blockIdx.x), quad = static_cast<int>(threadIdx.x >> 6), lane = static_cast<int>(threadIdx.x & 63);
+	const int u = (tile % tiles_x) * PIX_TILE + (quad & 1) * 8 + (lane & 7), v = (tile / tiles_x) * PIX_TILE + (quad >> 1) * 8 + (lane >> 3);
+	const bool valid = u < W && v < H && ref[static_cast<int64_t>(v) * W + u].w != 0.f;
+	const unsigned long long b = __ballot(valid);
+	if (lane == 0) counts[tile * 4 + quad] = __popcll(b);
+}
+
+// one workgroup: ranks of the working / idle quadrants in id order (chunked block scan, as k_tile_order). Idle quadrants
+// and the padding go to their table entries; the working ones to work[rank] (k_quad_place puts each band's run into the
+// table); totals[0] = the number of working quadrants
+__global__ __launch_bounds__(ORDER_THREADS) void k_quad_order(const int* __restrict__ counts, int quadrants, int* __restrict__ work, int* __restrict__ totals,
+                                                              int* __restrict__ order) {
+	__shared__ int s_w[ORDER_THREADS], s_i[ORDER_THREADS];
+	const int t = static_cast<int>(threadIdx.x);
+	const int per_band = 4 * quad_blocks_per_band(quadrants);
+	for (int i = t; i < 8 * per_band; i += ORDER_THREADS) order[i] = quadrants;
+	const int c = (quadrants + ORDER_THREADS - 1) / ORDER_THREADS, t0 = t * c < quadrants ? t * c : quadrants, t1 = t0 + c < quadrants ? t0 + c : quadrants;
+	int nw = 0, ni = 0;
+	for (int q = t0; q < t1; q++) (counts[q] ? nw : ni)++;
+	s_w[t] = nw;
+	s_i[t] = ni;
+	__syncthreads();
+	for (int d = 1; d < ORDER_THREADS; d <<= 1) {   // inclusive scan (Hillis-Steele)
+		const int aw = t >= d ? s_w[t - d] : 0, ai = t >= d ? s_i[t - d] : 0;
+		__syncthreads();
+		s_w[t] += aw;
+		s_i[t] += ai;
+		__syncthreads();
+	}
+	const int W = s_w[ORDER_THREADS - 1], I = s_i[ORDER_THREADS - 1];
+	int m = s_w[t] - nw, n = s_i[t] - ni;   // ranks of this chunk's first working / idle quadrant
+	if (t == 0) totals[0] = W;
+	for (int q = t0; q < t1; q++) {
+		if (counts[q]) {
+			work[m++] = q;
+		} else {
+			int x = 7;
+			while (x > 0 && (static_cast<int64_t>(x) * I) / 8 > n) x--;
+			const int wx = static_cast<int>((static_cast<int64_t>(x + 1) * W) / 8 - (static_cast<int64_t>(x) * W) / 8);
+			order[x * per_band + wx + (n - static_cast<int>((static_cast<int64_t>(x) * I) / 8))] = q;
+			n++;
+		}
+	}
+}
+
+// one wave per XCD band: the band's working run work[x W / 8 .. (x + 1) W / 8) into the table. Without overflow a copy.
+// With overflow ov = run - slots / 8 > 0: a histogram of the run's pixel counts gives the threshold count c* and the
+// number r of quadrants with exactly c* pixels that overflow (the first r by id); then the run is walked in order, 64
+// quadrants at a time, each lane taking its quadrant's rank among the band's quadrants of the same count (s_run) and, if
+// it stays, among those that stay
+__global__ __launch_bounds__(64) void k_quad_place(const int* __restrict__ counts, int quadrants, const int* __restrict__ work, const int* __restrict__ totals,
+                                                   int slots, int* __restrict__ order) {
+	__shared__ int s_hist[65], s_cum[65], s_run[65];
+	const int x = static_cast<int>(blockIdx.x), lane = static_cast<int>(threadIdx.x);
+	const int per_band = 4 * quad_blocks_per_band(quadrants);
+	const int W = totals[0];
+	const int first = static_cast<int>((static_cast<int64_t>(x) * W) / 8), run = static_cast<int>((static_cast<int64_t>(x + 1) * W) / 8) - first;
+	const int share = slots / 8 > 0 ? slots / 8 : 0;
+	const int ov = run > share ? run - share : 0;
+	int* band = order + x * per_band;
+	if (ov == 0) {
+		for (int j = lane; j < run; j += 64) band[j] = work[first + j];
+		return;
+	}
+	for (int i = lane; i < 65; i += 64) {
+		s_hist[i] = 0;
+		s_run[i] = 0;
+	}
+	__syncthreads();
+	for (int j = lane; j < run; j += 64) atomicAdd(&s_hist[counts[work[first + j]]], 1);
+	__syncthreads();
+	if (lane == 0) {
+		int sum = 0;
+		for (int i = 0; i < 65; i++) {
+			s_cum[i] = sum;
+			sum += s_hist[i];
+		}
+	}
+	__syncthreads();
+	// c*: the largest count whose lighter quadrants alone do not exceed the overflow (s_cum ascends; s_cum[1] = 0 <= ov)
+	int cs = 1;
+	for (int i = 1; i < 65; i++)
+		if (s_cum[i] <= ov) cs = i;
+	const int r = ov - s_cum[cs];
+	int kept = 0;   // quadrants staying in order so far (wave-uniform)
+	for (int j0 = 0; j0 < run; j0 += 64) {
+		const int j = j0 + lane;
+		const bool on = j < run;
+		const int q = on ? work[first + j] : 0;
+		const int cnt = on ? counts[q] : 0;   // working quadrants have 1..64; 0: no quadrant in this lane
+		unsigned long long same = 0ull;   // lanes holding the same count
+		for (int i = 0; i < 64; i++)
+			if (__shfl(cnt, i) == cnt) same |= 1ull << i;
+		const unsigned long long below = (1ull << lane) - 1ull;
+		const int k = s_run[cnt] + __popcll(same & below);   // rank among the band's quadrants of this count, by id
+		const bool over = on && (cnt < cs || (cnt == cs && k < r));
+		const unsigned long long stay = __ballot(on && !over);
+		if (over) band[(run - ov) + s_cum[cnt] + k] = q;
+		else if (on) band[kept + __popcll(stay & below)] = q;
+		kept += __popcll(stay);
+		__syncthreads();
+		if (on && (same >> lane) <= 1ull) s_run[cnt] += __popcll(same);   // the highest lane of each count
+		__syncthreads();
+	}
+}
+
+nnrt_status launch_quad_order(const float4* ref_points, int H, int W, int tiles_x, int tiles_y, int slots, int* scratch, int* order, hipStream_t stream) {
+	const int tiles = tiles_x * tiles_y, quadrants = 4 * tiles;
+	if (tiles == 0) return NNRT_OK;
+	int *counts = scratch, *work = scratch + quadrants, *totals = scratch + 2 * quadrants;
+	k_quad_flags<<<static_cast<unsigned>(tiles), 256, 0, stream>>>(ref_points, H, W, tiles_x, counts);
+	NNRT_LAUNCH_CHECK();
+	k_quad_order<<<1, ORDER_THREADS, 0, stream>>>(counts, quadrants, work, totals, order);
+	NNRT_LAUNCH_CHECK();
+	k_quad_place<<<8, 64, 0, stream>>>(counts, quadrants, work, totals, slots, order);
+	NNRT_LAUNCH_CHECK();
+	return NNRT_OK;
+}
+
 nnrt_status launch_fit_pixels(int mode, const FitPixelArgs& args, hipStream_t stream, hipEvent_t between) {
 	// `between` (stage timing) is recorded before the fused launch: the pixel-pass stage reads 0, the node-pass stage
 	// times both passes
 	if (between) NNRT_EV(hipEventRecord(between, stream));
-	const unsigned grid = static_cast<unsigned>((args.tile_order ? args.order_blocks : ((4 * args.tiles_x * args.tiles_y + PIX_WAVES - 1) / PIX_WAVES + 7) / 8 * 8) +
+	const unsigned grid = static_cast<unsigned>((args.tile_order || args.quad_order ? args.order_blocks : ((4 * args.tiles_x * args.tiles_y + PIX_WAVES - 1) / PIX_WAVES + 7) / 8 * 8) +
 	                                            args.arap_blocks);
 	// anchor slots per vertex: the common 4-anchor configuration gets its own instantiation (half the slot logic)
 	const bool k4 = args.anchor_count <= 4;

@@ -186,6 +186,7 @@ struct FitPixelArgs {
 	int arap_blocks;
 	const int* tile_order;  // [order_blocks] workgroup -> tile (launch_tile_order; nullable: the arithmetic XCD bands)
 	int order_blocks;
+	const int* quad_order;  // [4 * order_blocks] wave -> 8 x 8 quadrant (launch_quad_order; nullable; takes precedence)
 };
 
 struct SolveArgs {
@@ -219,6 +220,13 @@ int fit_pixels_arap_blocks(int E);
 int tile_order_blocks(int tiles);
 bool fit_pixels_tile_order_supported();   // false in NNRT_PIX_WAVES != 4 builds: the launch then ignores the table
 nnrt_status launch_tile_order(const float4* ref_points, int H, int W, int tiles_x, int tiles_y, int* flags, int* order, hipStream_t stream);
+// the same per 8 x 8 quadrant, one table entry per wave (launches of one residency round). slots: the launch's wave slots
+// at four waves per SIMD (16 per CU); a band's working quadrants beyond its eighth of them, the lightest, close its
+// working run. scratch: [quad_order_scratch(quadrants)] (counts, working list, totals: scratch[2 * quadrants] = the
+// number of working quadrants); order: [4 * quad_order_blocks(quadrants)], quadrants = 4 * tiles
+int quad_order_blocks(int quadrants);
+inline size_t quad_order_scratch(int quadrants) { return 2 * static_cast<size_t>(quadrants) + 1; }
+nnrt_status launch_quad_order(const float4* ref_points, int H, int W, int tiles_x, int tiles_y, int slots, int* scratch, int* order, hipStream_t stream);
 nnrt_status launch_solve_update(int mode, const SolveArgs& args, hipStream_t stream, bool from_identity = false);
 
 

@@ -131,6 +131,16 @@ nnrt_status nnrt_fitter_prepare(nnrt_fitter* fitter, nnrt_warp_field* warp_field
                                 int64_t vertex_count, const int64_t* d_faces, int64_t face_count, const float* d_depth,
                                 const uint8_t* d_mask, int32_t height, int32_t width, const double* h_K, const double* h_E,
                                 float depth_scale, void* stream);
+/* The per-frame wave -> 8 x 8 quadrant table of the fitter's pixel launch, as prepare() builds it for launches of one
+ * residency round (development / tests). Quadrants are numbered tile-major: 16 x 16 tiles in raster order, then the
+ * four quadrants of a tile (x fastest); quadrants = 4 * ceil(W / 16) * ceil(H / 16). The table has
+ * 4 * nnrt_fit_quad_order_blocks(quadrants) entries in 8 equal bands (one per XCD): a band's share of the quadrants
+ * with a valid pixel first, then its share of the others, then the value `quadrants` as padding. A band holding more
+ * quadrants with valid pixels than slots / 8 moves the excess, those with the fewest valid pixels, to the end of that
+ * run. h_valid: [H*W] uint8 (host); h_counts: [quadrants] valid pixels per quadrant; h_table: the table (host). */
+int32_t nnrt_fit_quad_order_blocks(int32_t quadrants);
+nnrt_status nnrt_fit_quad_order_table(const uint8_t* h_valid, int32_t height, int32_t width, int32_t slots, int32_t* h_counts,
+                                      int32_t* h_table);
 /* FitToImage(warp_field, canonical_mesh, color, reference_point_cloud, reference_point_mask, K, E, rendering_image_size)
  * (DeformableMeshToImageFitter.cpp:85-276, the overload the depth variant forwards to): d_points float32 [H*W,3]
  * organized reference points, d_point_mask uint8 [H*W] or NULL (all valid), (height, width) = rendering image size. */

@@ -1,14 +1,15 @@
 """Per-wave timeline of k_fit_pixels_fused (development; needs tools/dev/libnnrt_fitstamps.so:
 tools/dev/stamps_build.sh NNRT_FIT_STAMPS tools/dev/libnnrt_fitstamps.so). Runs C2 GN iterations from the mid-motion
 state (eager launches) and summarises the last launch: dispatch ramp, wave lifetimes (pass 1 / pass 2), the tail, and
-the load per CU / SIMD (100 MHz clock: 10 ns ticks)."""
+the load per CU / SIMD (100 MHz clock: 10 ns ticks), then per SIMD the working waves it held against its last end time.
+NNRT_STAMPS_LIB names another stamps build; NNRT_QUAD_ORDER / NNRT_PIX_WPE4 select the launch as in the product."""
 import ctypes
 import json
 import os
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-os.environ["NNRT_LIB_PATH"] = os.path.join(ROOT, "tools", "dev", "libnnrt_fitstamps.so")
+os.environ["NNRT_LIB_PATH"] = os.environ.get("NNRT_STAMPS_LIB") or os.path.join(ROOT, "tools", "dev", "libnnrt_fitstamps.so")
 sys.path[:0] = [ROOT]
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
@@ -37,7 +38,8 @@ fn = getattr(lib, "nnrt_dev_fit_stamps")
 fn.argtypes = [ctypes.c_void_p]
 assert fn(buf.ctypes.data) == 0
 tiles = ((sc.W + 15) // 16) * ((sc.H + 15) // 16)
-nw = ((tiles + 7) // 8) * 8 * 4
+nw = int((buf[:, 0] != 0).sum())   # the waves of the launch's grid (a table launch has more than the tiles' 4 each); rows past it stay 0
+assert nw >= ((tiles + 7) // 8) * 8 * 4 and (buf[:nw, 0] != 0).all()
 st = buf[:nw].astype(np.int64)
 t0 = st[:, 0].min()
 start, mid, end = (st[:, 0] - t0) * 10, (st[:, 1] - t0) * 10, (st[:, 2] - t0) * 10   # ns
@@ -58,6 +60,18 @@ np.maximum.at(last, inv, end / 1e3)
 for c in sorted(set(cnt)):
     m = cnt == c
     print(f"SIMDs with {c} waves: {m.sum()}, their last end: mean {last[m].mean():.1f} max {last[m].max():.1f} us")
+
+def per_simd_working(working, rule="lifetime > 4 us or pass-2 chunks > 0"):
+    """SIMDs by the number of working waves they held: how many, and the mean / max of their last wave's end"""
+    nwork = np.zeros(len(us), np.int64)
+    np.add.at(nwork, inv, working.astype(np.int64))
+    print(f"working waves {int(working.sum())} of {nw} on {len(us)} SIMDs (working: {rule})")
+    for c in sorted(set(nwork.tolist())):
+        m = nwork == c
+        print(f"SIMDs with {c} working waves: {int(m.sum())}, their last end: mean {last[m].mean():.1f} max {last[m].max():.1f} us; "
+              f"waves resident {cnt[m].mean():.2f}")
+
+
 hist, edges = np.histogram(life / 1e3, bins=12)
 print("lifetime histogram (us):", [(round(float(e), 1), int(h)) for e, h in zip(edges, hist)])
 if out_json:
@@ -71,6 +85,9 @@ if fnp is not None:
     assert fnp(ph.ctypes.data) == 0
     ph = ph[:nw].astype(np.float64)
     busy = ph[:, 3] > 0
+    per_simd_working((life > 4000) | busy)
+    # idle waves that share a SIMD with working ones can wait past 4 us for their few instructions: the chunk count alone
+    per_simd_working(busy, "pass-2 chunks > 0")
     tot = ph[busy, :3].sum(1)
     p2_ns = p2[busy].astype(np.float64)
     clk = (tot / np.maximum(p2_ns, 1)).mean()   # cycles per ns of wave time in pass 2 (the phases cover it)
@@ -80,3 +97,5 @@ if fnp is not None:
           f"{clk:.2f} cycles per ns of pass-2 time")
     print(f"  per wave: grouping steps {ph[busy, 5].mean():.1f}, slot-serial sum batches {ph[busy, 4].mean():.2f} of "
           f"{4 * ph[busy, 3].mean():.1f} (wave-level batches: 4 per chunk)")
+else:
+    per_simd_working(life > 4000, "lifetime > 4 us")
