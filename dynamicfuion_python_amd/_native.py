@@ -88,11 +88,14 @@ _SIGNATURES = {
     "nnrt_fitter_time_kernels": (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_void_p]),
     "nnrt_fitter_refine_info": (c_int32, [c_void_p, c_void_p, c_void_p]),
     "nnrt_fitter_set_refine_ratio": (c_int32, [c_void_p, c_float]),
+    "nnrt_fitter_set_anchor_graph": (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_void_p]),
     "nnrt_fitter_check": (c_int32, [c_void_p, c_void_p]),
     "nnrt_fitter_get_diagnostics": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "nnrt_fitter_get_anchors": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p]),
     "nnrt_compute_anchors_and_weights": (c_int32, [c_void_p, c_int64, c_void_p, c_int32, c_int32, c_float, c_void_p, c_int32,
                                                    c_void_p, c_void_p, c_void_p]),
+    "nnrt_compute_anchors_and_weights_shortest_path": (c_int32, [c_void_p, c_int64, c_void_p, c_int32, c_void_p, c_int32, c_int32, c_float,
+                                                                 c_void_p, c_void_p, c_void_p, c_void_p]),
     "nnrt_warp_mesh": (c_int32, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_int32,
                                  c_void_p, c_void_p, c_void_p, c_void_p]),
     "nnrt_warp_points": (c_int32, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_int32, c_float,

@@ -74,6 +74,11 @@ class RenderingAlignmentOptimizer:
             use_huber_penalty_for_arap_term=p.regularization_term_penalty_function == PenaltyFunction.HUBER,
             huber_penalty_constant=p.regularization_term_penalty_constant, device=dev, ndc_convention=p.ndc_convention)
 
+    def set_anchor_graph(self, edges):
+        """Anchor the canonical mesh along these edge rows ([N, D] int32, the graph's virtual node order, -1 = empty) in
+        every later optimize_graph call (AnchorComputationMode.SHORTEST_PATH); None: Euclidean anchors."""
+        self.fitter.set_anchor_graph(edges)
+
     def optimize_graph(self, graph: G.HierarchicalGraphWarpField, tsdf, target_points, target_rgb=None):
         """tsdf: an object with extract_surface_mesh(-1, 0) (NonRigidSurfaceVoxelBlockGrid) or the canonical mesh
         itself; target_points: organized [H,W,3] / [H*W,3] camera-space points (z <= 0 or non-finite = no target)."""

@@ -408,6 +408,10 @@ struct nnrt_fitter {
 	int n0 = 0;
 	int last_mode = 0;
 	DeviceBuffer<float> snapshot;   // [N,16] node state stored by nnrt_fitter_snapshot_motion (restore-before-iteration runs)
+	// nnrt_fitter_set_anchor_graph: edge rows [graph_nodes, graph_degree] in the warp field's virtual node order (checked
+	// when set); graph_degree == 0: Euclidean anchors
+	DeviceBuffer<int32_t> graph_edges;
+	int graph_nodes = 0, graph_degree = 0;
 	bool snapshot_valid = false;    // cleared by prepare() (the warp field or the node count may have changed)
 	// graphs: one per iteration sequence (the modes of the `count` iterations of an iterate() call, and what each
 	// iteration restarts from: RESET_NONE / RESET_IDENTITY / RESET_SNAPSHOT), captured once and replayed as ONE launch; the
@@ -665,6 +669,7 @@ void nnrt_fitter_destroy(nnrt_fitter* ft) {
 	ft->faces4.release();
 	ft->anchors.release();
 	ft->anchors16.release();
+	ft->graph_edges.release();
 	ft->face_nodes.release();
 	ft->wpos.release();
 	ft->wnrm.release();
@@ -718,6 +723,7 @@ nnrt_status prepare_frame(nnrt_fitter* ft, nnrt_warp_field* wf, const float* d_v
 	const int N = wf->N, K = wf->anchor_count, E = wf->E();
 	NNRT_CHECK_ARG(N >= K, "the warp field has fewer nodes than anchors per vertex");
 	NNRT_CHECK_ARG(N < FACE_NODE_MAX_NODES, "node count exceeds the face-node table's 20-bit node field");
+	NNRT_CHECK_ARG(ft->graph_degree == 0 || ft->graph_nodes == N, "the anchor graph's node_count differs from the warp field's");
 	if (E > 0) {
 		for (int i = 0; i < ft->p.iteration_mode_count; i++)
 			if (ft->p.iteration_modes[i] != NNRT_ITERATION_ALL) {
@@ -915,9 +921,15 @@ nnrt_status prepare_frame(nnrt_fitter* ft, nnrt_warp_field* wf, const float* d_v
 	k_to_float4<<<static_cast<unsigned>(ceil_div(V, 256)), 256, 0, s>>>(d_vertices, d_normals, V, ft->mesh_p4.ptr, ft->mesh_n4.ptr);
 	NNRT_LAUNCH_CHECK();
 	// once per frame (:96-106): anchors & weights on the canonical mesh in virtual node order
-	if ((st = launch_compute_anchors(ft->mesh_p.ptr, V, wf->node_positions.ptr, N, K, wf->coverage,
-	                                 wf->coverage_method == NNRT_MINIMAL_K_NEIGHBOR_NODE_DISTANCE ? wf->node_weights.ptr : nullptr,
-	                                 wf->threshold ? wf->minimum_valid : 0, ft->anchors.ptr, ft->weights.ptr, s)))
+	const float* anchor_node_weights = wf->coverage_method == NNRT_MINIMAL_K_NEIGHBOR_NODE_DISTANCE ? wf->node_weights.ptr : nullptr;
+	if (ft->graph_degree > 0) {
+		// along the anchor graph's edges (PlanarGraphWarpField::PrecomputeAnchorsAndWeights, SHORTEST_PATH): no distance
+		// threshold in this mode
+		if ((st = launch_anchors_shortest_path(ft->mesh_p.ptr, V, wf->node_positions.ptr, N, ft->graph_edges.ptr, ft->graph_degree, K,
+		                                       wf->coverage, anchor_node_weights, ft->anchors.ptr, ft->weights.ptr, s, true)))
+			return st;
+	} else if ((st = launch_compute_anchors(ft->mesh_p.ptr, V, wf->node_positions.ptr, N, K, wf->coverage, anchor_node_weights,
+	                                        wf->threshold ? wf->minimum_valid : 0, ft->anchors.ptr, ft->weights.ptr, s)))
 		return st;
 	// the faces' distinct anchor nodes (AssociateFacesWithAnchors, :105), consumed by the node pass of every iteration
 	if ((st = launch_face_node_table(ft->faces4.ptr, F, ft->anchors.ptr, K, ft->face_nodes.ptr, s))) return st;
@@ -1247,6 +1259,31 @@ nnrt_status nnrt_fitter_set_refine_ratio(nnrt_fitter* ft, float ratio) {
 	return NNRT_OK;
 }
 
+nnrt_status nnrt_fitter_set_anchor_graph(nnrt_fitter* ft, const int32_t* d_edges, int32_t node_count, int32_t graph_degree, void* stream) {
+	NNRT_CHECK_ARG(ft, "null pointer");
+	DeviceGuard guard(ft->device);
+	hipStream_t us = static_cast<hipStream_t>(stream);
+	if (!d_edges && ft->graph_degree == 0) return NNRT_OK;
+	if (d_edges) {
+		NNRT_CHECK_ARG(node_count >= 1 && graph_degree >= 1, "the anchor graph needs node_count >= 1 and graph_degree >= 1");
+		nnrt_status st = check_anchor_edges(d_edges, node_count, graph_degree, us);   // synchronizes the caller's stream
+		if (st) return st;
+	}
+	NNRT_HIP(hipStreamSynchronize(ft->work));
+	ft->drop_graphs();   // the anchors are inputs of the captured sequences
+	ft->prepared = false;   // the prepared frame's anchors are the previous mode's
+	ft->graph_nodes = ft->graph_degree = 0;
+	if (!d_edges) return NNRT_OK;
+	const size_t count = static_cast<size_t>(node_count) * graph_degree;
+	nnrt_status st = ft->graph_edges.ensure(count);
+	if (st) return st;
+	NNRT_HIP(hipMemcpyAsync(ft->graph_edges.ptr, d_edges, sizeof(int32_t) * count, hipMemcpyDeviceToDevice, us));
+	NNRT_HIP(hipStreamSynchronize(us));
+	ft->graph_nodes = node_count;
+	ft->graph_degree = graph_degree;
+	return NNRT_OK;
+}
+
 int32_t nnrt_fitter_graph_count(const nnrt_fitter* ft) {
 	if (!ft) return -1;
 	int32_t n = 0;
@@ -1506,6 +1543,15 @@ nnrt_status nnrt_fitter_get_anchors(nnrt_fitter* ft, int32_t* h_anchors, float* 
 // ---------------------------------------------------------------------------------------------------------------------
 // stage entry points
 // ---------------------------------------------------------------------------------------------------------------------
+nnrt_status nnrt_compute_anchors_and_weights_shortest_path(const float* d_points, int64_t V, const float* d_nodes, int32_t N, const int32_t* d_edges,
+                                                           int32_t D, int32_t K, float coverage, const float* d_node_weights,
+                                                           int32_t* d_anchors, float* d_weights, void* stream) {
+	NNRT_CHECK_ARG(V == 0 || (d_points && d_anchors && d_weights), "null pointer");
+	NNRT_CHECK_ARG(N == 0 || V == 0 || (d_nodes && d_edges), "null pointer");
+	return launch_anchors_shortest_path(d_points, V, d_nodes, N, d_edges, D, K, coverage, d_node_weights, d_anchors, d_weights,
+	                                    static_cast<hipStream_t>(stream));
+}
+
 nnrt_status nnrt_compute_anchors_and_weights(const float* d_points, int64_t V, const float* d_nodes, int32_t N, int32_t K, float coverage,
                                              const float* d_node_weights, int32_t minimum_valid, int32_t* d_anchors, float* d_weights,
                                              void* stream) {

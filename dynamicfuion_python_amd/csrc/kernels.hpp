@@ -85,6 +85,13 @@ __device__ inline f3 apply_extrinsics_normal(const WarpExtrinsics& E, f3 n) {
 nnrt_status launch_compute_anchors(const float* points, int64_t V, const float* nodes, int N, int K, float coverage,
                                    const float* node_weights, int minimum_valid, int32_t* anchors, float* weights, hipStream_t stream,
                                    int threshold = -1);   // -1: threshold iff minimum_valid > 0 (the anchor API); 0 / 1: forced
+// anchors_shortest_path.hip: anchors along the motion graph's edges (KnnUtilities_PriorityQueue.h:102-160); edges [N,D],
+// entry < 0 = empty. An entry >= N is refused before anything is written (check_anchor_edges, one stream
+// synchronization) unless the caller has checked these rows already (edges_checked).
+nnrt_status launch_anchors_shortest_path(const float* points, int64_t V, const float* nodes, int N, const int32_t* edges, int D, int K,
+                                         float coverage, const float* node_weights, int32_t* anchors, float* weights, hipStream_t stream,
+                                         bool edges_checked = false);
+nnrt_status check_anchor_edges(const int32_t* edges, int N, int D, hipStream_t stream);
 nnrt_status launch_warp_mesh(const float* points, const float* normals, int64_t V, const float* node_state, const int32_t* anchors,
                              const float* weights, int K, const WarpExtrinsics& E, float4* out_p, float4* out_n, float2* jrows,
                              hipStream_t stream, bool from_identity = false, const uint2* anchors16 = nullptr);

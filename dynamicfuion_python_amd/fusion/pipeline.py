@@ -21,6 +21,12 @@ Deviations: the mesh-extraction ramp counts processed frames, not 
 sequences ship sparse frames 300, 600, ...); the data and ARAP penalties default to SQUARE because the reference fitter's
 Tukey and Huber branches carry quirks A8/A9; the fitter runs with NDC_CONSISTENT, because the reference's image -> NDC
 mapping renders the mesh y-mirrored about cy (A11) and so fits a mirrored surface to a real depth frame.
+
+`FusionParameters.anchor_computation_mode = AnchorComputationMode.SHORTEST_PATH` (reference pipeline.py:577-582) makes the
+tracker anchor the canonical mesh along the motion graph's edges -- the DeepDeformGraph file's rows or the depth-image
+graph's geodesic rows, re-indexed to the warp field's virtual node order -- instead of to the Euclidean-nearest nodes.
+Only the fit uses these anchors: TSDF integration and `warp_mesh` keep the warp field's own Euclidean anchors, as in the
+reference.
 """
 from __future__ import annotations
 
@@ -62,6 +68,12 @@ class GraphGenerationMode(enum.Enum):
     PROVIDED_NODES = 3               # nodes handed to FusionPipeline(nodes=...)
 
 
+class AnchorComputationMode(enum.Enum):
+    """apps/fusion/pipeline.py AnchorComputationMode: how the tracker anchors canonical vertices to graph nodes."""
+    EUCLIDEAN = 0
+    SHORTEST_PATH = 1   # along the graph's edge rows: FIRST_FRAME_LOADED_GRAPH or FIRST_FRAME_DEPTH_IMAGE only
+
+
 class MeshExtractionWeightThresholdingMode(enum.Enum):
     CONSTANT = 0
     RAMP_UP_TO_CONSTANT = 1
@@ -80,6 +92,7 @@ class FusionParameters:
     tracking_method: TrackingMethod = TrackingMethod.RENDERING
     tracking_span_mode: TrackingSpanMode = TrackingSpanMode.FIRST_TO_CURRENT
     graph_generation_mode: GraphGenerationMode = GraphGenerationMode.FIRST_FRAME_LOADED_GRAPH
+    anchor_computation_mode: AnchorComputationMode = AnchorComputationMode.EUCLIDEAN
     mesh_extraction_weight_thresholding_mode: MeshExtractionWeightThresholdingMode = MeshExtractionWeightThresholdingMode.RAMP_UP_TO_CONSTANT
     mesh_extraction_weight_threshold: int = 10
     voxel_size: float = 0.005
@@ -118,6 +131,22 @@ class FrameResult:
     seconds: float = 0.0
 
 
+def remap_edges_to_node_order(edges, order) -> np.ndarray:
+    """Edge rows [N, D] over nodes in their original order -> rows over the same nodes re-ordered by `order` (order[v] = the
+    original index of new node v): row v is the row of node order[v] with every entry replaced by its new index; negative
+    entries (empty) are kept as -1."""
+    edges = np.asarray(edges, np.int32)
+    order = np.asarray(order, np.int64)
+    if edges.ndim != 2 or order.shape != (edges.shape[0],) or not np.array_equal(np.sort(order), np.arange(len(order))):
+        raise ValueError(f"`order` must be a permutation of the {edges.shape[0] if edges.ndim == 2 else '?'} edge rows")
+    if (edges >= len(order)).any():
+        raise ValueError("edge entry outside [-1, node count)")
+    inverse = np.empty(len(order), np.int32)
+    inverse[order] = np.arange(len(order), dtype=np.int32)
+    rows = edges[order]
+    return np.ascontiguousarray(np.where(rows >= 0, inverse[np.maximum(rows, 0)], -1).astype(np.int32))
+
+
 class FusionPipeline:
     def __init__(self, sequence: FrameSequenceDataset, parameters: Optional[FusionParameters] = None, nodes=None,
                  device: Optional[int] = None):
@@ -127,6 +156,10 @@ class FusionPipeline:
         if p.graph_generation_mode == GraphGenerationMode.FIRST_FRAME_DEPTH_IMAGE and not p.graph_from_depth_image:
             raise NotImplementedError(f"graph generation mode {p.graph_generation_mode.name} runs only with "
                                       "FusionParameters.graph_from_depth_image=True (the depth-image graph builder on the GPU)")
+        if p.anchor_computation_mode == AnchorComputationMode.SHORTEST_PATH and p.graph_generation_mode not in (
+                GraphGenerationMode.FIRST_FRAME_LOADED_GRAPH, GraphGenerationMode.FIRST_FRAME_DEPTH_IMAGE):
+            raise NotImplementedError(f"AnchorComputationMode.SHORTEST_PATH needs a graph with edge rows; graph generation mode "
+                                      f"{p.graph_generation_mode.name} has none (use FIRST_FRAME_LOADED_GRAPH or FIRST_FRAME_DEPTH_IMAGE)")
         if p.graph_generation_mode == GraphGenerationMode.PROVIDED_NODES and nodes is None:
             raise ValueError("GraphGenerationMode.PROVIDED_NODES needs nodes=")
         self.sequence = sequence if sequence._loaded else sequence.load()
@@ -152,6 +185,10 @@ class FusionPipeline:
         self.depth_image_graph = None
         self.geodesic_edges = None
         self.graph_clusters = None
+        # make_warp_field: the index, in the nodes it was given, of each node of the warp field it returned
+        self.node_order = None
+        # SHORTEST_PATH: the graph's edge rows in the warp field's virtual node order, as handed to the optimizer
+        self.anchor_graph_edges = None
         self.optimizer = RenderingAlignmentOptimizer((self.intrinsics.height, self.intrinsics.width), self.device, self.K, p.alignment)
         self.canonical_mesh = None
         self.warped_mesh = None
@@ -189,11 +226,12 @@ class FusionPipeline:
     def _initialize_graph(self, depth=None):
         """`depth`: the first frame's depth on the device, masked and clipped (FIRST_FRAME_DEPTH_IMAGE)."""
         p = self.parameters
+        edge_rows = None
         if p.graph_generation_mode == GraphGenerationMode.FIRST_FRAME_LOADED_GRAPH:
             name = self.sequence.get_current_graph_name()
             if name is None:
                 raise ValueError("no DeepDeformGraph file starts at the first frame")
-            nodes = self.sequence.load_graph_data(name)[0]
+            nodes, edge_rows = self.sequence.load_graph_data(name)[:2]
         elif p.graph_generation_mode == GraphGenerationMode.FIRST_FRAME_EXTRACTED_MESH:
             # pipeline.py:514-520: the mesh at weight threshold 0, erosion_iteration_count = 10
             self.graph_source_mesh = self.volume.extract_triangle_mesh(0.0, -1)
@@ -216,9 +254,15 @@ class FusionPipeline:
             self.sampled_node_positions, self.sampled_node_vertex_indices = g.node_positions, g.node_vertex_indices
             self.geodesic_edges, self.graph_clusters = g.edges, g.clusters
             nodes = g.node_positions.cpu().numpy()
+            edge_rows = g.edges.cpu().numpy()
         else:
             nodes = np.asarray(self._provided_nodes, np.float32)
         self.active_graph = self.make_warp_field(nodes)
+        if p.anchor_computation_mode == AnchorComputationMode.SHORTEST_PATH:
+            # the fitter computes anchors in the warp field's virtual node order
+            virtual_order = self.node_order[self.active_graph.get_virtual_node_indices()]
+            self.anchor_graph_edges = remap_edges_to_node_order(edge_rows, virtual_order)
+            self.optimizer.set_anchor_graph(self.anchor_graph_edges)
 
     def make_warp_field(self, nodes) -> G.HierarchicalGraphWarpField:
         """Hierarchical warp field over `nodes`, re-ordered toward the hierarchy's virtual order first (a few passes) so the
@@ -231,13 +275,16 @@ class FusionPipeline:
                                                 minimum_valid_anchor_count=p.fusion_minimum_valid_anchor_count,
                                                 layer_count=p.graph_layer_count, device=self.device)
         nodes = np.ascontiguousarray(nodes, np.float32)
+        order = np.arange(len(nodes))
         wf = build(nodes)
         for _ in range(3):
             vidx = wf.get_virtual_node_indices()
             if np.array_equal(vidx, np.arange(len(nodes))):
                 break
             nodes = nodes[vidx]
+            order = order[vidx]
             wf = build(nodes)
+        self.node_order = order
         return wf
 
     def extract_canonical_mesh(self):

@@ -159,7 +159,20 @@ class DeformableMeshToImageFitter:
         the threshold the last launched iterations ran with."""
         N.check(N.lib().nnrt_fitter_set_refine_ratio(self._h, float(ratio)))
 
-    def time_kernels(self, warp_field: HierarchicalGraphWarpField, reps: int = 20, trials: int = 5, stream=None) -> dict:
+    def set_anchor_graph(self, edges, stream=None):
+        """Anchor the canonical mesh along a motion graph's edges (the reference's AnchorComputationMethod.SHORTEST_PATH):
+        `edges` [N, D] int32 rows in the warp field's virtual node order (entry < 0 = empty), N the node count of the warp
+        field later handed to prepare(); None returns to Euclidean anchors. Takes effect at the next prepare()."""
+        if edges is None:
+            N.check(N.lib().nnrt_fitter_set_anchor_graph(self._h, None, 0, 0, N.stream_ptr(stream)))
+            return
+        dtype = edges.dtype if isinstance(edges, torch.Tensor) else np.asarray(edges).dtype
+        if dtype not in (torch.int32, np.dtype(np.int32)) or len(edges.shape) != 2:
+            raise RuntimeError(f"`edges` needs to be an int32 tensor of shape [node count, graph degree]. Got {dtype} {tuple(edges.shape)}.")
+        e = to_device(edges, torch.int32, self.device)
+        N.check(N.lib().nnrt_fitter_set_anchor_graph(self._h, N.ptr(e), e.shape[0], e.shape[1], N.stream_ptr(stream)))
+
+    def time_kernels(self,warp_field: HierarchicalGraphWarpField, reps: int = 20, trials: int = 5, stream=None) -> dict:
         """Per-kernel device ms of one iteration from the snapshot state, each kernel in its real context (prefix
         sequences of `reps` graph-captured iterations, median of `trials`; include/nnrt_mi355x.h)."""
         ms = np.zeros(len(KERNEL_TIMES), np.float32)

@@ -263,6 +263,48 @@ def compute_anchors_and_weights_euclidean_variable_node_weight(points, nodes, no
     return _anchors(points, nodes, anchor_count, 0.0, node_coverage_weights, minimum_valid_anchor_count)
 
 
+def _anchors_shortest_path(points, nodes, edges, anchor_count, coverage, node_weights):
+    dev = _dev()
+    p = to_device(points, torch.float32, dev)
+    if p.dim() not in (2, 3) or p.shape[-1] != 3:
+        raise RuntimeError(f"`points` needs to have shape [V, 3] or [H, W, 3]. Got {tuple(p.shape)}.")   # WarpAnchorComputation.cpp:29-71
+    if anchor_count < 1:
+        raise RuntimeError(f"anchor_count needs to be at least one. Got: {anchor_count}.")
+    n = to_device(nodes, torch.float32, dev).reshape(-1, 3)
+    if isinstance(edges, torch.Tensor):
+        edge_dtype, edge_shape = edges.dtype, tuple(edges.shape)
+    else:
+        edges = np.asarray(edges)
+        edge_dtype, edge_shape = edges.dtype, edges.shape
+    if edge_dtype not in (torch.int32, np.dtype(np.int32)) or len(edge_shape) != 2 or edge_shape[0] != n.shape[0] or edge_shape[1] < 1:
+        raise RuntimeError(f"`edges` needs to be an int32 tensor of shape [{n.shape[0]}, graph degree]. Got {edge_dtype} {tuple(edge_shape)}.")
+    e = to_device(edges, torch.int32, dev)
+    nw = None if node_weights is None else to_device(node_weights, torch.float32, dev).reshape(-1)
+    if nw is not None and nw.shape[0] != n.shape[0]:
+        raise RuntimeError(f"`node_coverage_weights` needs {n.shape[0]} entries, one per node. Got {nw.shape[0]}.")
+    flat = p.reshape(-1, 3)
+    a = torch.empty((flat.shape[0], anchor_count), dtype=torch.int32, device=dev)
+    w = torch.empty((flat.shape[0], anchor_count), dtype=torch.float32, device=dev)
+    N.check(N.lib().nnrt_compute_anchors_and_weights_shortest_path(N.ptr(flat), flat.shape[0], N.ptr(n), n.shape[0], N.ptr(e), e.shape[1],
+                                                                   int(anchor_count), float(coverage), N.ptr(nw), N.ptr(a), N.ptr(w),
+                                                                   N.stream_ptr()))
+    shape = tuple(p.shape[:-1]) + (anchor_count,)
+    return a.reshape(shape), w.reshape(shape)
+
+
+def compute_anchors_and_weights_shortest_path_fixed_node_weight(points, nodes, edges, anchor_count, node_coverage_weight):
+    """ComputeAnchorsAndWeights_ShortestPath_FixedNodeWeight (functional.cpp:63-67 -> WarpAnchorComputationImpl.h:146-237):
+    anchors along the graph's edges [N,D] int32 (entry < 0 = empty), -1 = slot never filled (weight 0); points [V,3] or
+    [H,W,3], outputs of the same leading shape; node_coverage_weight is the node coverage c (the reference's name for it).
+    An edge entry >= N is refused."""
+    return _anchors_shortest_path(points, nodes, edges, anchor_count, node_coverage_weight, None)
+
+
+def compute_anchors_and_weights_shortest_path_variable_node_weight(points, nodes, node_coverage_weights, edges, anchor_count):
+    """ComputeAnchorsAndWeights_ShortestPath_VariableNodeWeight (functional.cpp:69-73): per-node squared coverage weights."""
+    return _anchors_shortest_path(points, nodes, edges, anchor_count, 0.0, node_coverage_weights)
+
+
 def _check_min_valid(minimum_valid_anchor_count, anchor_count):
     if minimum_valid_anchor_count > anchor_count:
         raise RuntimeError(f"minimum_valid_anchor_count (now, {minimum_valid_anchor_count}) has to be smaller than or equal to anchor_count, "
@@ -499,6 +541,8 @@ functional = types.SimpleNamespace(
     compute_ordered_point_cloud_normals=compute_ordered_point_cloud_normals,
     compute_anchors_and_weights_euclidean_fixed_node_weight=compute_anchors_and_weights_euclidean_fixed_node_weight,
     compute_anchors_and_weights_euclidean_variable_node_weight=compute_anchors_and_weights_euclidean_variable_node_weight,
+    compute_anchors_and_weights_shortest_path_fixed_node_weight=compute_anchors_and_weights_shortest_path_fixed_node_weight,
+    compute_anchors_and_weights_shortest_path_variable_node_weight=compute_anchors_and_weights_shortest_path_variable_node_weight,
     warp_triangle_mesh=warp_triangle_mesh,
     warp_point_cloud=warp_point_cloud,
     median_grid_subsample_3d_points=median_grid_subsample_3d_points,

@@ -188,6 +188,16 @@ nnrt_status nnrt_fitter_refine_info(nnrt_fitter* fitter, float* h_out, void* str
  * diag(S) ratio falls below it (and is at least 1e-5); 0 never refines. Drops the fitter's cached graphs (a launch
  * argument). */
 nnrt_status nnrt_fitter_set_refine_ratio(nnrt_fitter* fitter, float ratio);
+/* Anchor the canonical mesh along a motion graph's edges instead of by Euclidean distance (the reference's
+ * AnchorComputationMethod::SHORTEST_PATH, PlanarGraphWarpField::PrecomputeAnchorsAndWeights; apps/fusion/pipeline.py:577-582):
+ * d_edges [node_count, graph_degree] int32 rows in the warp field's virtual node order (entry < 0 = empty) are copied
+ * into the fitter, and every later prepare() / prepare_point_cloud() computes its anchors with
+ * nnrt_compute_anchors_and_weights_shortest_path (the warp field's node weights when its coverage is variable). An
+ * entry >= node_count is refused here; prepare() refuses a node_count that differs from the warp field's.
+ * d_edges == NULL returns to Euclidean anchors. Drops the fitter's cached graphs and the prepared frame (prepare()
+ * again before iterating). Synchronizes `stream`. */
+nnrt_status nnrt_fitter_set_anchor_graph(nnrt_fitter* fitter, const int32_t* d_edges, int32_t node_count, int32_t graph_degree,
+                                         void* stream);
 /* Store the warp field's current node motion (R, t) in the fitter (a device copy on `stream`). */
 nnrt_status nnrt_fitter_snapshot_motion(nnrt_fitter* fitter, nnrt_warp_field* warp_field, void* stream);
 /* Benchmark form of iterate() that runs the general (non-identity) kernels: before every iteration the warp field's
@@ -239,6 +249,21 @@ nnrt_status nnrt_fitter_get_anchors(nnrt_fitter* fitter, int32_t* h_anchors, flo
 nnrt_status nnrt_compute_anchors_and_weights(const float* d_points, int64_t point_count, const float* d_nodes, int32_t node_count,
                                              int32_t anchor_count, float node_coverage, const float* d_node_coverage_weights,
                                              int32_t minimum_valid_anchor_count, int32_t* d_anchors, float* d_weights, void* stream);
+/* nnrt.geometry.functional.compute_anchors_and_weights_shortest_path_{fixed,variable}_node_weight
+ * (cpp/pybind/geometry/functional/functional.cpp:63-73 -> WarpAnchorComputationImpl.h:146-237,
+ * KnnUtilities_PriorityQueue.h:102-160, WarpUtilities.h:347-375): per point, K anchors in the order a 40-entry
+ * min-queue over (path length, node) pops them, seeded with the Euclidean-nearest node that is no anchor yet and fed
+ * along d_edges [node_count, graph_degree] int32 (entry < 0 = empty); seeded again whenever the queue runs dry.
+ * Weights exp(-d^2 / (2 c^2)) of the path lengths, normalized; no distance threshold, no minimum valid count.
+ * d_node_coverage_weights == NULL -> fixed coverage. Equal keys of two different nodes pop the lower index first. A
+ * slot never filled (fewer than K reachable nodes) is anchor -1 with weight 0; a row without any anchor has weights
+ * 1 / K. anchor_count in [1, 8], graph_degree >= 1, node_count >= 0. An edge entry >= node_count is refused
+ * (NNRT_ERROR_ARGUMENT) before anything is written; that check synchronizes `stream`. */
+nnrt_status nnrt_compute_anchors_and_weights_shortest_path(const float* d_points, int64_t point_count, const float* d_nodes,
+                                                           int32_t node_count, const int32_t* d_edges, int32_t graph_degree,
+                                                           int32_t anchor_count, float node_coverage,
+                                                           const float* d_node_coverage_weights, int32_t* d_anchors, float* d_weights,
+                                                           void* stream);
 /* WarpTriangleMeshUsingSuppliedAnchors (cpp/geometry/functional/Warping.cpp:222-264). h_E may be NULL. */
 nnrt_status nnrt_warp_mesh(const float* d_vertices, const float* d_normals, int64_t vertex_count, const float* d_nodes,
                            const float* d_rotations, const float* d_translations, int32_t node_count, const int32_t* d_anchors,
