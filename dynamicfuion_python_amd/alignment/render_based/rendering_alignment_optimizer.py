@@ -42,6 +42,11 @@ class RenderingAlignmentParameters:
     # A.NDC_REFERENCE reproduces the reference's y-mirrored render placement (A11); A.NDC_CONSISTENT is what real depth
     # frames need (the fusion pipeline's default)
     ndc_convention: int = A.NDC_REFERENCE
+    # The form of the TUKEY / HUBER penalties and the zero-rotation guard (DeformableMeshToImageFitter.set_robust_options).
+    # The defaults are the reference's arithmetic (quirks A8 / A9, NaN rotations A7); real sequences want
+    # PenaltyForm.IRLS and guard_zero_rotation=True.
+    penalty_form: A.PenaltyForm = A.PenaltyForm.REFERENCE
+    guard_zero_rotation: bool = False
 
 
 def as_triangle_mesh(mesh) -> G.TriangleMesh:
@@ -72,7 +77,8 @@ class RenderingAlignmentOptimizer:
             tukey_penalty_cutoff_cm=p.data_term_penalty_constant, preconditioning_dampening_factor=p.preconditioning_dampening_factor,
             arap_term_weight=p.arap_term_weight,
             use_huber_penalty_for_arap_term=p.regularization_term_penalty_function == PenaltyFunction.HUBER,
-            huber_penalty_constant=p.regularization_term_penalty_constant, device=dev, ndc_convention=p.ndc_convention)
+            huber_penalty_constant=p.regularization_term_penalty_constant, device=dev, ndc_convention=p.ndc_convention,
+            penalty_form=p.penalty_form, guard_zero_rotation=p.guard_zero_rotation)
 
     def set_anchor_graph(self, edges):
         """Anchor the canonical mesh along these edge rows ([N, D] int32, the graph's virtual node order, -1 = empty) in

@@ -392,7 +392,7 @@ __global__ void k_arrow_back(int n0, int n_update, const float* __restrict__ din
                              const int32_t* __restrict__ edges, const float* __restrict__ wing, const float* __restrict__ rhs,
                              float* __restrict__ x, const float* state_in, float* node_state, float* __restrict__ updates_out,
                              float* __restrict__ x_base, const unsigned* gate = nullptr, float ratio = 0.f, int mode = 0,
-                             const float* __restrict__ diag = nullptr, float* __restrict__ res = nullptr) {
+                             const float* __restrict__ diag = nullptr, float* __restrict__ res = nullptr, int guard_rot = 0) {
 	const int i = blockIdx.x * blockDim.x + threadIdx.x;
 	bool refining = false;
 	if (gate && mode == 2) {
@@ -402,7 +402,7 @@ __global__ void k_arrow_back(int n0, int n_update, const float* __restrict__ din
 	if (gate && mode == 1) refining = refine_gate_on(gate, ratio);
 	if (i >= n_update && i >= n0) return;
 	arrow_back_node<false>(i, n0, n_update, dinv, edge_offsets, edge_list, edges, wing, XPlain{rhs}, x, XPlain{x}, state_in, node_state,
-	                       updates_out, x_base, XPlain{x_base}, gate ? mode : 0, refining, diag, res);
+	                       updates_out, x_base, XPlain{x_base}, gate ? mode : 0, refining, diag, res, guard_rot != 0);
 }
 
 // ---- iterative refinement: the correction's corner right-hand side (one wave per corner node a; runs only when the gate
@@ -430,10 +430,11 @@ __global__ __launch_bounds__(64) void k_refine_correction(int n0, int N, const f
 	                              XPlain{res}, dx, XPlain{dx}, XPlain{x}, guard);
 }
 __global__ __launch_bounds__(64) void k_refine_apply(int N, const float* __restrict__ dx, float* __restrict__ x, const float* state_in, float* node_state,
-                                                     float* __restrict__ updates_out, const unsigned* gate, float ratio, const unsigned* guard) {
+                                                     float* __restrict__ updates_out, const unsigned* gate, float ratio, const unsigned* guard,
+                                                     int guard_rot) {
 	if (!refine_gate_on(gate, ratio)) return;
 	refine_apply_node(static_cast<int>(blockIdx.x * blockDim.x + threadIdx.x), N, refine_guard_accepts(guard), XPlain{dx}, XPlain{x}, x, state_in,
-	                  node_state, updates_out);
+	                  node_state, updates_out, guard_rot != 0);
 }
 
 nnrt_status arrowhead_solve_core(const ArrowheadWorkspace& ws, const int32_t* edges, const float* wing, int* error_flag, hipStream_t stream,
@@ -498,6 +499,7 @@ nnrt_status arrowhead_solve_core(const ArrowheadWorkspace& ws, const int32_t* ed
 		fs.guard = refine ? ws.corner->refine_guard() : nullptr;
 		fs.ratio = ws.refine_ratio;
 		fs.error_flag = error_flag;
+		fs.guard_zero_rotation = ws.guard_zero_rotation;
 		return ws.corner->launch_flow(fs, stream);
 	}
 	if (m > 0) {
@@ -509,7 +511,8 @@ nnrt_status arrowhead_solve_core(const ArrowheadWorkspace& ws, const int32_t* ed
 		const int threads = node_state ? ws.N : ws.n0;
 		if (threads > 0) {
 			k_arrow_back<<<static_cast<unsigned>(ceil_div(threads, 64)), 64, 0, stream>>>(ws.n0, threads, ws.dinv, ws.edge_offsets, ws.edge_list, edges,
-			                                                                             wing, ws.rhs, ws.x, state_in, node_state, updates_out, nullptr);
+			                                                                             wing, ws.rhs, ws.x, state_in, node_state, updates_out, nullptr, nullptr, 0.f, 0,
+			                                                                             nullptr, nullptr, ws.guard_zero_rotation);
 			NNRT_LAUNCH_CHECK();
 		}
 		return NNRT_OK;
@@ -521,7 +524,7 @@ nnrt_status arrowhead_solve_core(const ArrowheadWorkspace& ws, const int32_t* ed
 	const float ratio = ws.refine_ratio;
 	k_arrow_back<<<static_cast<unsigned>(ceil_div(ws.N, 64)), 64, 0, stream>>>(ws.n0, ws.N, ws.dinv, ws.edge_offsets, ws.edge_list, edges, wing,
 	                                                                          ws.rhs, ws.x, state_in, node_state, updates_out, nullptr, gate, ratio, 1,
-	                                                                          ws.diag, ws.res);
+	                                                                          ws.diag, ws.res, ws.guard_zero_rotation);
 	NNRT_LAUNCH_CHECK();
 	k_refine_corner_rhs<<<static_cast<unsigned>(ceil_div(static_cast<int64_t>(m / 6) * 64, 256)), 256, 0, stream>>>(
 	    ws.n0, m / 6, ws.dinv_b, ws.diag, ws.inc_off, ws.inc_list, edges, wing, ws.rhs, ws.x, ws.res, ws.corner->map().node_row,
@@ -534,7 +537,7 @@ nnrt_status arrowhead_solve_core(const ArrowheadWorkspace& ws, const int32_t* ed
 	                                                                                 ws.res, ws.dx, ws.x, gate, ratio, ws.corner->refine_guard());
 	NNRT_LAUNCH_CHECK();
 	k_refine_apply<<<static_cast<unsigned>(ceil_div(ws.N, 64)), 64, 0, stream>>>(ws.N, ws.dx, ws.x, state_in, node_state, updates_out, gate, ratio,
-	                                                                            ws.corner->refine_guard());
+	                                                                            ws.corner->refine_guard(), ws.guard_zero_rotation);
 	NNRT_LAUNCH_CHECK();
 	return NNRT_OK;
 }

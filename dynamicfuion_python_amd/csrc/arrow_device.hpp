@@ -95,7 +95,9 @@ __device__ __forceinline__ void store6(float* dst, const float (&v)[6]) {
 // the iteration started from is read from state_in (the warp field's state, or a snapshot the iteration restarts from)
 // and the result written to node_state (g is never changed by an update)
 // (state_in may equal node_state: no __restrict__ on either)
-__device__ __forceinline__ void arrow_update_node(int n, const float (&xl)[6], const float* state_in, float* node_state, float* __restrict__ updates_out) {
+// guard_rot (wavefront-uniform launch argument): a rotation increment of angle exactly 0 leaves R untouched (no 0 / 0)
+__device__ __forceinline__ void arrow_update_node(int n, const float (&xl)[6], const float* state_in, float* node_state, float* __restrict__ updates_out,
+                                                  bool guard_rot) {
 	for (int c = 0; c < 6; c++) updates_out[6 * static_cast<int64_t>(n) + c] = xl[c];
 	const float* os = state_in + static_cast<int64_t>(n) * NODE_STRIDE;
 	float* ns = node_state + static_cast<int64_t>(n) * NODE_STRIDE;
@@ -104,9 +106,13 @@ __device__ __forceinline__ void arrow_update_node(int n, const float (&xl)[6], c
 	ns[3] = old[0] + xl[3];
 	ns[4] = old[1] + xl[4];
 	ns[5] = old[2] + xl[5];
+	const float* R = old + 3;
+	if (guard_rot && rotation_update_is_zero(xl[0], xl[1], xl[2])) {
+		for (int i = 0; i < 9; i++) ns[6 + i] = R[i];
+		return;
+	}
 	float dR[9];
 	rodrigues_device(xl[0], xl[1], xl[2], dR);
-	const float* R = old + 3;
 	for (int r = 0; r < 3; r++)
 		for (int c = 0; c < 3; c++) ns[6 + 3 * r + c] = (R[3 * r] * dR[c] + R[3 * r + 1] * dR[3 + c]) + R[3 * r + 2] * dR[6 + c];
 }
@@ -256,7 +262,7 @@ __device__ __forceinline__ void arrow_back_node(int i, int n0, int n_update, con
                                                 const int* __restrict__ edge_list, const int32_t* __restrict__ edges, const float* __restrict__ wing,
                                                 const RL& rl, float* __restrict__ x, const XL& xc, const float* state_in, float* node_state,
                                                 float* __restrict__ updates_out, float* __restrict__ x_base, const BL& bl, int mode, bool refining,
-                                                const float* __restrict__ diag, float* __restrict__ res) {
+                                                const float* __restrict__ diag, float* __restrict__ res, bool guard_rot) {
 	if (mode == 1 && refining) node_state = nullptr;   // the refinement's last pass applies the update
 	if (i >= n0) {
 		if (i < n_update && (node_state || x_base)) {
@@ -270,7 +276,7 @@ __device__ __forceinline__ void arrow_back_node(int i, int n0, int n_update, con
 					x_base[6 * static_cast<int64_t>(i) + c] = xl[c];
 				}
 			}
-			if (node_state) arrow_update_node(i, xl, state_in, node_state, updates_out);
+			if (node_state) arrow_update_node(i, xl, state_in, node_state, updates_out, guard_rot);
 		}
 		return;
 	}
@@ -291,7 +297,7 @@ __device__ __forceinline__ void arrow_back_node(int i, int n0, int n_update, con
 			x_base[6 * static_cast<int64_t>(i) + c] = o[c];
 		}
 	}
-	if (node_state) arrow_update_node(i, o, state_in, node_state, updates_out);
+	if (node_state) arrow_update_node(i, o, state_in, node_state, updates_out, guard_rot);
 }
 
 // ---- the refinement's last passes (round 6: a safeguarded step) ----
@@ -343,7 +349,7 @@ __device__ __forceinline__ bool refine_guard_accepts(const unsigned* guard) {
 // else x_base; x_base <- x and the node's update (the solve's own pass skipped it while refining)
 template <class DL, class BL>
 __device__ __forceinline__ void refine_apply_node(int i, int n_update, bool accept, const DL& dl, const BL& bl, float* __restrict__ x_base,
-                                                  const float* state_in, float* node_state, float* __restrict__ updates_out) {
+                                                  const float* state_in, float* node_state, float* __restrict__ updates_out, bool guard_rot) {
 	if (i >= n_update) return;
 	float o[6];
 	bl.ld6(i, o);
@@ -356,7 +362,7 @@ __device__ __forceinline__ void refine_apply_node(int i, int n_update, bool acce
 			x_base[6 * static_cast<int64_t>(i) + c] = o[c];
 		}
 	}
-	if (node_state) arrow_update_node(i, o, state_in, node_state, updates_out);
+	if (node_state) arrow_update_node(i, o, state_in, node_state, updates_out, guard_rot);
 }
 
 // ---- iterative refinement: the correction's corner right-hand side of corner node a (one wave; lane < 6 returns entry

@@ -405,6 +405,10 @@ struct nnrt_fitter {
 	ArrowheadWorkspace aw;
 	float refine_ratio = NNRT_REFINE_PIVOT_RATIO;   // refinement gate threshold (nnrt_fitter_set_refine_ratio)
 	float refine_ratio_used = NNRT_REFINE_PIVOT_RATIO;   // the threshold the last launched iterations ran with (refine_info)
+	// nnrt_fitter_set_robust_options: the form the Tukey / Huber penalties take where the parameters enable them, and
+	// whether a node update of rotation angle exactly 0 keeps the rotation (launch arguments of every iteration)
+	int32_t penalty_form = NNRT_PENALTY_REFERENCE;
+	int32_t guard_zero_rotation = 0;
 	int n0 = 0;
 	int last_mode = 0;
 	DeviceBuffer<float> snapshot;   // [N,16] node state stored by nnrt_fitter_snapshot_motion (restore-before-iteration runs)
@@ -521,7 +525,8 @@ nnrt_status enqueue_iteration(nnrt_fitter* ft, const nnrt_warp_field* wf, int mo
 	fa.ay = ro.ay;
 	fa.perspective = ft->p.use_perspective_correction;
 	fa.max_depth = ft->p.max_depth;
-	fa.use_tukey = ft->p.use_tukey_penalty_for_data_term;
+	const int penalty = ft->penalty_form == NNRT_PENALTY_IRLS ? PENALTY_IRLS : PENALTY_REFERENCE;
+	fa.use_tukey = ft->p.use_tukey_penalty_for_data_term ? penalty : PENALTY_NONE;
 	fa.tukey_c = ft->p.tukey_penalty_cutoff_cm;
 	fa.anchor_count = ft->K;
 	fa.keys = ft->keys.ptr;
@@ -556,7 +561,7 @@ nnrt_status enqueue_iteration(nnrt_fitter* ft, const nnrt_warp_field* wf, int mo
 		aa.N = ft->N;
 		aa.n0 = ft->n0;
 		aa.lambda = ft->p.arap_term_weight;
-		aa.use_huber = ft->p.use_huber_penalty_for_arap_term;
+		aa.use_huber = ft->p.use_huber_penalty_for_arap_term ? penalty : PENALTY_NONE;
 		aa.huber_delta = ft->p.huber_penalty_constant;
 		aa.coverage_variable = wf->coverage_method == NNRT_MINIMAL_K_NEIGHBOR_NODE_DISTANCE;
 		aa.edges = wf->edges.ptr;
@@ -592,6 +597,7 @@ nnrt_status enqueue_iteration(nnrt_fitter* ft, const nnrt_warp_field* wf, int mo
 		sa.gradient_out = ft->gradient.ptr;
 		sa.hessian_out = ft->hessian.ptr;
 		sa.error_flag = ft->error_flag.ptr;
+		sa.guard_zero_rotation = ft->guard_zero_rotation;
 		if ((st = launch_solve_update(mode, sa, s, from_identity))) return st;
 	}
 	return mark(6);
@@ -871,6 +877,7 @@ nnrt_status prepare_frame(nnrt_fitter* ft, nnrt_warp_field* wf, const float* d_v
 		ft->aw.x = ft->a_x.ptr;
 		ft->aw.refine = NNRT_ARAP_REFINE != 0;
 		ft->aw.refine_ratio = ft->refine_ratio;
+		ft->aw.guard_zero_rotation = ft->guard_zero_rotation;
 		ft->aw.res = ft->a_res.ptr;
 		ft->aw.dx = ft->a_dx.ptr;
 		ft->aw.edge_offsets = ft->a_offsets.ptr;
@@ -1256,6 +1263,28 @@ nnrt_status nnrt_fitter_set_refine_ratio(nnrt_fitter* ft, float ratio) {
 	ft->refine_ratio = ratio;
 	ft->aw.refine_ratio = ratio;
 	ft->drop_graphs();   // the threshold is a launch argument of the captured sequences
+	return NNRT_OK;
+}
+
+nnrt_status nnrt_fitter_set_robust_options(nnrt_fitter* ft, int32_t penalty_form, int32_t guard_zero_rotation) {
+	NNRT_CHECK_ARG(ft, "null pointer");
+	NNRT_CHECK_ARG(penalty_form == NNRT_PENALTY_REFERENCE || penalty_form == NNRT_PENALTY_IRLS,
+	               "penalty_form must be NNRT_PENALTY_REFERENCE (0) or NNRT_PENALTY_IRLS (1)");
+	NNRT_CHECK_ARG(guard_zero_rotation == 0 || guard_zero_rotation == 1, "guard_zero_rotation must be 0 or 1");
+	if (penalty_form == ft->penalty_form && guard_zero_rotation == ft->guard_zero_rotation) return NNRT_OK;
+	DeviceGuard guard(ft->device);
+	NNRT_HIP(hipStreamSynchronize(ft->work));
+	ft->penalty_form = penalty_form;
+	ft->guard_zero_rotation = guard_zero_rotation;
+	ft->aw.guard_zero_rotation = guard_zero_rotation;
+	ft->drop_graphs();   // both are launch arguments of the captured sequences; the prepared frame stays
+	return NNRT_OK;
+}
+
+nnrt_status nnrt_fitter_get_robust_options(const nnrt_fitter* ft, int32_t* penalty_form, int32_t* guard_zero_rotation) {
+	NNRT_CHECK_ARG(ft && penalty_form && guard_zero_rotation, "null pointer");
+	*penalty_form = ft->penalty_form;
+	*guard_zero_rotation = ft->guard_zero_rotation;
 	return NNRT_OK;
 }
 

@@ -1791,11 +1791,11 @@ __global__ __launch_bounds__(CT) void k_corner_flow(FlowArgs a) {
 			float o[6];
 			stem_solve_pre(i, pre, a.st.dinv, a.st.wing, XPlain{a.st.rhs}, x_sc1, o);
 			store6<true>(a.st.x + 6 * static_cast<int64_t>(i), o);
-			if (a.st.node_state) arrow_update_node(i, o, a.st.state_in, a.st.node_state, a.st.updates_out);
+			if (a.st.node_state) arrow_update_node(i, o, a.st.state_in, a.st.node_state, a.st.updates_out, a.st.guard_zero_rotation != 0);
 		} else if (live)
 			arrow_back_node<true>(i, a.st.n0, a.st.n_update, a.st.dinv, a.st.edge_offsets, a.st.edge_list, a.st.edges, a.st.wing,
 			                      XPlain{a.st.rhs}, a.st.x, x_sc1, a.st.state_in, a.st.node_state, a.st.updates_out, nullptr, XPlain{nullptr},
-			                      a.st.mode, refining, a.st.diag, a.st.res);
+			                      a.st.mode, refining, a.st.diag, a.st.res, a.st.guard_zero_rotation != 0);
 		if (a.refine) flow_signal(ctl0 + 2);
 		FLOW_RT(k + nB, 64, 2);
 		return;
@@ -1854,7 +1854,8 @@ __global__ __launch_bounds__(CT) void k_corner_flow(FlowArgs a) {
 	}
 	k -= S;
 	if (!flow_wait(guard + REFINE_GUARD_COUNT, static_cast<unsigned>(S), a.st.error_flag)) return;
-	refine_apply_node(k * CT + t, a.st.N, refine_guard_accepts(guard), dx_sc1, x_sc1, a.st.x, a.st.state_in, a.st.node_state, a.st.updates_out);
+	refine_apply_node(k * CT + t, a.st.N, refine_guard_accepts(guard), dx_sc1, x_sc1, a.st.x, a.st.state_in, a.st.node_state, a.st.updates_out,
+	                  a.st.guard_zero_rotation != 0);
 }
 
 // ===================================================================================================================

@@ -150,7 +150,20 @@ __device__ __forceinline__ void pixel_body(const FitPixelArgs& a, float* dn, int
 		float dist = dot3(nl, d);
 		if (!mask) dist = 0.0f;
 		float residual = dist;
-		if (a.use_tukey) {
+		bool contributes = mask;
+		f3 dr_dwl = nl, dr_dnl = d;
+		if (a.use_tukey == PENALTY_IRLS) {
+			// iteratively re-weighted least squares with Tukey's biweight (1 - q^2)^2, q = r / c: residual and Jacobian
+			// row are both scaled by its square root s, so pass 2 sums s^2 J^T J and (s J)^T (s r); a pixel beyond the
+			// cutoff (or with a NaN residual) carries no weight
+			const float c = a.tukey_c;
+			contributes = mask && fabsf(dist) <= c;
+			const float qq = dist / c;
+			const float s = 1.f - qq * qq;
+			residual = contributes ? s * dist : 0.f;
+			dr_dwl = make3(s * nl.x, s * nl.y, s * nl.z);
+			dr_dnl = make3(s * d.x, s * d.y, s * d.z);
+		} else if (a.use_tukey) {
 			const float c = a.tukey_c;
 			const float c6 = (c * c / 6.f);
 			const float qq = dist / c;
@@ -162,9 +175,7 @@ __device__ __forceinline__ void pixel_body(const FitPixelArgs& a, float* dn, int
 		a.residual_mask[p] = mask ? 1 : 0;
 		a.pixel_face[p] = face;
 
-		bool contributes = mask;
-		f3 dr_dwl = nl, dr_dnl = d;
-		if (contributes && a.use_tukey) {
+		if (contributes && a.use_tukey == PENALTY_REFERENCE) {
 			const float r = dot3(nl, d);
 			if (fabsf(r) > a.tukey_c) contributes = false;
 			const float qq = r / a.tukey_c;
@@ -1202,8 +1213,9 @@ nnrt_status launch_fit_pixels(int mode, const FitPixelArgs& args, hipStream_t st
 // t += dt, R <- R * dR). One thread per node; consumes and re-zeroes the accumulator row.
 // =====================================================================================================================
 // old = the node's (t, R) as loaded at kernel start (stride-15 state row, entries 3..14)
+// guard (SolveArgs::guard_zero_rotation, wavefront-uniform): a rotation update of angle exactly 0 leaves R as it is
 template <int MODE>
-__device__ inline void apply_update(float* ns, const float* old, const float* x) {
+__device__ inline void apply_update(float* ns, const float* old, const float* x, bool guard) {
 	if (MODE == NNRT_ITERATION_ALL) {
 		ns[3] = old[0] + x[3];
 		ns[4] = old[1] + x[4];
@@ -1217,7 +1229,7 @@ __device__ inline void apply_update(float* ns, const float* old, const float* x)
 		ns[4] = old[1];
 		ns[5] = old[2];
 	}
-	if (MODE != NNRT_ITERATION_TRANSLATION_ONLY) {
+	if (MODE != NNRT_ITERATION_TRANSLATION_ONLY && !(guard && rotation_update_is_zero(x[0], x[1], x[2]))) {
 		float dR[9], R[9], o[9];
 		rodrigues_device(x[0], x[1], x[2], dR);
 #pragma unroll
@@ -1316,7 +1328,7 @@ __global__ __launch_bounds__(64) void k_solve_update(SolveArgs a) {
 	}
 #pragma unroll
 	for (int c = 0; c < S; c++) a.updates_out[static_cast<int64_t>(n) * S + c] = x[c];
-	apply_update<MODE>(ns, old, x);
+	apply_update<MODE>(ns, old, x, a.guard_zero_rotation != 0);
 }
 
 // Eight lanes per node (lane r of the node's group owns row r of H and of its factor L): the same operations as
@@ -1448,7 +1460,7 @@ __global__ __launch_bounds__(64) void k_solve_update_lanes(SolveArgs a) {
 	for (int c = 1; c < S; c++) xr = r == c ? x[c] : xr;
 	if (gl < S) a.updates_out[static_cast<int64_t>(n) * S + r] = xr;
 	float o[15];
-	apply_update<MODE>(o, old, x);   // o[3 .. 14]: the node's new (t, R)
+	apply_update<MODE>(o, old, x, a.guard_zero_rotation != 0);   // o[3 .. 14]: the node's new (t, R)
 	float* ns = a.node_state + static_cast<int64_t>(n) * NODE_STRIDE;
 	float v0 = o[3], v1 = o[11];
 #pragma unroll

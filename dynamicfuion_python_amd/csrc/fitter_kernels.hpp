@@ -16,11 +16,15 @@ namespace nnrt {
 #endif
 constexpr int ACC_STRIDE = 28;   // per node: 21 JtJ upper-triangle entries + 6 Jt r (+1 pad); 3-dof modes use 6 + 3
 
+// values of FitPixelArgs::use_tukey and ArapArgs::use_huber (launch arguments, wavefront-uniform): no penalty, the
+// reference's branches as written, or the re-weighted forms of nnrt_fitter_set_robust_options
+constexpr int PENALTY_NONE = 0, PENALTY_REFERENCE = 1, PENALTY_IRLS = 2;
+
 // ARAP (regularized, mode ALL) path
 struct ArapArgs {
 	int E, N, n0;
 	float lambda;
-	int use_huber;
+	int use_huber;                  // PENALTY_*
 	float huber_delta;
 	int coverage_variable;          // 1: edge weight = max(c2_i, c2_j)
 	const int32_t* edges;           // [E,2] virtual
@@ -78,15 +82,25 @@ __device__ inline void arap_edge(const ArapArgs& a, int e) {
 	const float lw = a.lambda * w_res;
 	float r[3] = {lw * (((gi.x + ti.x) - (gj.x + tj.x)) - Rd.x), lw * (((gi.y + ti.y) - (gj.y + tj.y)) - Rd.y),
 	              lw * (((gi.z + ti.z) - (gj.z + tj.z)) - Rd.z)};
-	if (a.use_huber) {
+	if (a.use_huber == PENALTY_REFERENCE) {
 		const float half = 0.5f * a.huber_delta * a.huber_delta;
 #pragma unroll
 		for (int c = 0; c < 3; c++) r[c] = (r[c] >= a.huber_delta) ? fabsf(r[c]) - half : 0.5f * r[c] * r[c];
 	}
+	const float s = -a.lambda * w_jac;
+	float j5[5] = {s * Rd.x, s * Rd.y, s * Rd.z, a.lambda * w_jac, -a.lambda * w_jac};
+	if (a.use_huber == PENALTY_IRLS) {
+		// iteratively re-weighted least squares with Huber's weight on the edge's 3-vector: min(1, delta / |r|), whose
+		// square root scales the residual and the Jacobian terms; everything below follows from the scaled values
+		const float n = sqrtf((r[0] * r[0] + r[1] * r[1]) + r[2] * r[2]);
+		const float hs = (n <= a.huber_delta) ? 1.f : sqrtf(a.huber_delta / n);
+#pragma unroll
+		for (int c = 0; c < 3; c++) r[c] *= hs;
+#pragma unroll
+		for (int c = 0; c < 5; c++) j5[c] *= hs;
+	}
 #pragma unroll
 	for (int c = 0; c < 3; c++) a.edge_residuals[3 * e + c] = r[c];
-	const float s = -a.lambda * w_jac;
-	const float j5[5] = {s * Rd.x, s * Rd.y, s * Rd.z, a.lambda * w_jac, -a.lambda * w_jac};
 	float dEi[3][6];
 	edge_block_i(j5, dEi);
 	// wing block dEi^T dEj: dEj = [0 | b I]
@@ -160,7 +174,7 @@ struct FitPixelArgs {
 	PixelAxis ax, ay;       // pixel-centre NDC constants (make_pixel_axis)
 	int perspective;
 	float max_depth;
-	int use_tukey;
+	int use_tukey;          // PENALTY_*
 	float tukey_c;
 	int anchor_count;
 	uint64_t* keys;         // [P] raster keys (consumed and reset)
@@ -199,6 +213,7 @@ struct SolveArgs {
 	float* gradient_out;    // [N*s]
 	float* hessian_out;     // [N*s*s] (nullable)
 	int* error_flag;
+	int guard_zero_rotation;   // 1: a node whose rotation update has angle exactly 0 keeps its R (0: Rodrigues' NaN, A7)
 };
 
 // Per face (once per frame, after the anchors): the face's distinct anchor nodes in ascending order, each with, per face
@@ -326,6 +341,7 @@ struct FlowStem {
 	unsigned* guard = nullptr;    // the refinement safeguard's words (the gate word's block: REFINE_GUARD_*)
 	float ratio = 0.f;
 	int* error_flag = nullptr;
+	int guard_zero_rotation = 0;   // the node updates keep R where the rotation increment is exactly zero
 };
 __host__ __device__ inline int flow_ctl_words(int nB) { return 4 + 3 * nB; }
 
@@ -464,6 +480,7 @@ struct ArrowheadWorkspace {
 	// the correction; the update is x + dx
 	bool refine = false;
 	float refine_ratio = NNRT_REFINE_PIVOT_RATIO;   // gate threshold on the corner's min pivot / diag(S)
+	int guard_zero_rotation = 0;   // nnrt_fitter_set_robust_options: the node updates keep R where the rotation increment is 0
 	float* res = nullptr;
 	float* dx = nullptr;
 	int* edge_offsets = nullptr;// [n0+1] CSR of stem edges by source node (edges grouped by source)

@@ -190,6 +190,11 @@ __device__ inline void rodrigues_device(float w0, float w1, float w2, float* R) 
 	}
 }
 
+// the fitter's zero-rotation guard (nnrt_fitter_set_robust_options): rodrigues_device's angle of this update is exactly
+// zero, so its axis would be 0 / 0; the update sites then leave the node's rotation as it is. A NaN update is not
+// guarded: it stays NaN.
+__device__ inline bool rotation_update_is_zero(float w0, float w1, float w2) { return sqrtf((w0 * w0 + w1 * w1) + w2 * w2) == 0.f; }
+
 // lower Cholesky of an n x n (n <= 6) row-major SPD matrix in registers (LAPACK potrf semantics); false if not PD
 template <int n>
 __host__ __device__ inline bool cholesky_small(float (&A)[n][n]) {

@@ -19,7 +19,8 @@ first frame (`FIRST_FRAME_LOADED_GRAPH`) or nodes supplied by the caller; the re
 
 Deviations: the mesh-extraction ramp counts processed frames, not frame-index differences (DeepDeform test
 sequences ship sparse frames 300, 600, ...); the data and ARAP penalties default to SQUARE because the reference fitter's
-Tukey and Huber branches carry quirks A8/A9; the fitter runs with NDC_CONSISTENT, because the reference's image -> NDC
+Tukey and Huber branches carry quirks A8/A9 (real sequences should be run with the re-weighted forms instead, see
+below); the fitter runs with NDC_CONSISTENT, because the reference's image -> NDC
 mapping renders the mesh y-mirrored about cy (A11) and so fits a mirrored surface to a real depth frame.
 
 `FusionParameters.anchor_computation_mode = AnchorComputationMode.SHORTEST_PATH` (reference pipeline.py:577-582) makes the
@@ -27,6 +28,17 @@ tracker anchor the canonical mesh along the motion graph's edges -- the DeepDefo
 graph's geodesic rows, re-indexed to the warp field's virtual node order -- instead of to the Euclidean-nearest nodes.
 Only the fit uses these anchors: TSDF integration and `warp_mesh` keep the warp field's own Euclidean anchors, as in the
 reference.
+
+Real sequences: pass `FusionParameters(alignment=RenderingAlignmentParameters(data_term_penalty_function=
+PenaltyFunction.TUKEY, regularization_term_penalty_function=PenaltyFunction.HUBER, penalty_form=PenaltyForm.IRLS,
+guard_zero_rotation=True, ndc_convention=NDC_CONSISTENT, ...))`. With `PenaltyForm.IRLS` the penalties are iteratively
+re-weighted least squares instead of the reference's branches: a masked-in pixel with point-to-plane residual r and
+cutoff c contributes iff |r| <= c, and its residual and Jacobian row are scaled by s = 1 - (r / c)^2 (Tukey's biweight
+(1 - (r / c)^2)^2 on the squared residual), so depth discontinuities, occlusion edges and sensor outliers carry no
+weight; an ARAP edge's residual 3-vector r and its Jacobian terms are scaled by s = 1 if |r| <= delta else
+sqrt(delta / |r|) (Huber's weight min(1, delta / |r|)). `guard_zero_rotation=True` keeps the rotation of a node whose
+rotation update is exactly zero (every node without pixels), where the reference's Rodrigues formula gives NaN (A7).
+The defaults (`_default_alignment`) keep their values.
 """
 from __future__ import annotations
 

@@ -24,6 +24,14 @@ class IterationMode(enum.IntEnum):
     ROTATION_ONLY = 2
 
 
+class PenaltyForm(enum.IntEnum):
+    """The form the Tukey (data term) and Huber (ARAP term) penalties take where the fitter's parameters enable them
+    (include/nnrt_mi355x.h NNRT_PENALTY_*): the reference's branches as written, or iteratively
+    re-weighted least squares."""
+    REFERENCE = 0
+    IRLS = 1
+
+
 NDC_REFERENCE = 0     # the reference's image -> NDC mapping (SURVEY A11)
 NDC_CONSISTENT = 1    # raster pixel (u, v) == pixel (u, v) of the intrinsics
 
@@ -38,7 +46,8 @@ class DeformableMeshToImageFitter:
                  use_perspective_correction: bool = True, max_depth: float = 10.0, use_tukey_penalty_for_data_term: bool = False,
                  tukey_penalty_cutoff_cm: float = 0.01, preconditioning_dampening_factor: float = 0.0, arap_term_weight: float = 200.0,
                  use_huber_penalty_for_arap_term: bool = False, huber_penalty_constant: float = 1e-4, device: int | None = None,
-                 use_hip_graph: int = 1, ndc_convention: int = 0):
+                 use_hip_graph: int = 1, ndc_convention: int = 0, penalty_form: PenaltyForm = PenaltyForm.REFERENCE,
+                 guard_zero_rotation: bool = False):
         device = N.current_device() if device is None else int(device)
         p = N.FitterParams()
         N.lib().nnrt_fitter_default_params(ctypes.byref(p))
@@ -65,6 +74,7 @@ class DeformableMeshToImageFitter:
         self.device = torch.device("cuda", device)
         self.modes = modes
         self._frame = None
+        self.set_robust_options(penalty_form, guard_zero_rotation)
 
     def __del__(self):
         h = getattr(self, "_h", None)
@@ -158,6 +168,29 @@ class DeformableMeshToImageFitter:
         1e-2; 0: never refine; inf: refine whenever the ratio is at least the floor). refine_info() reports
         the threshold the last launched iterations ran with."""
         N.check(N.lib().nnrt_fitter_set_refine_ratio(self._h, float(ratio)))
+
+    def set_robust_options(self, penalty_form, guard_zero_rotation):
+        """penalty_form: PenaltyForm.REFERENCE (default) keeps the reference's Tukey / Huber branches; PenaltyForm.IRLS
+        re-weights instead. Data term (use_tukey_penalty_for_data_term): a masked-in pixel with residual r contributes
+        iff |r| <= c; s = 1 - (r / c)^2, residual s r, Jacobian row s J. ARAP term (use_huber_penalty_for_arap_term):
+        the edge's residual 3-vector and Jacobian terms times s = 1 if |r| <= delta else sqrt(delta / |r|). No effect on
+        a square term. guard_zero_rotation: a node whose rotation update is exactly zero keeps its rotation instead of
+        getting Rodrigues' NaN. Drops the cached graphs, keeps the prepared frame; other values raise."""
+        if isinstance(guard_zero_rotation, (bool, np.bool_)):
+            guard_zero_rotation = int(guard_zero_rotation)
+        N.check(N.lib().nnrt_fitter_set_robust_options(self._h, int(penalty_form), int(guard_zero_rotation)))
+
+    @property
+    def robust_options(self):
+        """(PenaltyForm, guard_zero_rotation) as the fitter holds them."""
+        form, guard = ctypes.c_int32(), ctypes.c_int32()
+        N.check(N.lib().nnrt_fitter_get_robust_options(self._h, ctypes.byref(form), ctypes.byref(guard)))
+        return PenaltyForm(form.value), bool(guard.value)
+
+    @property
+    def graph_count(self) -> int:
+        """Instantiated iteration-sequence graphs the fitter holds."""
+        return int(N.lib().nnrt_fitter_graph_count(self._h))
 
     def set_anchor_graph(self, edges, stream=None):
         """Anchor the canonical mesh along a motion graph's edges (the reference's AnchorComputationMethod.SHORTEST_PATH):

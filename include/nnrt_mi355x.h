@@ -188,6 +188,24 @@ nnrt_status nnrt_fitter_refine_info(nnrt_fitter* fitter, float* h_out, void* str
  * diag(S) ratio falls below it (and is at least 1e-5); 0 never refines. Drops the fitter's cached graphs (a launch
  * argument). */
 nnrt_status nnrt_fitter_set_refine_ratio(nnrt_fitter* fitter, float ratio);
+/* Robust options (both off by default: the reference's arithmetic, NaN for NaN). They are launch arguments, so the
+ * setter drops the fitter's cached graphs; the prepared frame stays. Any other value of either argument is
+ * NNRT_ERROR_ARGUMENT, nnrt_last_error() naming the argument.
+ *  penalty_form: the form of the penalties that use_tukey_penalty_for_data_term / use_huber_penalty_for_arap_term
+ *   enable (no effect on a square term). NNRT_PENALTY_REFERENCE: the reference's branches as written.
+ *   NNRT_PENALTY_IRLS: iteratively re-weighted least squares.
+ *    Data term, Tukey's biweight: r = n_l . (w_l - o_l), c = tukey_penalty_cutoff_cm; a pixel contributes iff it is
+ *    masked in and |r| <= c; q = r / c, s = 1 - q q (the square root of the weight (1 - q^2)^2); residual s r (0 where
+ *    the pixel does not contribute), Jacobian row s J: H = sum s^2 J^T J, g = sum (s J)^T (s r).
+ *    ARAP term, Huber's weight on the edge's residual 3-vector r: n = |r|, delta = huber_penalty_constant,
+ *    s = 1 if n <= delta else sqrt(delta / n); the edge's residual and Jacobian terms are multiplied by s.
+ *  guard_zero_rotation: 1 = a node whose rotation update has angle exactly 0 (every node without pixels under the
+ *   block-diagonal solve) keeps its rotation; its translation update is applied as usual. 0: Rodrigues' 0 / 0 makes that
+ *   node's rotation NaN, as in the reference. nnrt_axis_angle_to_matrices_rodrigues is not affected. */
+#define NNRT_PENALTY_REFERENCE 0
+#define NNRT_PENALTY_IRLS 1
+nnrt_status nnrt_fitter_set_robust_options(nnrt_fitter* fitter, int32_t penalty_form, int32_t guard_zero_rotation);
+nnrt_status nnrt_fitter_get_robust_options(const nnrt_fitter* fitter, int32_t* penalty_form, int32_t* guard_zero_rotation);
 /* Anchor the canonical mesh along a motion graph's edges instead of by Euclidean distance (the reference's
  * AnchorComputationMethod::SHORTEST_PATH, PlanarGraphWarpField::PrecomputeAnchorsAndWeights; apps/fusion/pipeline.py:577-582):
  * d_edges [node_count, graph_degree] int32 rows in the warp field's virtual node order (entry < 0 = empty) are copied
