@@ -98,6 +98,9 @@ _SIGNATURES = {
                                                    c_void_p, c_void_p, c_void_p]),
     "nnrt_compute_anchors_and_weights_shortest_path": (c_int32, [c_void_p, c_int64, c_void_p, c_int32, c_void_p, c_int32, c_int32, c_float,
                                                                  c_void_p, c_void_p, c_void_p, c_void_p]),
+    "nnrt_rigid_align_point_to_plane": (c_int32, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int32, c_int32, c_float, c_float, c_float,
+                                                  c_float, c_void_p, c_int32, c_float, c_float, c_int32, c_int32, c_void_p, c_void_p, c_int32,
+                                                  c_void_p, c_void_p]),
     "nnrt_warp_mesh": (c_int32, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_int32,
                                  c_void_p, c_void_p, c_void_p, c_void_p]),
     "nnrt_warp_points": (c_int32, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_int32, c_float,

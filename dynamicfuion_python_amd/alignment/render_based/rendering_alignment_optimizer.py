@@ -85,9 +85,10 @@ class RenderingAlignmentOptimizer:
         every later optimize_graph call (AnchorComputationMode.SHORTEST_PATH); None: Euclidean anchors."""
         self.fitter.set_anchor_graph(edges)
 
-    def optimize_graph(self, graph: G.HierarchicalGraphWarpField, tsdf, target_points, target_rgb=None):
+    def optimize_graph(self, graph: G.HierarchicalGraphWarpField, tsdf, target_points, target_rgb=None, extrinsics=None):
         """tsdf: an object with extract_surface_mesh(-1, 0) (NonRigidSurfaceVoxelBlockGrid) or the canonical mesh
-        itself; target_points: organized [H,W,3] / [H*W,3] camera-space points (z <= 0 or non-finite = no target)."""
+        itself; target_points: organized [H,W,3] / [H*W,3] camera-space points (z <= 0 or non-finite = no target);
+        extrinsics: the 4 x 4 world -> camera matrix the fitter applies to the mesh (None: identity)."""
         mesh = tsdf.extract_surface_mesh(-1, 0) if hasattr(tsdf, "extract_surface_mesh") else tsdf
         mesh = as_triangle_mesh(mesh)
         H, W = self.image_size_hw
@@ -95,5 +96,5 @@ class RenderingAlignmentOptimizer:
         pts = pts.to(torch.float32).reshape(H * W, 3)
         valid = torch.isfinite(pts).all(dim=1) & (pts[:, 2] > 0)
         pts = torch.where(valid[:, None], pts, torch.zeros_like(pts))
-        self.fitter.fit_to_image(graph, mesh, target_rgb, pts, valid.to(torch.uint8), self.intrinsic_matrix, None, (H, W))
+        self.fitter.fit_to_image(graph, mesh, target_rgb, pts, valid.to(torch.uint8), self.intrinsic_matrix, extrinsics, (H, W))
         return graph

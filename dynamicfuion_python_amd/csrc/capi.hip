@@ -1581,6 +1581,40 @@ nnrt_status nnrt_compute_anchors_and_weights_shortest_path(const float* d_points
 	                                    static_cast<hipStream_t>(stream));
 }
 
+nnrt_status nnrt_rigid_align_point_to_plane(const float* d_points, const float* d_normals, int64_t V, const float* d_target_points,
+                                            const float* d_target_normals, int32_t H, int32_t W, float fx, float fy, float cx, float cy,
+                                            const double* h_T_init, int32_t iterations, float distance_threshold, float normal_agreement_cos,
+                                            int32_t cull_back_faces, int32_t minimum_correspondence_count, double* h_T_out, double* h_log,
+                                            int32_t log_row_capacity, int32_t* h_status, void* stream) {
+	NNRT_CHECK_ARG(V >= 0, "points: negative vertex count");
+	NNRT_CHECK_ARG(V == 0 || d_points, "points: null pointer");
+	NNRT_CHECK_ARG(V == 0 || d_normals, "normals: null pointer");
+	NNRT_CHECK_ARG(H >= 1 && W >= 1, "target_points: height and width must be at least 1");
+	NNRT_CHECK_ARG(V == 0 || d_target_points, "target_points: null pointer");
+	NNRT_CHECK_ARG(V == 0 || d_target_normals, "target_normals: null pointer");
+	NNRT_CHECK_ARG(std::isfinite(fx) && std::isfinite(fy) && std::isfinite(cx) && std::isfinite(cy), "intrinsics: fx, fy, cx, cy must be finite");
+	NNRT_CHECK_ARG(h_T_init, "T_init: null pointer");
+	for (int k = 0; k < 12; k++) NNRT_CHECK_ARG(std::isfinite(h_T_init[k]), "T_init: rows 0..2 must be finite");
+	NNRT_CHECK_ARG(iterations >= 1, "iterations must be at least 1");
+	NNRT_CHECK_ARG(std::isfinite(distance_threshold) && distance_threshold > 0.f, "distance_threshold must be positive and finite");
+	NNRT_CHECK_ARG(!std::isnan(normal_agreement_cos), "normal_agreement_cos is NaN");
+	NNRT_CHECK_ARG(minimum_correspondence_count >= 0, "minimum_correspondence_count is negative");
+	NNRT_CHECK_ARG(h_T_out, "T_out: null pointer");
+	NNRT_CHECK_ARG(h_log, "log: null pointer");
+	NNRT_CHECK_ARG(log_row_capacity >= iterations, "log: room for " + std::to_string(log_row_capacity) + " rows, " +
+	                                                    std::to_string(iterations) + " iterations need as many");
+	NNRT_CHECK_ARG(h_status, "status: null pointer");
+	if (V == 0) {   // nothing to align: an ordinary result
+		for (int k = 0; k < 16; k++) h_T_out[k] = h_T_init[k];
+		for (int k = 0; k < 2 * iterations; k++) h_log[k] = 0.0;
+		*h_status = NNRT_RIGID_ALIGN_DEGENERATE;
+		return NNRT_OK;
+	}
+	return launch_rigid_align(d_points, d_normals, V, d_target_points, d_target_normals, H, W, fx, fy, cx, cy, h_T_init, iterations,
+	                          distance_threshold, normal_agreement_cos, cull_back_faces, minimum_correspondence_count, h_T_out, h_log, h_status,
+	                          static_cast<hipStream_t>(stream));
+}
+
 nnrt_status nnrt_compute_anchors_and_weights(const float* d_points, int64_t V, const float* d_nodes, int32_t N, int32_t K, float coverage,
                                              const float* d_node_weights, int32_t minimum_valid, int32_t* d_anchors, float* d_weights,
                                              void* stream) {

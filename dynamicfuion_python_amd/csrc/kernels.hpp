@@ -92,6 +92,12 @@ nnrt_status launch_anchors_shortest_path(const float* points, int64_t V, const f
                                          float coverage, const float* node_weights, int32_t* anchors, float* weights, hipStream_t stream,
                                          bool edges_checked = false);
 nnrt_status check_anchor_edges(const int32_t* edges, int N, int D, hipStream_t stream);
+// rigid_align.hip: `iterations` point-to-plane Gauss-Newton steps of the rigid pose on the device (arguments checked by the
+// caller, V >= 1); h_T_out [16], h_log [iterations, 2]. Synchronizes `stream` once, at the end.
+nnrt_status launch_rigid_align(const float* points, const float* normals, int64_t V, const float* target_points, const float* target_normals, int H,
+                               int W, float fx, float fy, float cx, float cy, const double* h_T_init, int iterations, float distance_threshold,
+                               float normal_agreement_cos, int cull_back_faces, int minimum_correspondence_count, double* h_T_out, double* h_log,
+                               int32_t* h_status, hipStream_t stream);
 nnrt_status launch_warp_mesh(const float* points, const float* normals, int64_t V, const float* node_state, const int32_t* anchors,
                              const float* weights, int K, const WarpExtrinsics& E, float4* out_p, float4* out_n, float2* jrows,
                              hipStream_t stream, bool from_identity = false, const uint2* anchors16 = nullptr);

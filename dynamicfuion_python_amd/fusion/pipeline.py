@@ -14,8 +14,13 @@ the first frame's extracted mesh on the GPU (`GraphGenerationMode.FIRST_FRAME_EX
 default graph from the first masked depth image on the GPU (`FIRST_FRAME_DEPTH_IMAGE` together with
 `FusionParameters.graph_from_depth_image=True`: pixel-connected mesh, erosion, node sampling, geodesic edges, clean-up,
 clusters) -- both need nothing but depth frames --, uses the DeepDeformGraph file of the
-first frame (`FIRST_FRAME_LOADED_GRAPH`) or nodes supplied by the caller; the reference's rigid odometry (Open3D
-`rgbd_odometry_multi_scale`) is out of scope (the camera is static, identity extrinsics, as in the DeepDeform sequences).
+first frame (`FIRST_FRAME_LOADED_GRAPH`) or nodes supplied by the caller.
+
+Camera motion: with `FusionParameters.rigid_alignment=True` every tracked frame first aligns the previous frame's warped
+mesh rigidly to the live point image on the GPU (`nnrt.alignment.align_rigid_point_to_plane`; the reference
+calls Open3D's `rgbd_odometry_multi_scale` at pipeline.py:338-354 and drops its result) and hands the estimated
+extrinsics to the fit and to the TSDF calls, so the warp field is left with the non-rigid residual. Off (the default),
+the extrinsics stay the identity: a static camera.
 
 Deviations: the mesh-extraction ramp counts processed frames, not frame-index differences (DeepDeform test
 sequences ship sparse frames 300, 600, ...); the data and ARAP penalties default to SQUARE because the reference fitter's
@@ -36,7 +41,8 @@ re-weighted least squares instead of the reference's branches: a masked-in pixel
 cutoff c contributes iff |r| <= c, and its residual and Jacobian row are scaled by s = 1 - (r / c)^2 (Tukey's biweight
 (1 - (r / c)^2)^2 on the squared residual), so depth discontinuities, occlusion edges and sensor outliers carry no
 weight; an ARAP edge's residual 3-vector r and its Jacobian terms are scaled by s = 1 if |r| <= delta else
-sqrt(delta / |r|) (Huber's weight min(1, delta / |r|)). `guard_zero_rotation=True` keeps the rotation of a node whose
+sqrt(delta / |r|) (Huber's weight min(1, delta / |r|)). Hand-held sequences (DeepDeform's are) also want
+`rigid_alignment=True`. `guard_zero_rotation=True` keeps the rotation of a node whose
 rotation update is exactly zero (every node without pixels), where the reference's Rodrigues formula gives NaN (A7).
 The defaults (`_default_alignment`) keep their values.
 """
@@ -56,7 +62,7 @@ from ..data import camera as dcam
 from ..data.frame import FrameSequenceDataset
 from ..nnrt import geometry as G
 from ..nnrt import image_proc
-from ..nnrt.alignment import NDC_CONSISTENT
+from ..nnrt.alignment import NDC_CONSISTENT, align_rigid_point_to_plane
 from ..warp_field.graph_warp_field import build_graph_nodes_from_depth_image, sample_graph_nodes_from_mesh
 
 
@@ -129,6 +135,11 @@ class FusionParameters:
     graph_remove_nodes_with_too_few_neighbors: bool = True
     graph_use_only_valid_vertices: bool = True
     graph_sample_random_shuffle: bool = False
+    # rigid frame-to-model alignment ahead of the non-rigid fit; off: the extrinsics stay the identity
+    rigid_alignment: bool = False
+    rigid_alignment_iteration_counts: tuple = (6, 3, 1)   # coarse to fine
+    rigid_alignment_distance_threshold: float = 0.07
+    rigid_alignment_normal_agreement_cos: float = 0.5
     alignment: RenderingAlignmentParameters = field(default_factory=_default_alignment)
 
 
@@ -141,6 +152,9 @@ class FrameResult:
     new_block_count: int = 0       # blocks activated for this frame
     active_block_count: int = 0    # blocks in the volume after integration
     seconds: float = 0.0
+    rigid_correspondence_count: int = 0   # rigid alignment: correspondences and RMSE of its last iteration (0 when it did not run)
+    rigid_inlier_rmse: float = 0.0
+    extrinsics: Optional[np.ndarray] = None   # a copy of the world -> camera matrix this frame was tracked and fused with
 
 
 def remap_edges_to_node_order(edges, order) -> np.ndarray:
@@ -325,8 +339,18 @@ class FusionPipeline:
             canonical = self.canonical_mesh
             points = image_proc.backproject_depth_ushort(depth, self.fx, self.fy, self.cx, self.cy, p.depth_scale)
             res.canonical_vertex_count, res.canonical_triangle_count = canonical.vertex_positions.shape[0], canonical.triangle_indices.shape[0]
+            if p.rigid_alignment and self.warped_mesh is not None and self.warped_mesh.triangle_indices.shape[0] > 0:
+                # the camera's motion since the previous frame, before the non-rigid fit (pipeline.py:338-354): the warped
+                # surface as of the previous frame (world coordinates) against the live points
+                rigid = align_rigid_point_to_plane(
+                    self.warped_mesh.vertex_positions, self.warped_mesh.vertex_normals, points, self.K,
+                    initial_transformation=self.extrinsics, iteration_counts=p.rigid_alignment_iteration_counts,
+                    distance_threshold=p.rigid_alignment_distance_threshold, normal_agreement_cos=p.rigid_alignment_normal_agreement_cos)
+                if rigid.status == 0:
+                    self.extrinsics = rigid.transformation
+                res.rigid_correspondence_count, res.rigid_inlier_rmse = rigid.correspondence_count, rigid.inlier_rmse
             if res.canonical_triangle_count > 0:
-                self.optimizer.optimize_graph(self.active_graph, canonical, points)
+                self.optimizer.optimize_graph(self.active_graph, canonical, points, extrinsics=self.extrinsics)
                 res.tracked = True
             # fuse: blocks the warped surface's truncation band touches, then non-rigid integration (:371-417)
             blocks = self.volume.find_blocks_intersecting_truncation_region(depth, self.active_graph, self.K, self.extrinsics,
@@ -340,6 +364,7 @@ class FusionPipeline:
         self.canonical_mesh = self.extract_canonical_mesh()
         self.warped_mesh = self.active_graph.warp_mesh(self.canonical_mesh) if self.canonical_mesh.triangle_indices.shape[0] else None
         res.active_block_count = self.volume.get_block_count()
+        res.extrinsics = np.array(self.extrinsics, np.float64)
         torch.cuda.synchronize(self.device)
         res.seconds = time.perf_counter() - t0
         self.results.append(res)

@@ -11,6 +11,7 @@ import torch
 from .. import _native as N
 from ._tensors import to_device, to_host_f64
 from .geometry import HierarchicalGraphWarpField, TriangleMesh
+from .rigid_alignment import DEGENERATE, RigidAlignmentResult, align_rigid_point_to_plane  # noqa: F401
 
 # nnrt_fitter_iterate_timed stage order (include/nnrt_mi355x.h, NNRT_TIMED_STAGES)
 TIMED_STAGES = ("warp", "raster", "pixel_jacobians", "node_reduce", "arap", "solve")

@@ -365,6 +365,30 @@ nnrt_status nnrt_compute_vertex_normals(const float* d_vertices, int64_t vertex_
  * kernel NormalsOperationsImpl.h:170-214): organized [H*W,3] points -> [H*W,3] normals facing the camera, 0 on the border */
 nnrt_status nnrt_compute_ordered_point_cloud_normals(const float* d_points, int64_t point_count, int32_t height, int32_t width, float* d_out,
                                                      void* stream);
+/* Rigid frame-to-model alignment (the rigid step of the reference loop, apps/fusion/pipeline.py:338-354, an Open3D call
+ * there): dense projective point-to-plane Gauss-Newton of model vertices d_points / d_normals [vertex_count,3] against an
+ * organized live point image d_target_points [height,width,3] with normals d_target_normals [height,width,3] (camera
+ * frame; a pixel with a non-finite entry, z <= 0 or a zero normal is no target). h_T_init float64[16] row-major maps
+ * model to live-camera coordinates (rows 0..2 are read; they must be finite). Per iteration and vertex, in float:
+ * q = R p + t, m = R n; dropped unless q is finite with q.z > 0 and pixel (floor(fx q.x / q.z + cx + 0.5),
+ * floor(fy q.y / q.z + cy + 0.5)) lies in the image and holds a target (d, g); dropped if |q - d|^2 >
+ * distance_threshold^2, unless |m . g| >= normal_agreement_cos (a value <= 0 disables this test), if cull_back_faces
+ * and m . q >= 0, or if a term overflowed float. Residual r = g . (q - d), Jacobian row [q x g, g] (left perturbation
+ * about the camera origin). The 6 x 6 normal equations are summed in float64 in an order fixed by vertex_count alone
+ * (bit-reproducible), solved by float64 Cholesky on the device, and T <- exp(xi^) T. The `iterations` (>= 1) steps are
+ * enqueued back to back on `stream`; pose, log and status are read once at the end (one stream synchronization).
+ * h_log [iterations,2] float64 receives (correspondence count, sum r^2) as found at the start of each iteration;
+ * log_row_capacity is the number of rows h_log has room for and must be >= iterations. *h_status: 0, or
+ * NNRT_RIGID_ALIGN_DEGENERATE when some iteration found fewer than minimum_correspondence_count correspondences, a
+ * Cholesky pivot <= 1e-12 * the largest diagonal entry, or a non-finite update: that iteration left T as it was (never a
+ * NaN, never an error). vertex_count == 0 is legal: DEGENERATE, h_T_out = h_T_init, a zero log. h_T_out float64[16]. */
+#define NNRT_RIGID_ALIGN_DEGENERATE 1
+nnrt_status nnrt_rigid_align_point_to_plane(const float* d_points, const float* d_normals, int64_t vertex_count,
+                                            const float* d_target_points, const float* d_target_normals, int32_t height, int32_t width,
+                                            float fx, float fy, float cx, float cy, const double* h_T_init, int32_t iterations,
+                                            float distance_threshold, float normal_agreement_cos, int32_t cull_back_faces,
+                                            int32_t minimum_correspondence_count, double* h_T_out, double* h_log,
+                                            int32_t log_row_capacity, int32_t* h_status, void* stream);
 /* nnrt.core.matmul3d(array_of_matrices_a, array_of_matrices_b) (cpp/pybind/core/core.cpp:32 -> cpp/core/linalg/Matmul3D.cpp:25-83):
  * d_c [batch, m, n] = d_a [batch, m, k] x d_b [batch, k, n] per batch entry, float32 row-major (n = 1: array of vectors). */
 nnrt_status nnrt_matmul3d(const float* d_a, const float* d_b, int64_t batch, int32_t m, int32_t k, int32_t n, float* d_c, void* stream);
