@@ -123,6 +123,9 @@ _SIGNATURES = {
     "nnrt_median_grid_subsample_3d_points": (c_int32, [c_void_p, c_int64, c_float, c_void_p, c_void_p, c_void_p]),
     "nnrt_get_vertex_erosion_mask": (c_int32, [c_int64, c_void_p, c_int64, c_int32, c_int32, c_void_p, c_void_p]),
     "nnrt_sample_nodes": (c_int32, [c_void_p, c_int64, c_void_p, c_void_p, c_float, c_void_p, c_int64, c_void_p, c_void_p, c_void_p]),
+    "nnrt_compute_vertex_support": (c_int32, [c_void_p, c_int64, c_void_p, c_int32, c_float, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "nnrt_blend_node_transforms": (c_int32, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_float, c_void_p, c_void_p,
+                                             c_void_p, c_void_p, c_void_p]),
     "nnrt_compute_mesh_from_depth": (c_int32, [c_void_p, c_int32, c_int32, c_float, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_void_p,
                                                c_void_p, c_void_p]),
     "nnrt_compute_edges_shortest_path": (c_int32, [c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_int32, c_int32, c_float, c_int32,
@@ -162,6 +165,7 @@ _SIGNATURES = {
     "nnrt_voxel_grid_integrate_non_rigid": (c_int32, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p,
                                                       c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_float, c_float,
                                                       c_void_p, c_void_p]),
+    "nnrt_voxel_grid_set_non_rigid_surface_growth": (c_int32, [c_void_p, c_int32]),
     "nnrt_voxel_grid_extract_voxel_values_and_coordinates": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p]),
     "nnrt_voxel_grid_extract_voxel_values_at": (c_int32, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p]),
     "nnrt_voxel_grid_copy_result_rows": (c_int32, [c_void_p, c_void_p, c_void_p]),

@@ -1917,6 +1917,36 @@ nnrt_status nnrt_sample_nodes(const float* d_points, int64_t point_count, const 
 	                           static_cast<hipStream_t>(stream));
 }
 
+nnrt_status nnrt_compute_vertex_support(const float* d_points, int64_t point_count, const float* d_nodes, int32_t node_count, float node_coverage,
+                                        const float* d_node_coverage_weights, float* d_out_support_ratio, int32_t* d_out_nearest_node,
+                                        void* stream) {
+	NNRT_CHECK_ARG(point_count >= 0 && point_count < (int64_t(1) << 31) / 3, "point count out of range");
+	NNRT_CHECK_ARG(node_count >= 0, "negative node count");
+	NNRT_CHECK_ARG(point_count == 0 || (d_points && d_out_support_ratio && d_out_nearest_node), "null pointer");
+	NNRT_CHECK_ARG(point_count == 0 || node_count == 0 || d_nodes, "null nodes");
+	NNRT_CHECK_ARG(d_node_coverage_weights || (node_coverage > 0.f && std::isfinite(node_coverage)), "node_coverage must be positive and finite");
+	return launch_vertex_support(d_points, point_count, d_nodes, node_count, node_coverage, d_node_coverage_weights, d_out_support_ratio,
+	                             d_out_nearest_node, static_cast<hipStream_t>(stream));
+}
+
+nnrt_status nnrt_blend_node_transforms(const float* d_points, int64_t point_count, const float* d_nodes, const float* d_node_rotations,
+                                       const float* d_node_translations, int32_t node_count, int32_t anchor_count, float node_coverage,
+                                       float* d_out_rotations, float* d_out_translations, uint8_t* d_out_fallback, int64_t* h_out_fallback_count,
+                                       void* stream) {
+	NNRT_CHECK_ARG(anchor_count >= 1 && anchor_count <= MAX_ANCHORS, "anchor_count must be in [1, 8]");
+	NNRT_CHECK_ARG(point_count >= 0 && point_count < (int64_t(1) << 31) / 9, "point count out of range");
+	NNRT_CHECK_ARG(node_count >= 0, "negative node count");
+	NNRT_CHECK_ARG(point_count == 0 || node_count >= 1, "no node to blend from");
+	NNRT_CHECK_ARG(point_count == 0 || (d_points && d_nodes && d_node_rotations && d_node_translations && d_out_rotations && d_out_translations &&
+	                                    d_out_fallback),
+	               "null pointer");
+	NNRT_CHECK_ARG(node_coverage > 0.f && std::isfinite(node_coverage) && std::isnormal(node_coverage * node_coverage),
+	               "node_coverage must be positive and finite, with a finite normal square");
+	return launch_blend_node_transforms(d_points, point_count, d_nodes, d_node_rotations, d_node_translations, node_count, anchor_count,
+	                                    node_coverage, d_out_rotations, d_out_translations, d_out_fallback, h_out_fallback_count,
+	                                    static_cast<hipStream_t>(stream));
+}
+
 nnrt_status nnrt_compute_mesh_from_depth(const float* d_point_image, int32_t height, int32_t width, float max_triangle_edge_distance,
                                          float* d_out_vertices, int32_t* d_out_vertex_pixels, int64_t vertex_capacity, int32_t* d_out_faces,
                                          int64_t face_capacity, int64_t* h_out_vertex_count, int64_t* h_out_face_count, void* stream) {

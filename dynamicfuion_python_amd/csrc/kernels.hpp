@@ -124,6 +124,13 @@ nnrt_status launch_vertex_erosion_mask(int64_t V, const int64_t* faces, int64_t 
                                        int* error_flag, hipStream_t s);
 nnrt_status launch_sample_nodes(const float* pts, int64_t V, const uint8_t* mask, const int64_t* order, float coverage, int64_t* out,
                                 int64_t* h_count, int32_t* h_rounds, hipStream_t s);
+// warp_extension.hip: nearest node and support ratio of every point; the warp's own motion at new node positions
+// (arguments checked by the caller). launch_blend_node_transforms synchronizes `s` iff h_fallback_count is given.
+nnrt_status launch_vertex_support(const float* points, int64_t V, const float* nodes, int N, float coverage, const float* node_weights,
+                                  float* ratio, int32_t* nearest, hipStream_t s);
+nnrt_status launch_blend_node_transforms(const float* points, int64_t M, const float* nodes, const float* rotations, const float* translations,
+                                         int N, int K, float coverage, float* out_rotations, float* out_translations, uint8_t* fallback,
+                                         int64_t* h_fallback_count, hipStream_t s);
 // depth_graph.hip: the motion graph from a depth image (cpp/cpu/image_proc.cpp:341-482, cpp/cpu/graph_proc.cpp:181-338, :540-636)
 nnrt_status launch_mesh_from_depth(const float* pts, int H, int W, float limit, float* vertices, int32_t* pixels, int64_t vertex_cap, int32_t* faces,
                                    int64_t face_cap, int64_t* h_vertex_count, int64_t* h_face_count, hipStream_t s);

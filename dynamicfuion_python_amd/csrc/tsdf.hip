@@ -485,7 +485,7 @@ constexpr int NR_CAND = 2048;
 template <int KT>
 __global__ __launch_bounds__(NR_BLOCK) void k_integrate_non_rigid(GridView g, int64_t nb, WarpFieldView wf, ImageView im, const float* __restrict__ normals,
                                                                   Xform depth_x, Xform color_x, float sdf_trunc, float color_multiplier,
-                                                                  float range, uint64_t* __restrict__ cos_key) {
+                                                                  float range, uint64_t* __restrict__ cos_key, int grow_surface) {
 	__shared__ int s_cand[NR_CAND];
 	__shared__ int s_count;
 	__shared__ int s_wave_counts[NR_BLOCK / 64];
@@ -588,7 +588,9 @@ __global__ __launch_bounds__(NR_BLOCK) void k_integrate_non_rigid(GridView g, in
 		// linear index wins (the serial loop's last writer)
 		atomicMax(reinterpret_cast<unsigned long long*>(cos_key + pix),
 		          (static_cast<unsigned long long>(lin + 1) << 32) | __builtin_bit_cast(uint32_t, cosine));
-		if (psdf <= -sdf_trunc || cosine > 0.5f) continue;
+		// the reference skips cosine > 0.5, which with camera-facing normals is every surface seen head-on (T1);
+		// grow_surface keeps those and skips the grazing ones (and pixels without a normal: cosine 0) instead
+		if (psdf <= -sdf_trunc || (grow_surface ? !(cosine >= 0.5f) : cosine > 0.5f)) continue;
 		const float tsdf_n = (psdf < sdf_trunc ? psdf : sdf_trunc) / sdf_trunc;
 		const float weight = read_store(g.weight, g.weight_type, lin);
 		const float inv_wsum = 1.0f / (weight + 1);
@@ -606,6 +608,9 @@ __global__ __launch_bounds__(NR_BLOCK) void k_integrate_non_rigid(GridView g, in
 				}
 			}
 		}
+		// the reference never counts the observation (T2), so a voxel first seen here keeps weight 0 and never reaches
+		// the extracted mesh; grow_surface counts it as k_integrate_rigid does
+		if (grow_surface) write_store(g.weight, g.weight_type, lin, weight + 1);
 	}
 }
 
@@ -1027,6 +1032,7 @@ struct nnrt_voxel_grid {
 	int64_t capacity = 0, active = 0;
 	int weight_type = ST_F32, color_type = ST_NONE;
 	uint64_t table_size = 0;
+	bool grow_surface = false;   // nnrt_voxel_grid_set_non_rigid_surface_growth
 	DevBuf<float> tsdf;
 	DevBuf<uint8_t> weight, color;
 	DevBuf<int32_t> keys;
@@ -1397,6 +1403,12 @@ nnrt_status nnrt_voxel_grid_integrate(nnrt_voxel_grid* vg, const int32_t* d_bloc
 	return NNRT_OK;
 }
 
+nnrt_status nnrt_voxel_grid_set_non_rigid_surface_growth(nnrt_voxel_grid* vg, int32_t enabled) {
+	NNRT_CHECK_ARG(vg, "null voxel grid");
+	vg->grow_surface = enabled != 0;
+	return NNRT_OK;
+}
+
 nnrt_status nnrt_voxel_grid_integrate_non_rigid(nnrt_voxel_grid* vg, const int32_t* d_block_coords, int64_t count, const nnrt_warp_field* wf,
                                                 const void* d_depth, int32_t depth_dtype, int32_t height, int32_t width, const void* d_color,
                                                 int32_t color_height, int32_t color_width, const float* d_depth_normals, const double* h_depth_K,
@@ -1433,7 +1445,8 @@ nnrt_status nnrt_voxel_grid_integrate_non_rigid(nnrt_voxel_grid* vg, const int32
 #define NNRT_NR_CASE(KK)                                                                                                          \
 	case KK:                                                                                                                      \
 		k_integrate_non_rigid<KK><<<static_cast<unsigned>(vg->active), NR_BLOCK, 0, s>>>(gv, vg->active, wv, im, d_depth_normals, xd, xc, \
-		                                                                               trunc, cm, range, vg->s_packed.ptr);        \
+		                                                                               trunc, cm, range, vg->s_packed.ptr,         \
+		                                                                               vg->grow_surface ? 1 : 0);                  \
 		break;
 		NNRT_NR_CASE(1) NNRT_NR_CASE(2) NNRT_NR_CASE(3) NNRT_NR_CASE(4) NNRT_NR_CASE(5) NNRT_NR_CASE(6) NNRT_NR_CASE(7) NNRT_NR_CASE(8)
 #undef NNRT_NR_CASE

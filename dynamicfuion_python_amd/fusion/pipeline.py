@@ -63,7 +63,7 @@ from ..data.frame import FrameSequenceDataset
 from ..nnrt import geometry as G
 from ..nnrt import image_proc
 from ..nnrt.alignment import NDC_CONSISTENT, align_rigid_point_to_plane
-from ..warp_field.graph_warp_field import build_graph_nodes_from_depth_image, sample_graph_nodes_from_mesh
+from ..warp_field.graph_warp_field import build_graph_nodes_from_depth_image, extend_warp_field, sample_graph_nodes_from_mesh
 
 
 class TrackingMethod(enum.Enum):
@@ -140,6 +140,12 @@ class FusionParameters:
     rigid_alignment_iteration_counts: tuple = (6, 3, 1)   # coarse to fine
     rigid_alignment_distance_threshold: float = 0.07
     rigid_alignment_normal_agreement_cos: float = 0.5
+    # grow the motion graph over surface fused beyond its nodes' support, after every tracked frame (extend_warp_field,
+    # DESIGN §18), and let non-rigid integration take newly seen surface into the model
+    # (NonRigidSurfaceVoxelBlockGrid.set_non_rigid_surface_growth); off: the nodes are the first frame's for the whole run
+    warp_field_extension: bool = False
+    warp_field_extension_support_ratio: float = 1.0
+    warp_field_extension_minimum_new_node_count: int = 1
     alignment: RenderingAlignmentParameters = field(default_factory=_default_alignment)
 
 
@@ -155,6 +161,8 @@ class FrameResult:
     rigid_correspondence_count: int = 0   # rigid alignment: correspondences and RMSE of its last iteration (0 when it did not run)
     rigid_inlier_rmse: float = 0.0
     extrinsics: Optional[np.ndarray] = None   # a copy of the world -> camera matrix this frame was tracked and fused with
+    node_count: int = 0       # nodes of the motion graph after this frame
+    new_node_count: int = 0   # of them, added by this frame's warp field extension
 
 
 def remap_edges_to_node_order(edges, order) -> np.ndarray:
@@ -186,6 +194,9 @@ class FusionPipeline:
                 GraphGenerationMode.FIRST_FRAME_LOADED_GRAPH, GraphGenerationMode.FIRST_FRAME_DEPTH_IMAGE):
             raise NotImplementedError(f"AnchorComputationMode.SHORTEST_PATH needs a graph with edge rows; graph generation mode "
                                       f"{p.graph_generation_mode.name} has none (use FIRST_FRAME_LOADED_GRAPH or FIRST_FRAME_DEPTH_IMAGE)")
+        if p.warp_field_extension and p.anchor_computation_mode == AnchorComputationMode.SHORTEST_PATH:
+            raise NotImplementedError("warp_field_extension adds nodes without edge rows, which AnchorComputationMode.SHORTEST_PATH "
+                                      "anchors along; use AnchorComputationMode.EUCLIDEAN")
         if p.graph_generation_mode == GraphGenerationMode.PROVIDED_NODES and nodes is None:
             raise ValueError("GraphGenerationMode.PROVIDED_NODES needs nodes=")
         self.sequence = sequence if sequence._loaded else sequence.load()
@@ -199,6 +210,9 @@ class FusionPipeline:
         self.volume = G.NonRigidSurfaceVoxelBlockGrid(["tsdf", "weight", "color"], ["float32", "uint16", "uint16"], [1, 1, 3],
                                                       voxel_size=p.voxel_size, block_resolution=p.block_resolution,
                                                       block_count=p.initial_block_count, device=self.device)
+        if p.warp_field_extension:
+            # new nodes are sampled on fused surface: the model has to be able to take in surface it first sees while tracking
+            self.volume.set_non_rigid_surface_growth(True)
         self.truncation_voxel_multiplier = p.sdf_truncation_distance / p.voxel_size
         self._provided_nodes = nodes
         self.active_graph: Optional[G.HierarchicalGraphWarpField] = None
@@ -211,7 +225,8 @@ class FusionPipeline:
         self.depth_image_graph = None
         self.geodesic_edges = None
         self.graph_clusters = None
-        # make_warp_field: the index, in the nodes it was given, of each node of the warp field it returned
+        # make_warp_field: the index, in the nodes it was given, of each node of the warp field it returned; with
+        # warp_field_extension, the index in [the first frame's nodes; the nodes added since, in the order they were added]
         self.node_order = None
         # SHORTEST_PATH: the graph's edge rows in the warp field's virtual node order, as handed to the optimizer
         self.anchor_graph_edges = None
@@ -313,6 +328,20 @@ class FusionPipeline:
         self.node_order = order
         return wf
 
+    def _extend_graph(self) -> int:
+        """New nodes over the canonical surface the graph does not support yet, moving with the current warp; the number
+        added. The optimizer needs no reset: the fitter rebuilds its per-graph state for a warp field it has not prepared
+        (it recognises fields by a unique id), and TSDF integration and warp_mesh read the field they are handed."""
+        p = self.parameters
+        previous_order = self.node_order
+        graph, order, added = extend_warp_field(self.active_graph, self.canonical_mesh, lambda nodes: (self.make_warp_field(nodes), self.node_order),
+                                                p.warp_field_extension_support_ratio, p.warp_field_extension_minimum_new_node_count)
+        if graph is self.active_graph:
+            return 0
+        self.active_graph = graph
+        self.node_order = np.concatenate([previous_order, np.arange(len(previous_order), len(order))])[order]
+        return int(added.shape[0])
+
     def extract_canonical_mesh(self):
         mesh = self.volume.extract_triangle_mesh(float(self.mesh_extraction_threshold()), -1)
         return mesh
@@ -362,6 +391,9 @@ class FusionPipeline:
             res.new_block_count = int(blocks.shape[0])
         # canonical + warped mesh of the volume as fused so far (pipeline.py:419-420; the reference skips the first frame)
         self.canonical_mesh = self.extract_canonical_mesh()
+        if p.warp_field_extension and res.tracked and self.canonical_mesh.triangle_indices.shape[0]:
+            res.new_node_count = self._extend_graph()
+        res.node_count = self.active_graph.node_count
         self.warped_mesh = self.active_graph.warp_mesh(self.canonical_mesh) if self.canonical_mesh.triangle_indices.shape[0] else None
         res.active_block_count = self.volume.get_block_count()
         res.extrinsics = np.array(self.extrinsics, np.float64)

@@ -305,6 +305,51 @@ def compute_anchors_and_weights_shortest_path_variable_node_weight(points, nodes
     return _anchors_shortest_path(points, nodes, edges, anchor_count, 0.0, node_coverage_weights)
 
 
+def compute_vertex_support(points, nodes, node_coverage=0.05, node_coverage_weights=None):
+    """No counterpart in the reference (csrc/warp_extension.hip; DESIGN "Extending the warp field"): (support_ratio [V]
+    float32, nearest_node [V] int32), device tensors. support_ratio is d_min / node_coverage over the nodes, nearest_node
+    the node at d_min (the lowest index on ties; slot 0 of compute_anchors_and_weights_euclidean_fixed_node_weight). With
+    node_coverage_weights [N] (squared per-node coverages, as HierarchicalGraphWarpField.get_node_coverage_weights holds
+    them) the minimum is taken over d / c_i instead. A point with a non-finite coordinate gets ratio 0 and index -1; no
+    nodes give ratio +inf and index -1."""
+    dev = _dev()
+    p = to_device(points, torch.float32, dev).reshape(-1, 3)
+    n = to_device(nodes, torch.float32, dev).reshape(-1, 3)
+    nw = None
+    if node_coverage_weights is not None:
+        nw = to_device(node_coverage_weights, torch.float32, dev).reshape(-1)
+        if nw.shape[0] != n.shape[0]:
+            raise RuntimeError(f"`node_coverage_weights` needs {n.shape[0]} entries, one per node. Got {nw.shape[0]}.")
+    ratio = torch.empty(p.shape[0], dtype=torch.float32, device=dev)
+    nearest = torch.empty(p.shape[0], dtype=torch.int32, device=dev)
+    N.check(N.lib().nnrt_compute_vertex_support(N.ptr(p), p.shape[0], N.ptr(n), n.shape[0], float(node_coverage), N.ptr(nw), N.ptr(ratio),
+                                                N.ptr(nearest), N.stream_ptr()))
+    return ratio, nearest
+
+
+def blend_node_transformations(points, nodes, node_rotations, node_translations, anchor_count=4, node_coverage=0.05):
+    """No counterpart in the reference (csrc/warp_extension.hip): the motion of the field (nodes [N,3], node_rotations
+    [N,3,3], node_translations [N,3]) at each query point, blended over its min(anchor_count, N) nearest nodes with
+    normalised weights exp(-d^2 / (2 node_coverage^2)), no distance threshold: (rotations [M,3,3], translations [M,3],
+    fallback_count). translations is the warped point minus the point; rotations the rotation nearest to the weighted
+    rotation average, or the nearest node's rotation where that average is singular (rotations about 180 degrees apart),
+    which fallback_count counts."""
+    dev = _dev()
+    p = to_device(points, torch.float32, dev).reshape(-1, 3)
+    n = to_device(nodes, torch.float32, dev).reshape(-1, 3)
+    R = to_device(node_rotations, torch.float32, dev).reshape(-1, 3, 3)
+    t = to_device(node_translations, torch.float32, dev).reshape(-1, 3)
+    if R.shape[0] != n.shape[0] or t.shape[0] != n.shape[0]:
+        raise RuntimeError(f"{n.shape[0]} nodes need as many rotations and translations. Got {R.shape[0]} and {t.shape[0]}.")
+    out_R = torch.empty((p.shape[0], 3, 3), dtype=torch.float32, device=dev)
+    out_t = torch.empty((p.shape[0], 3), dtype=torch.float32, device=dev)
+    fallback = torch.empty(p.shape[0], dtype=torch.uint8, device=dev)
+    count = np.zeros(1, np.int64)
+    N.check(N.lib().nnrt_blend_node_transforms(N.ptr(p), p.shape[0], N.ptr(n), N.ptr(R), N.ptr(t), n.shape[0], int(anchor_count),
+                                               float(node_coverage), N.ptr(out_R), N.ptr(out_t), N.ptr(fallback), N.ptr(count), N.stream_ptr()))
+    return out_R, out_t, int(count[0])
+
+
 def _check_min_valid(minimum_valid_anchor_count, anchor_count):
     if minimum_valid_anchor_count > anchor_count:
         raise RuntimeError(f"minimum_valid_anchor_count (now, {minimum_valid_anchor_count}) has to be smaller than or equal to anchor_count, "
@@ -548,6 +593,8 @@ functional = types.SimpleNamespace(
     median_grid_subsample_3d_points=median_grid_subsample_3d_points,
     unproject_raster_depth_without_filtering=unproject_raster_depth_without_filtering,
     compute_point_to_plane_distances=compute_point_to_plane_distances,
+    compute_vertex_support=compute_vertex_support,
+    blend_node_transformations=blend_node_transformations,
 )
 
 

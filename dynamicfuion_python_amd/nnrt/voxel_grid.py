@@ -194,6 +194,12 @@ class VoxelBlockGrid:
 class NonRigidSurfaceVoxelBlockGrid(VoxelBlockGrid):
     """NonRigidSurfaceVoxelBlockGrid (cpp/geometry/NonRigidSurfaceVoxelBlockGrid.h:30-65)."""
 
+    def set_non_rigid_surface_growth(self, enabled: bool):
+        """No counterpart in the reference. On: integrate_non_rigid keeps surface seen head-on (it skips cosine < 0.5
+        instead of the reference's cosine > 0.5) and counts each observation in the voxel weight (T2), so
+        that surface first seen in a non-rigid step reaches the extracted mesh. Off (the default): the reference's."""
+        N.check(N.lib().nnrt_voxel_grid_set_non_rigid_surface_growth(self._h, int(bool(enabled))))
+
     def integrate_non_rigid(self, block_coords, warp_field, depth, color, depth_normals, depth_intrinsics, color_intrinsics, extrinsics,
                             depth_scale: float, depth_max: float, truncation_voxel_multiplier: float) -> torch.Tensor:
         """IntegrateNonRigid (NonRigidSurfaceVoxelBlockGrid.cpp:33-66) -> cos(voxel ray, normal) per pixel [H,W]."""

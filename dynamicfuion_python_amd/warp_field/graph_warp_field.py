@@ -45,6 +45,40 @@ def build_deformation_graph_from_mesh(mesh: G.TriangleMesh, node_coverage: float
                                         minimum_valid_anchor_count=minimum_valid_anchor_count, layer_count=layer_count, device=device)
 
 
+def extend_warp_field(warp_field: G.HierarchicalGraphWarpField, canonical_mesh, make_warp_field, support_ratio_threshold: float = 1.0,
+                      minimum_new_node_count: int = 1):
+    """Extend the warp field over canonical surface its nodes do not support (DynamicFusion section 3.4; the reference has
+    no counterpart): (warp_field, order, new_node_positions).
+
+    The vertices of `canonical_mesh` (a TriangleMesh or a [V, 3] array) farther than support_ratio_threshold * node_coverage
+    from every node are the candidates; new nodes are sampled among them greedily in ascending vertex index at spacing
+    node_coverage (nnrt.graph_proc.sample_node_indices). Fewer than minimum_new_node_count of them (or none): the field is
+    returned as it is, with the identity order and an empty (0, 3) tensor. Otherwise each new node takes the current field's
+    own motion at its position (functional.blend_node_transformations over the field's anchor_count nearest nodes, original
+    node order), `make_warp_field([old nodes; new nodes])` builds the new field -- it returns the field, or (field, order)
+    with order[v] = the index in the nodes it was given of the field's node v when it re-orders them
+    (FusionPipeline.make_warp_field, quirk A5) -- and the field's motion is set to [R_old; R_new][order], [t_old; t_new][order]:
+    old nodes keep their motion exactly. new_node_positions (M, 3) is a device tensor in sampling order."""
+    vertices = getattr(canonical_mesh, "vertex_positions", canonical_mesh)
+    nodes = warp_field.get_node_positions()
+    coverage = warp_field.node_coverage
+    support_ratio, _ = G.compute_vertex_support(vertices, nodes, coverage)
+    vertices = torch.as_tensor(vertices, device=support_ratio.device).to(torch.float32).reshape(-1, 3)
+    indices, _ = nnrt.graph_proc.sample_node_indices(vertices, support_ratio > support_ratio_threshold, None, coverage)
+    new_positions = vertices[indices]
+    if indices.shape[0] < max(int(minimum_new_node_count), 1):
+        return warp_field, np.arange(warp_field.node_count), new_positions[:0]
+    rotations, translations = warp_field.get_node_rotations(), warp_field.get_node_translations()
+    new_rotations, new_translations, _ = G.blend_node_transformations(new_positions, nodes, rotations, translations, warp_field.anchor_count,
+                                                                      coverage)
+    made = make_warp_field(np.concatenate([nodes, new_positions.cpu().numpy()]))
+    extended, order = made if isinstance(made, tuple) else (made, np.arange(warp_field.node_count + indices.shape[0]))
+    order = np.asarray(order, np.int64)
+    extended.set_node_rotations(np.concatenate([rotations, new_rotations.cpu().numpy()])[order])
+    extended.set_node_translations(np.concatenate([translations, new_translations.cpu().numpy()])[order])
+    return extended, order, new_positions
+
+
 @dataclass
 class DepthImageGraph:
     """What build_graph_nodes_from_depth_image computes; device tensors, nodes in sampling order with the removed ones

@@ -420,6 +420,31 @@ nnrt_status nnrt_get_vertex_erosion_mask(int64_t vertex_count, const int64_t* d_
  * O(point_count). Synchronizes `stream`. */
 nnrt_status nnrt_sample_nodes(const float* d_points, int64_t point_count, const uint8_t* d_mask, const int64_t* d_order, float node_coverage,
                               int64_t* d_out_indices, int64_t out_capacity, int64_t* h_out_count, int32_t* h_out_rounds, void* stream);
+/* Extending the warp field over newly fused surface (DynamicFusion section 3.4; no counterpart in the reference).
+ * nnrt_compute_vertex_support: for each of point_count points the nearest of node_count nodes (d_out_nearest_node int32,
+ * the lowest index on ties) and the support ratio d_min / c (d_out_support_ratio float32), with the squared distance
+ * ((dx*dx + dy*dy) + dz*dz), d = node - point, in unfused f32 as nnrt_compute_anchors_and_weights forms it.
+ * d_node_coverage_weights NULL: c = node_coverage, the ratio is sqrtf(min sq) / node_coverage. Otherwise [node_count]
+ * squared per-node coverages w_j > 0 (nnrt_warp_field_get_node_coverage_weights; node_coverage is ignored): the minimum
+ * is taken over sq * RN(1 / w_j) and the ratio is its sqrtf. A point with a non-finite coordinate gets ratio 0 and
+ * index -1; node_count == 0 gives ratio +inf and index -1. Asynchronous on `stream`.
+ * nnrt_blend_node_transforms: the motion of the field (d_nodes [node_count, 3], d_node_rotations [node_count, 3, 3],
+ * d_node_translations [node_count, 3]) at each of point_count query points p: over the min(anchor_count, node_count)
+ * nearest nodes in ascending (distance, index) order, without a distance threshold, with weights
+ * exp(-d^2 / (2 node_coverage^2)) normalised and f32 sums in that order: d_out_translations = sum_k w_k ((R_k (p - g_k) -
+ * (p - g_k)) + t_k), i.e. the warped point minus p; d_out_rotations = the rotation nearest to sum_k w_k R_k (its
+ * orthogonal polar factor, det = +1, by a fixed number of Newton steps). Where that sum's determinant is at most 1e-3
+ * (rotations about 180 degrees apart) or the result misses orthogonality by more than 1e-5, the rotation is the nearest
+ * node's and d_out_fallback [point_count] uint8 is 1, else 0. h_out_fallback_count (nullable) receives the number of
+ * such points; when it is given the call synchronizes `stream`. anchor_count must be in [1, 8], node_count >= 1 unless
+ * point_count == 0. */
+nnrt_status nnrt_compute_vertex_support(const float* d_points, int64_t point_count, const float* d_nodes, int32_t node_count, float node_coverage,
+                                        const float* d_node_coverage_weights, float* d_out_support_ratio, int32_t* d_out_nearest_node,
+                                        void* stream);
+nnrt_status nnrt_blend_node_transforms(const float* d_points, int64_t point_count, const float* d_nodes, const float* d_node_rotations,
+                                       const float* d_node_translations, int32_t node_count, int32_t anchor_count, float node_coverage,
+                                       float* d_out_rotations, float* d_out_translations, uint8_t* d_out_fallback, int64_t* h_out_fallback_count,
+                                       void* stream);
 /* nnrt.compute_mesh_from_depth(point_image, max_triangle_edge_distance) (nnrt_pybind.cpp:79-80 -> cpp/cpu/image_proc.cpp:341-482):
  * the pixel-connected mesh of d_point_image [height, width, 3] float32. The 2x2 pixel cell at (x, y) emits triangle
  * (00, 01, 10) if all three points have z > 0 (NaN is invalid) and all three edges have
@@ -581,6 +606,12 @@ nnrt_status nnrt_voxel_grid_integrate_non_rigid(nnrt_voxel_grid* grid, const int
                                                 int32_t color_width, const float* d_depth_normals, const double* h_depth_K,
                                                 const double* h_color_K, const double* h_E, float depth_scale, float depth_max,
                                                 float trunc_voxel_multiplier, float* d_cos_out, void* stream);
+/* No counterpart in the reference. Off (the default), nnrt_voxel_grid_integrate_non_rigid is the reference's: it skips
+ * a voxel whose view ray and (camera-facing) pixel normal have cosine > 0.5 and never increments the voxel weight, so
+ * surface first seen in a non-rigid step never reaches the extracted mesh. enabled != 0: later calls on this grid skip
+ * cosine < 0.5 instead (grazing views, and pixels without a normal) and add 1 to the weight of every voxel they
+ * update, as nnrt_voxel_grid_integrate does. Host state only. */
+nnrt_status nnrt_voxel_grid_set_non_rigid_surface_growth(nnrt_voxel_grid* grid, int32_t enabled);
 /* ExtractVoxelValuesAndCoordinates (NonRigidSurfaceVoxelBlockGrid.cpp:168-184): d_out [active * res^3, C], rows
  * (x, y, z, tsdf, weight[, r, g, b]), C = 5 or 8 (h_channels) */
 nnrt_status nnrt_voxel_grid_extract_voxel_values_and_coordinates(const nnrt_voxel_grid* grid, float* d_out, int32_t* h_channels,
