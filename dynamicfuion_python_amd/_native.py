@@ -42,6 +42,7 @@ _SIGNATURES = {
     "nnrt_last_error": (ctypes.c_char_p, []),
     "nnrt_runtime_version": (c_int32, []),
     "nnrt_device_count": (c_int32, []),
+    "nnrt_device_bytes_in_use": (c_int64, []),
     "nnrt_build_jacobian_fma": (c_int32, []),
     "nnrt_build_refine_floor": (c_float, []),
     "nnrt_warp_field_create": (c_int32, [c_void_p, c_int32, c_float, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p,

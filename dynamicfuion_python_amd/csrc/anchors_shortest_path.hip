@@ -207,17 +207,16 @@ nnrt_status launch_anchors_shortest_path(const float* points, int64_t V, const f
 nnrt_status check_anchor_edges(const int32_t* edges, int N, int D, hipStream_t stream) {
 	const int64_t count = static_cast<int64_t>(N) * D;
 	if (count == 0) return NNRT_OK;
-	int* flag = nullptr;
-	NNRT_HIP(hipMalloc(reinterpret_cast<void**>(&flag), sizeof(int)));
+	DeviceBuffer<int> flag;
+	if (nnrt_status st = flag.ensure(1)) return st;
 	int err = 0;
-	hipError_t e = hipMemsetAsync(flag, 0, sizeof(int), stream);
+	hipError_t e = hipMemsetAsync(flag.ptr, 0, sizeof(int), stream);
 	if (e == hipSuccess) {
-		k_check_anchor_edges<<<static_cast<unsigned>(ceil_div(count, 256)), 256, 0, stream>>>(edges, count, N, flag);
+		k_check_anchor_edges<<<static_cast<unsigned>(ceil_div(count, 256)), 256, 0, stream>>>(edges, count, N, flag.ptr);
 		e = hipGetLastError();
 	}
-	if (e == hipSuccess) e = hipMemcpyAsync(&err, flag, sizeof(int), hipMemcpyDeviceToHost, stream);
+	if (e == hipSuccess) e = hipMemcpyAsync(&err, flag.ptr, sizeof(int), hipMemcpyDeviceToHost, stream);
 	if (e == hipSuccess) e = hipStreamSynchronize(stream);
-	(void)hipFree(flag);
 	NNRT_HIP(e);
 	if (err) {
 		set_error("invalid argument: edge entry outside [-1, node_count) in the anchor graph");

@@ -342,6 +342,19 @@ __global__ __launch_bounds__(256) void k_stem_schur_rhs(int targets, int nc, Cor
 	}
 }
 
+StemEdgeCsr build_stem_edge_csr(const int32_t* edges, int E, int n0) {
+	StemEdgeCsr c;
+	c.offsets.assign(static_cast<size_t>(n0) + 1, 0);
+	c.list.resize(static_cast<size_t>(E));
+	for (int e = 0; e < E; e++)
+		if (edges[2 * e] < n0) c.offsets[edges[2 * e] + 1]++;
+	for (int i = 0; i < n0; i++) c.offsets[i + 1] += c.offsets[i];
+	std::vector<int> fill(c.offsets.begin(), c.offsets.end() - 1);
+	for (int e = 0; e < E; e++)
+		if (edges[2 * e] < n0) c.list[fill[edges[2 * e]]++] = e;
+	return c;
+}
+
 StemSchurLists build_stem_schur_lists(const int32_t* edges, int E, int n0, int N) {
 	StemSchurLists L;
 	const int nc = N - n0;

@@ -63,57 +63,6 @@ Camera pixel_camera(const double* K) {
 	return Camera{static_cast<float>(K[0]), static_cast<float>(K[4]), static_cast<float>(K[2]), static_cast<float>(K[5])};
 }
 
-// ---- device buffer helper ----
-template <typename T>
-struct DeviceBuffer {
-	T* ptr = nullptr;
-	size_t count = 0;
-	nnrt_status ensure(size_t n) {
-		if (n <= count && ptr) return NNRT_OK;
-		if (ptr) hipFree(ptr);
-		ptr = nullptr;
-		count = 0;
-		const size_t bytes = sizeof(T) * std::max<size_t>(n, 1);
-		hipError_t e = hipMalloc(reinterpret_cast<void**>(&ptr), bytes);
-		if (e != hipSuccess) {
-			set_error(std::string("hipMalloc failed: ") + hipGetErrorString(e));
-			ptr = nullptr;
-			return NNRT_ERROR_HIP;
-		}
-		count = std::max<size_t>(n, 1);
-		return NNRT_OK;
-	}
-	void release() {
-		if (ptr) hipFree(ptr);
-		ptr = nullptr;
-		count = 0;
-	}
-};
-
-template <typename T>
-nnrt_status upload(DeviceBuffer<T>& buf, const std::vector<T>& host) {
-	nnrt_status st = buf.ensure(host.size());
-	if (st) return st;
-	if (!host.empty() && hipMemcpy(buf.ptr, host.data(), sizeof(T) * host.size(), hipMemcpyHostToDevice) != hipSuccess) {
-		set_error("hipMemcpy failed");
-		return NNRT_ERROR_HIP;
-	}
-	return NNRT_OK;
-}
-
-struct DeviceGuard {
-	int prev = -1;
-	explicit DeviceGuard(int device) {
-		hipGetDevice(&prev);
-		if (device >= 0 && device != prev) hipSetDevice(device);
-	}
-	~DeviceGuard() {
-		int cur = -1;
-		hipGetDevice(&cur);
-		if (prev >= 0 && cur != prev) hipSetDevice(prev);
-	}
-};
-
 } // namespace nnrt
 
 using namespace nnrt;
@@ -186,6 +135,8 @@ int32_t nnrt_device_count(void) {
 	return n;
 }
 
+int64_t nnrt_device_bytes_in_use(void) { return g_device_bytes_in_use.load(std::memory_order_relaxed); }
+
 nnrt_status nnrt_warp_field_create(const float* h_nodes, int32_t node_count, float node_coverage, int32_t threshold_nodes_by_distance,
                                    int32_t anchor_count, int32_t minimum_valid_anchor_count, int32_t coverage_method, int32_t layer_count,
                                    int32_t max_vertex_degree, const float* h_layer_radii, int32_t device, nnrt_warp_field** out) {
@@ -249,12 +200,6 @@ nnrt_status nnrt_warp_field_create(const float* h_nodes, int32_t node_count, flo
 void nnrt_warp_field_destroy(nnrt_warp_field* wf) {
 	if (!wf) return;
 	DeviceGuard guard(wf->device);
-	wf->state.release();
-	wf->node_positions.release();
-	wf->node_weights.release();
-	wf->edges.release();
-	wf->edge_layers.release();
-	wf->radii.release();
 	delete wf;
 }
 
@@ -662,45 +607,10 @@ void nnrt_fitter_destroy(nnrt_fitter* ft) {
 	DeviceGuard guard(ft->device);
 	hipStreamSynchronize(ft->work);
 	ft->drop_graphs();
-	ft->acc.release();
-	ft->ref_points.release();
-	ft->tile_flags.release();
-	ft->tile_order.release();
-	ft->quad_scratch.release();
-	ft->quad_order.release();
-	ft->records.release();
-	for (auto* b : {&ft->mesh_p, &ft->mesh_n, &ft->weights, &ft->residuals, &ft->edge_jr, &ft->updates, &ft->gradient,
-	                &ft->hessian, &ft->wing, &ft->edge_residuals, &ft->a_diag, &ft->a_dinv, &ft->a_dinvb, &ft->a_rhs, &ft->a_x, &ft->a_res, &ft->a_dx})
-		b->release();
-	ft->faces4.release();
-	ft->anchors.release();
-	ft->anchors16.release();
-	ft->graph_edges.release();
-	ft->face_nodes.release();
-	ft->wpos.release();
-	ft->wnrm.release();
-	ft->jrows.release();
-	ft->mesh_p4.release();
-	ft->mesh_n4.release();
-	ft->keys.release();
-	ft->residual_mask.release();
-	ft->pixel_face.release();
-	ft->error_flag.release();
-	ft->a_offsets.release();
-	ft->a_list.release();
-	ft->a_tgt_off.release();
-	ft->a_rhs_off.release();
-	ft->a_rhs_edges.release();
-	ft->a_tgt_ab.release();
-	ft->a_pairs.release();
-	ft->a_inc_off.release();
-	ft->a_inc_list.release();
-	ft->a_inc_slot.release();
 	if (ft->ev_in) hipEventDestroy(ft->ev_in);
 	if (ft->ev_out) hipEventDestroy(ft->ev_out);
-
 	if (ft->work) hipStreamDestroy(ft->work);
-	delete ft;
+	delete ft;   // the members free their device memory: after the work stream has drained and the graph execs are gone
 }
 
 namespace {
@@ -817,23 +727,10 @@ nnrt_status prepare_frame(nnrt_fitter* ft, nnrt_warp_field* wf, const float* d_v
 		    (st = ft->a_dinvb.ensure(static_cast<size_t>(E) * 36)) ||
 		    (st = ft->edge_jr.ensure(2 * static_cast<size_t>(E) * EDGE_TERMS)) ||
 		    (st = ft->a_rhs.ensure(6 * static_cast<size_t>(N))) || (st = ft->a_x.ensure(6 * static_cast<size_t>(N))) ||
-		    (st = ft->a_res.ensure(6 * static_cast<size_t>(N))) || (st = ft->a_dx.ensure(6 * static_cast<size_t>(N))) ||
-		    (st = ft->a_offsets.ensure(n0 + 1)) || (st = ft->a_list.ensure(E)))
+		    (st = ft->a_res.ensure(6 * static_cast<size_t>(N))) || (st = ft->a_dx.ensure(6 * static_cast<size_t>(N))))
 			return st;
-		// CSR of stem edges by source node
-		std::vector<int> counts(n0 + 1, 0), list(E), fill;
-		for (int e = 0; e < E; e++) {
-			const int i = wf->h.edges[2 * e];
-			if (i < n0) counts[i + 1]++;
-		}
-		for (int i = 0; i < n0; i++) counts[i + 1] += counts[i];
-		fill.assign(counts.begin(), counts.end() - 1);
-		for (int e = 0; e < E; e++) {
-			const int i = wf->h.edges[2 * e];
-			if (i < n0) list[fill[i]++] = e;
-		}
-		NNRT_HIP(hipMemcpy(ft->a_offsets.ptr, counts.data(), sizeof(int) * (n0 + 1), hipMemcpyHostToDevice));
-		NNRT_HIP(hipMemcpy(ft->a_list.ptr, list.data(), sizeof(int) * E, hipMemcpyHostToDevice));
+		const StemEdgeCsr stem = build_stem_edge_csr(wf->h.edges.data(), E, n0);
+		if ((st = upload(ft->a_offsets, stem.offsets)) || (st = upload(ft->a_list, stem.list))) return st;
 		// CSR of edge incidences by node (source: 2 e, target: 2 e + 1), ascending e per node
 		std::vector<int> inc_off(static_cast<size_t>(N) + 1, 0), inc_list(2 * static_cast<size_t>(E));
 		for (int e = 0; e < E; e++) {
@@ -997,9 +894,6 @@ nnrt_status nnrt_fit_quad_order_table(const uint8_t* h_valid, int32_t H, int32_t
 			st = NNRT_ERROR_HIP;
 		}
 	}
-	d_ref.release();
-	d_scratch.release();
-	d_order.release();
 	return st;
 }
 
@@ -1628,18 +1522,16 @@ nnrt_status nnrt_warp_mesh(const float* d_vertices, const float* d_normals, int6
                            const double* h_E, float* d_out_vertices, float* d_out_normals, void* stream) {
 	NNRT_CHECK_ARG(d_vertices && d_normals && d_nodes && d_anchors && d_weights && d_out_vertices && d_out_normals, "null pointer");
 	hipStream_t s = static_cast<hipStream_t>(stream);
-	float* state = nullptr;
-	float4 *wp = nullptr, *wn = nullptr;
-	NNRT_HIP(hipMallocAsync(reinterpret_cast<void**>(&state), sizeof(float) * NODE_STRIDE * std::max(N, 1), s));
-	NNRT_HIP(hipMallocAsync(reinterpret_cast<void**>(&wp), sizeof(float4) * std::max<int64_t>(V, 1), s));
-	NNRT_HIP(hipMallocAsync(reinterpret_cast<void**>(&wn), sizeof(float4) * std::max<int64_t>(V, 1), s));
-	nnrt_status st = launch_pack_nodes(d_nodes, d_rotations, d_translations, N, state, s);
-	if (!st) st = launch_warp_mesh(d_vertices, d_normals, V, state, d_anchors, d_weights, K, make_extrinsics(h_E), wp, wn, nullptr, s);
-	if (!st) st = launch_unpack_float4x3(wp, V, d_out_vertices, s);
-	if (!st) st = launch_unpack_float4x3(wn, V, d_out_normals, s);
-	hipFreeAsync(state, s);
-	hipFreeAsync(wp, s);
-	hipFreeAsync(wn, s);
+	StreamScratch<float> state;
+	StreamScratch<float4> wp, wn;
+	nnrt_status st;
+	if ((st = state.alloc(static_cast<size_t>(NODE_STRIDE) * std::max(N, 1), s)) || (st = wp.alloc(std::max<int64_t>(V, 1), s)) ||
+	    (st = wn.alloc(std::max<int64_t>(V, 1), s)))
+		return st;
+	st = launch_pack_nodes(d_nodes, d_rotations, d_translations, N, state.ptr, s);
+	if (!st) st = launch_warp_mesh(d_vertices, d_normals, V, state.ptr, d_anchors, d_weights, K, make_extrinsics(h_E), wp.ptr, wn.ptr, nullptr, s);
+	if (!st) st = launch_unpack_float4x3(wp.ptr, V, d_out_vertices, s);
+	if (!st) st = launch_unpack_float4x3(wn.ptr, V, d_out_normals, s);
 	return st;
 }
 
@@ -1655,25 +1547,21 @@ nnrt_status nnrt_warp_points(const float* d_points, const float* d_normals, int6
 	NNRT_CHECK_ARG(!d_anchors == !d_weights, "anchors and anchor_weights must both be given");
 	if (V == 0) return NNRT_OK;
 	hipStream_t s = static_cast<hipStream_t>(stream);
-	float* state = nullptr;
-	int32_t* anchors = nullptr;
-	float* weights = nullptr;
-	NNRT_HIP(hipMallocAsync(reinterpret_cast<void**>(&state), sizeof(float) * NODE_STRIDE * std::max(N, 1), s));
-	nnrt_status st = launch_pack_nodes(d_nodes, d_rotations, d_translations, N, state, s);
+	StreamScratch<float> state, weights;
+	StreamScratch<int32_t> anchors;
+	nnrt_status st = state.alloc(static_cast<size_t>(NODE_STRIDE) * std::max(N, 1), s);
+	if (st) return st;
+	st = launch_pack_nodes(d_nodes, d_rotations, d_translations, N, state.ptr, s);
 	const int32_t* a = d_anchors;
 	const float* w = d_weights;
 	if (!st && !d_anchors) {   // online anchors: FindAnchorsAndWeightsForPoint_Euclidean[_Threshold]_FixedNodeCoverageWeight
-		NNRT_HIP(hipMallocAsync(reinterpret_cast<void**>(&anchors), sizeof(int32_t) * V * K, s));
-		NNRT_HIP(hipMallocAsync(reinterpret_cast<void**>(&weights), sizeof(float) * V * K, s));
-		st = launch_compute_anchors(d_points, V, d_nodes, N, K, coverage, nullptr, minimum_valid, anchors, weights, s, threshold ? 1 : 0);
-		a = anchors;
-		w = weights;
+		if ((st = anchors.alloc(static_cast<size_t>(V) * K, s)) || (st = weights.alloc(static_cast<size_t>(V) * K, s))) return st;
+		st = launch_compute_anchors(d_points, V, d_nodes, N, K, coverage, nullptr, minimum_valid, anchors.ptr, weights.ptr, s, threshold ? 1 : 0);
+		a = anchors.ptr;
+		w = weights.ptr;
 	}
-	if (!st) st = launch_warp_points(d_points, d_normals, V, state, a, w, K, threshold ? minimum_valid : -1, make_extrinsics(h_E), d_out_points,
+	if (!st) st = launch_warp_points(d_points, d_normals, V, state.ptr, a, w, K, threshold ? minimum_valid : -1, make_extrinsics(h_E), d_out_points,
 	                                 d_out_normals, s);
-	hipFreeAsync(state, s);
-	if (anchors) hipFreeAsync(anchors, s);
-	if (weights) hipFreeAsync(weights, s);
 	return st;
 }
 
@@ -1734,12 +1622,12 @@ nnrt_status nnrt_rasterize_ndc_triangles(const float* d_face_ndc, const uint8_t*
 	const RasterOptions o = make_raster_options(H, W, blur_radius_pixels / (static_cast<float>(fminf(H, W)) / 2.0f), perspective, clip_barycentric, cull_back_faces);
 	if (faces_per_pixel == 1) {
 		const int64_t P = static_cast<int64_t>(H) * W;
-		uint64_t* keys = nullptr;
-		NNRT_HIP(hipMallocAsync(reinterpret_cast<void**>(&keys), sizeof(uint64_t) * P, s));
-		NNRT_HIP(hipMemsetAsync(keys, 0xff, sizeof(uint64_t) * P, s));
-		nnrt_status st = launch_raster_scatter_ndc(d_face_ndc, d_clip_mask, F, o, keys, s);
-		if (!st) st = launch_raster_resolve(d_face_ndc, F, o, keys, d_faces_out, d_depth_out, d_bary_out, d_dist_out, s);
-		hipFreeAsync(keys, s);
+		StreamScratch<uint64_t> keys;
+		nnrt_status st = keys.alloc(static_cast<size_t>(P), s);
+		if (st) return st;
+		NNRT_HIP(hipMemsetAsync(keys.ptr, 0xff, sizeof(uint64_t) * P, s));
+		st = launch_raster_scatter_ndc(d_face_ndc, d_clip_mask, F, o, keys.ptr, s);
+		if (!st) st = launch_raster_resolve(d_face_ndc, F, o, keys.ptr, d_faces_out, d_depth_out, d_bary_out, d_dist_out, s);
 		return st;
 	}
 	return launch_raster_multi(d_face_ndc, d_clip_mask, F, o, faces_per_pixel, d_faces_out, d_depth_out, d_bary_out, d_dist_out, s);
@@ -1814,17 +1702,15 @@ nnrt_status nnrt_axis_angle_to_matrices_rodrigues(const float* d_vectors, int32_
 nnrt_status nnrt_solve_block_diagonal_cholesky(const float* d_blocks, const float* d_b, int32_t count, int32_t block_size, float* d_x,
                                                void* stream) {
 	hipStream_t s = static_cast<hipStream_t>(stream);
-	int* flag = nullptr;
-	NNRT_HIP(hipMallocAsync(reinterpret_cast<void**>(&flag), sizeof(int), s));
-	NNRT_HIP(hipMemsetAsync(flag, 0, sizeof(int), s));
-	nnrt_status st = launch_solve_block_diagonal(d_blocks, d_b, count, block_size, d_x, flag, s);
-	int host_flag = 0;
-	if (!st) {
-		NNRT_HIP(hipMemcpyAsync(&host_flag, flag, sizeof(int), hipMemcpyDeviceToHost, s));
-		NNRT_HIP(hipStreamSynchronize(s));
-	}
-	hipFreeAsync(flag, s);
+	StreamScratch<int> flag;
+	nnrt_status st = flag.alloc(1, s);
 	if (st) return st;
+	NNRT_HIP(hipMemsetAsync(flag.ptr, 0, sizeof(int), s));
+	st = launch_solve_block_diagonal(d_blocks, d_b, count, block_size, d_x, flag.ptr, s);
+	if (st) return st;
+	int host_flag = 0;
+	NNRT_HIP(hipMemcpyAsync(&host_flag, flag.ptr, sizeof(int), hipMemcpyDeviceToHost, s));
+	NNRT_HIP(hipStreamSynchronize(s));
 	if (host_flag) {
 		set_error("potrf failed in SolveBlockDiagonalCholesky (block not positive-definite)");
 		return NNRT_ERROR_NOT_POSITIVE_DEFINITE;
@@ -1835,17 +1721,15 @@ nnrt_status nnrt_solve_block_diagonal_cholesky(const float* d_blocks, const floa
 nnrt_status nnrt_invert_positive_semidefinite_blocks(const float* d_blocks, int32_t count, int32_t block_size, float* d_out, void* stream) {
 	hipStream_t s = static_cast<hipStream_t>(stream);
 	NNRT_CHECK_ARG(count >= 0, "negative block count");
-	int* flag = nullptr;
-	NNRT_HIP(hipMallocAsync(reinterpret_cast<void**>(&flag), sizeof(int), s));
-	NNRT_HIP(hipMemsetAsync(flag, 0, sizeof(int), s));
-	nnrt_status st = launch_invert_psd_blocks(d_blocks, count, block_size, d_out, flag, s);
-	int host_flag = 0;
-	if (!st) {
-		NNRT_HIP(hipMemcpyAsync(&host_flag, flag, sizeof(int), hipMemcpyDeviceToHost, s));
-		NNRT_HIP(hipStreamSynchronize(s));
-	}
-	hipFreeAsync(flag, s);
+	StreamScratch<int> flag;
+	nnrt_status st = flag.alloc(1, s);
 	if (st) return st;
+	NNRT_HIP(hipMemsetAsync(flag.ptr, 0, sizeof(int), s));
+	st = launch_invert_psd_blocks(d_blocks, count, block_size, d_out, flag.ptr, s);
+	if (st) return st;
+	int host_flag = 0;
+	NNRT_HIP(hipMemcpyAsync(&host_flag, flag.ptr, sizeof(int), hipMemcpyDeviceToHost, s));
+	NNRT_HIP(hipStreamSynchronize(s));
 	if (host_flag) {
 		set_error("potrf failed in InvertPositiveSemidefiniteBlocks (block not positive-definite)");
 		return NNRT_ERROR_NOT_POSITIVE_DEFINITE;
@@ -1857,17 +1741,15 @@ extern "C++" {
 // runs launch(flag) on the stream with a zeroed device flag; a raised flag becomes `code` with `message`
 template <typename F>
 nnrt_status with_device_flag(hipStream_t s, nnrt_status code, const char* message, F&& launch) {
-	int* flag = nullptr;
-	NNRT_HIP(hipMallocAsync(reinterpret_cast<void**>(&flag), sizeof(int), s));
-	NNRT_HIP(hipMemsetAsync(flag, 0, sizeof(int), s));
-	nnrt_status st = launch(flag);
-	int host_flag = 0;
-	if (!st) {
-		NNRT_HIP(hipMemcpyAsync(&host_flag, flag, sizeof(int), hipMemcpyDeviceToHost, s));
-		NNRT_HIP(hipStreamSynchronize(s));
-	}
-	hipFreeAsync(flag, s);
+	StreamScratch<int> flag;
+	nnrt_status st = flag.alloc(1, s);
 	if (st) return st;
+	NNRT_HIP(hipMemsetAsync(flag.ptr, 0, sizeof(int), s));
+	st = launch(flag.ptr);
+	if (st) return st;
+	int host_flag = 0;
+	NNRT_HIP(hipMemcpyAsync(&host_flag, flag.ptr, sizeof(int), hipMemcpyDeviceToHost, s));
+	NNRT_HIP(hipStreamSynchronize(s));
 	if (host_flag) {
 		set_error(message);
 		return code;
@@ -2119,11 +2001,6 @@ struct ArrowheadPlan {
 	DeviceBuffer<float> dinv, dinv_b;
 	DeviceBuffer<int> edge_offsets, edge_list, flag, tgt_off, rhs_off, rhs_edges;
 	DeviceBuffer<int2> tgt_ab, pairs;
-	~ArrowheadPlan() {
-		for (auto* b : {&dinv, &dinv_b}) b->release();
-		for (auto* b : {&edge_offsets, &edge_list, &flag, &tgt_off, &rhs_off, &rhs_edges}) b->release();
-		for (auto* b : {&tgt_ab, &pairs}) b->release();
-	}
 	bool matches(int dev, int32_t n, int32_t base, const std::vector<int32_t>& c) const {
 		return device == dev && N == n && n0 == base && coords == c;
 	}
@@ -2133,19 +2010,13 @@ struct ArrowheadPlan {
 		n0 = base;
 		coords = std::move(c);
 		E = static_cast<int>(coords.size() / 2);
-		std::vector<int> counts(n0 + 1, 0), list(std::max(E, 1)), fill;
-		for (int e = 0; e < E; e++)
-			if (coords[2 * e] < n0) counts[coords[2 * e] + 1]++;
-		for (int i = 0; i < n0; i++) counts[i + 1] += counts[i];
-		fill.assign(counts.begin(), counts.end() - 1);
-		for (int e = 0; e < E; e++)
-			if (coords[2 * e] < n0) list[fill[coords[2 * e]]++] = e;
+		const StemEdgeCsr stem = build_stem_edge_csr(coords.data(), E, n0);
 		nnrt_status st = corner.prepare(coords.data(), E, n0, N);
 		if (st) return st;
 		const StemSchurLists sl = build_stem_schur_lists(coords.data(), E, n0, N);
 		targets = static_cast<int>(sl.tgt_ab.size());
 		if ((st = dinv.ensure(36 * static_cast<size_t>(std::max(n0, 1)))) || (st = dinv_b.ensure(36 * static_cast<size_t>(std::max(E, 1)))) ||
-		    (st = flag.ensure(1)) || (st = upload(edge_offsets, counts)) || (st = upload(edge_list, list)) || (st = upload(tgt_off, sl.tgt_off)) ||
+		    (st = flag.ensure(1)) || (st = upload(edge_offsets, stem.offsets)) || (st = upload(edge_list, stem.list)) || (st = upload(tgt_off, sl.tgt_off)) ||
 		    (st = upload(tgt_ab, sl.tgt_ab)) || (st = upload(pairs, sl.pairs)) || (st = upload(rhs_off, sl.rhs_off)) ||
 		    (st = upload(rhs_edges, sl.rhs_edges)))
 			return st;
@@ -2233,7 +2104,7 @@ nnrt_status nnrt_solve_block_sparse_arrowhead_cholesky(const float* d_diag, cons
 			return NNRT_ERROR_HIP;   // the plan is dropped (its device work state is unknown)
 		}
 		// the stream is drained: the plan's scratch is free for the next call with this structure; evicted plans are
-		// destroyed after the lock is released (hipFree synchronises the device and must not block other threads' lookups)
+		// destroyed after the lock is released (freeing device memory synchronises the device and must not block other threads' lookups)
 		std::list<std::unique_ptr<ArrowheadPlan>> evicted;
 		{
 			std::lock_guard<std::mutex> lock(g_arrow_mu);
@@ -2258,7 +2129,7 @@ nnrt_status nnrt_solve_block_sparse_arrowhead_cholesky(const float* d_diag, cons
 }
 
 void nnrt_release_arrowhead_plans(void) {
-	std::list<std::unique_ptr<ArrowheadPlan>> released;   // freed after the lock is dropped (hipFree synchronises)
+	std::list<std::unique_ptr<ArrowheadPlan>> released;   // freed after the lock is dropped (freeing synchronises the device)
 	{
 		std::lock_guard<std::mutex> lock(g_arrow_mu);
 		released.swap(arrow_pool());

@@ -303,3 +303,5 @@ __host__ __device__ inline void pixel_span(float lo, float hi, int dim, int othe
 }
 
 } // namespace nnrt
+
+#include "device_memory.hpp"   // DeviceBuffer, StreamScratch, DeviceGuard: who owns device memory

@@ -1876,11 +1876,6 @@ constexpr int WALK_LDS_BUDGET = 160 * 1024;   // the CU's LDS: the walk's dynami
 #ifndef NNRT_WALK_MAX_TILES
 #define NNRT_WALK_MAX_TILES 48
 #endif
-struct WalkElem {
-	const float* tile;   // 64 x 64 row-major tile
-	int x_off;           // entry: first unknown of the tile whose x (back) / y (forward) it multiplies; head: J * 64
-	int info;            // entry: -1; head: 1 if the tile is L_JJ^-1, 0 if it is L_JJ
-};
 struct CornerWalkArgs {
 	const unsigned* gate;  // nullable: run only if the pivot ratio word is below ratio (the refinement pass)
 	float ratio;
@@ -2077,20 +2072,6 @@ __global__ __launch_bounds__(WT) void k_corner_walk(CornerWalkArgs a) {
 // ===================================================================================================================
 // CornerSolver
 // ===================================================================================================================
-template <typename T>
-static nnrt_status dev_upload(T*& ptr, const std::vector<T>& host) {
-	if (ptr) hipFree(ptr);
-	ptr = nullptr;
-	NNRT_HIP(hipMalloc(reinterpret_cast<void**>(&ptr), sizeof(T) * std::max<size_t>(host.size(), 1)));
-	if (!host.empty()) NNRT_HIP(hipMemcpy(ptr, host.data(), sizeof(T) * host.size(), hipMemcpyHostToDevice));
-	return NNRT_OK;
-}
-
-static void dev_free(void*& p) {
-	if (p) hipFree(p);
-	p = nullptr;
-}
-
 // development switches (A/B builds without rebuilding): NNRT_CORNER_WALK=1 enables the single-workgroup walk for small
 // corners (round 4's default; the dataflow launch measured faster at C1_ARAP, 7,636 vs 7,500 GN it/s, and equal at
 // C2_ARAP in round 5), NNRT_CORNER_FLOW=0 disables the dataflow substitution launch, NNRT_CORNER_TRIM=0 the
@@ -2116,33 +2097,10 @@ static bool walk_lds_cap_set() {
 	return true;
 }
 
-CornerSolver::~CornerSolver() { release(); }
-
 void CornerSolver::release() {
-	for (void** p : {reinterpret_cast<void**>(&tiles), reinterpret_cast<void**>(&ldiag), reinterpret_cast<void**>(&minv),
-	                 reinterpret_cast<void**>(&cb2), reinterpret_cast<void**>(&d_fwd_chains), reinterpret_cast<void**>(&d_fwd_cols),
-	                 reinterpret_cast<void**>(&sdiag), reinterpret_cast<void**>(&pivot_word),
-	                 reinterpret_cast<void**>(&d_fwd_ent), reinterpret_cast<void**>(&d_walk_back), reinterpret_cast<void**>(&d_walk_fwd),
-	                 reinterpret_cast<void**>(&cb),
-	                 reinterpret_cast<void**>(&xp), reinterpret_cast<void**>(&d_tile_slot), reinterpret_cast<void**>(&d_slot_ij),
-	                 reinterpret_cast<void**>(&d_row_node), reinterpret_cast<void**>(&d_node_row), reinterpret_cast<void**>(&d_tasks),
-	                 reinterpret_cast<void**>(&d_srcs), reinterpret_cast<void**>(&d_back_cols), reinterpret_cast<void**>(&d_back_ent), reinterpret_cast<void**>(&d_back_chains),
-	                 reinterpret_cast<void**>(&d_corner_edges), reinterpret_cast<void**>(&zx), reinterpret_cast<void**>(&d_back_pre),
-	                 reinterpret_cast<void**>(&d_fwd_pre), reinterpret_cast<void**>(&d_flow_chains), reinterpret_cast<void**>(&d_flow_need),
-	                 reinterpret_cast<void**>(&d_col_chain), reinterpret_cast<void**>(&flow_ctl), reinterpret_cast<void**>(&d_inv_cols)})
-		dev_free(*p);
-	use_flow = false;
-	fold_invert = false;
-	n_inv_cols = 0;
-	n_chains = n_flow_ctl = 0;
-	back_pre_off.clear();
-	fwd_pre_off.clear();
-	nc = ld = T = H = slots = n_corner_edges = 0;
-	level_off.clear();
-	level_panel.clear();
-	fwd_off.clear();
-	back_off.clear();
-	key.clear();
+	const uint64_t g = generation;
+	*this = CornerSolver();   // the members free their device memory
+	generation = g;
 }
 
 nnrt_status CornerSolver::prepare(const int32_t* edges, int E, int n0, int N, const float* corner_pos) {
@@ -2155,7 +2113,7 @@ nnrt_status CornerSolver::prepare(const int32_t* edges, int E, int n0, int N, co
 		k.resize(at + nf);
 		std::memcpy(k.data() + at, corner_pos, sizeof(float) * nf);
 	}
-	if (k == key && (nc == 0 || tiles)) return NNRT_OK;   // same hierarchy: keep the plan and its buffers
+	if (k == key && (nc == 0 || tiles.ptr)) return NNRT_OK;   // same hierarchy: keep the plan and its buffers
 	// the old buffers go now: bump the generation first, so that whatever captured them (the fitter's graphs) is dropped
 	// even if the new plan fails below; a failure leaves the solver empty (released), never half-built
 	release();
@@ -2165,26 +2123,22 @@ nnrt_status CornerSolver::prepare(const int32_t* edges, int E, int n0, int N, co
 		release();
 		return st;
 	};
-	auto alloc = [&](float*& ptr, size_t n) -> nnrt_status {
-		NNRT_HIP(hipMalloc(reinterpret_cast<void**>(&ptr), sizeof(float) * n));
-		return NNRT_OK;
-	};
 	if (p.nc > 0) {
 		nnrt_status st;
-		if ((st = alloc(tiles, p.slot_ij.size() * TILE_ELEMS)) || (st = alloc(ldiag, static_cast<size_t>(p.T) * TILE_ELEMS)) ||
-		    (st = alloc(minv, static_cast<size_t>(p.T) * TILE_ELEMS)) || (st = alloc(cb2, static_cast<size_t>(p.ld))) ||
-		    (st = alloc(sdiag, static_cast<size_t>(p.ld))) || (st = alloc(reinterpret_cast<float*&>(pivot_word), REFINE_WORDS)) ||
-		    (st = alloc(cb, static_cast<size_t>(p.ld))) || (st = alloc(xp, static_cast<size_t>(p.ld))) || (st = alloc(xp2, static_cast<size_t>(p.ld))) ||
-		    (st = alloc(zx, static_cast<size_t>(p.ld))))
+		if ((st = tiles.ensure(p.slot_ij.size() * TILE_ELEMS)) || (st = ldiag.ensure(static_cast<size_t>(p.T) * TILE_ELEMS)) ||
+		    (st = minv.ensure(static_cast<size_t>(p.T) * TILE_ELEMS)) || (st = cb2.ensure(static_cast<size_t>(p.ld))) ||
+		    (st = sdiag.ensure(static_cast<size_t>(p.ld))) || (st = pivot_word.ensure(REFINE_WORDS)) ||
+		    (st = cb.ensure(static_cast<size_t>(p.ld))) || (st = xp.ensure(static_cast<size_t>(p.ld))) || (st = xp2.ensure(static_cast<size_t>(p.ld))) ||
+		    (st = zx.ensure(static_cast<size_t>(p.ld))))
 			return fail(st);
-		if ((st = dev_upload(d_tile_slot, p.tile_slot)) || (st = dev_upload(d_slot_ij, p.slot_ij)) || (st = dev_upload(d_row_node, p.row_node)) ||
-		    (st = dev_upload(d_node_row, p.node_row)) || (st = dev_upload(d_tasks, p.tasks)) || (st = dev_upload(d_srcs, p.srcs)) ||
-		    (st = dev_upload(d_back_cols, p.back_cols)) || (st = dev_upload(d_back_ent, p.back_ent)) || (st = dev_upload(d_back_chains, p.back_chains)) ||
-		    (st = dev_upload(d_corner_edges, p.corner_edges)) ||
-		    (st = dev_upload(d_fwd_chains, p.fwd_chains)) || (st = dev_upload(d_fwd_cols, p.fwd_cols)) || (st = dev_upload(d_fwd_ent, p.fwd_ent)) ||
-		    (st = dev_upload(d_back_pre, p.back_pre)) || (st = dev_upload(d_fwd_pre, p.fwd_pre)))
+		if ((st = upload(d_tile_slot, p.tile_slot)) || (st = upload(d_slot_ij, p.slot_ij)) || (st = upload(d_row_node, p.row_node)) ||
+		    (st = upload(d_node_row, p.node_row)) || (st = upload(d_tasks, p.tasks)) || (st = upload(d_srcs, p.srcs)) ||
+		    (st = upload(d_back_cols, p.back_cols)) || (st = upload(d_back_ent, p.back_ent)) || (st = upload(d_back_chains, p.back_chains)) ||
+		    (st = upload(d_corner_edges, p.corner_edges)) ||
+		    (st = upload(d_fwd_chains, p.fwd_chains)) || (st = upload(d_fwd_cols, p.fwd_cols)) || (st = upload(d_fwd_ent, p.fwd_ent)) ||
+		    (st = upload(d_back_pre, p.back_pre)) || (st = upload(d_fwd_pre, p.fwd_pre)))
 			return fail(st);
-		if (hipMemset(cb2, 0, sizeof(float) * static_cast<size_t>(p.ld)) != hipSuccess) {   // identity padding rows stay 0
+		if (hipMemset(cb2.ptr, 0, sizeof(float) * static_cast<size_t>(p.ld)) != hipSuccess) {   // identity padding rows stay 0
 			set_error("hipMemset failed");
 			return fail(NNRT_ERROR_HIP);
 		}
@@ -2200,13 +2154,13 @@ nnrt_status CornerSolver::prepare(const int32_t* edges, int E, int n0, int N, co
 		if (ring_tiles >= 2) {
 			std::vector<WalkElem> wb, wf;
 			auto elem = [&](const int4& e) {
-				const float* base = e.x == 0 ? tiles : e.x == 1 ? minv : ldiag;
+				const float* base = e.x == 0 ? tiles.ptr : e.x == 1 ? minv.ptr : ldiag.ptr;
 				return WalkElem{base + static_cast<int64_t>(e.y) * TILE_ELEMS, e.z, e.w};
 			};
 			for (const auto& e : p.walk_back) wb.push_back(elem(e));
 			for (const auto& e : p.walk_fwd) wf.push_back(elem(e));
 			nnrt_status st;
-			if ((st = dev_upload(d_walk_back, wb)) || (st = dev_upload(d_walk_fwd, wf))) return fail(st);
+			if ((st = upload(d_walk_back, wb)) || (st = upload(d_walk_fwd, wf))) return fail(st);
 			walk_ring = ring_tiles;
 			walk_lds = static_cast<int>(fixed + static_cast<size_t>(ring_tiles) * 4 * TILE_ELEMS);
 			n_walk_back = static_cast<int>(wb.size());
@@ -2220,11 +2174,11 @@ nnrt_status CornerSolver::prepare(const int32_t* edges, int E, int n0, int N, co
 	}
 	if (p.nc > 0 && !walk_ok && env_flag("NNRT_CORNER_FLOW", true)) {   // dataflow substitution launches (k_corner_flow)
 		nnrt_status st;
-		if ((st = dev_upload(d_flow_chains, p.flow_chains)) || (st = dev_upload(d_flow_need, p.flow_need)) || (st = dev_upload(d_col_chain, p.col_chain)))
+		if ((st = upload(d_flow_chains, p.flow_chains)) || (st = upload(d_flow_need, p.flow_need)) || (st = upload(d_col_chain, p.col_chain)))
 			return fail(st);
 		n_chains = static_cast<int>(p.flow_chains.size());
 		n_flow_ctl = 2 * flow_ctl_words(n_chains);
-		if ((st = alloc(reinterpret_cast<float*&>(flow_ctl), static_cast<size_t>(n_flow_ctl)))) return fail(st);
+		if ((st = flow_ctl.ensure(static_cast<size_t>(n_flow_ctl)))) return fail(st);
 		use_flow = true;
 	}
 	nc = p.nc;
@@ -2265,14 +2219,14 @@ nnrt_status CornerSolver::prepare(const int32_t* edges, int E, int n0, int N, co
 				if (!last[static_cast<size_t>(J)]) cols.push_back(J);
 			n_inv_cols = static_cast<int>(cols.size());
 			nnrt_status st;
-			if (!cols.empty() && (st = dev_upload(d_inv_cols, cols))) return fail(st);
+			if (!cols.empty() && (st = upload(d_inv_cols, cols))) return fail(st);
 		}
 	}
 	key.swap(k);
 	return NNRT_OK;
 }
 
-CornerMap CornerSolver::map() const { return CornerMap{T, d_tile_slot, d_node_row, tiles, sdiag}; }
+CornerMap CornerSolver::map() const { return CornerMap{T, d_tile_slot.ptr, d_node_row.ptr, tiles.ptr, sdiag.ptr}; }
 
 nnrt_status CornerSolver::launch_init(int n0, const float* diag, const float* rhs, const int32_t* edges, const float* wing, hipStream_t s) const {
 	if (nc == 0) return NNRT_OK;
@@ -2285,7 +2239,7 @@ nnrt_status CornerSolver::launch_init(int n0, const float* diag, const float* rh
 nnrt_status CornerSolver::launch_offdiag(int n0, const int32_t* edges, const float* wing, hipStream_t s) const {
 	if (nc == 0) return NNRT_OK;
 	if (n_corner_edges > 0) {
-		k_corner_offdiag<<<n_corner_edges, 64, 0, s>>>(d_corner_edges, n0, edges, wing, map());
+		k_corner_offdiag<<<n_corner_edges, 64, 0, s>>>(d_corner_edges.ptr, n0, edges, wing, map());
 		NNRT_LAUNCH_CHECK();
 	}
 	return NNRT_OK;
@@ -2296,43 +2250,43 @@ nnrt_status CornerSolver::launch_solve(float* xout, int* error_flag, hipStream_t
 	nnrt_status st = launch_factor(error_flag, s);
 	if (st) return st;
 	if (walk_ok) {   // the back substitution as one single-workgroup walk
-		const CornerWalkArgs wa{nullptr, 0.f, nullptr, d_walk_back, 0, n_walk_back, cb, d_row_node, xout, ld, walk_ring};
+		const CornerWalkArgs wa{nullptr, 0.f, nullptr, d_walk_back.ptr, 0, n_walk_back, cb.ptr, d_row_node.ptr, xout, ld, walk_ring};
 		k_corner_walk<<<1, WT, walk_lds, s>>>(wa);
 		NNRT_LAUNCH_CHECK();
 		return NNRT_OK;
 	}
-	return launch_back(cb, xout, s, nullptr, 0.f);
+	return launch_back(cb.ptr, xout, s, nullptr, 0.f);
 }
 
 nnrt_status CornerSolver::launch_factor(int* error_flag, hipStream_t s) const {
 	if (nc == 0) return NNRT_OK;
 	CornerFactorArgs fa{};
-	fa.tiles = tiles;
-	fa.ldiag = ldiag;
-	fa.cb = cb;
-	fa.srcs = d_srcs;
+	fa.tiles = tiles.ptr;
+	fa.ldiag = ldiag.ptr;
+	fa.cb = cb.ptr;
+	fa.srcs = d_srcs.ptr;
 	fa.error_flag = error_flag;
-	fa.sdiag = sdiag;
-	fa.pivot_word = pivot_word;
-	fa.minv = minv;
-	fa.inv_cols = d_inv_cols;
+	fa.sdiag = sdiag.ptr;
+	fa.pivot_word = pivot_word.ptr;
+	fa.minv = minv.ptr;
+	fa.inv_cols = d_inv_cols.ptr;
 	for (int l = 0; l < H; l++) {
 		fa.level = l;
 		const int n = level_off[static_cast<size_t>(l) + 1] - level_off[static_cast<size_t>(l)];
-		fa.tasks = d_tasks + level_off[static_cast<size_t>(l)];
+		fa.tasks = d_tasks.ptr + level_off[static_cast<size_t>(l)];
 		fa.n_panel = level_panel[static_cast<size_t>(l)];
 		fa.n_tasks = n;
 		const bool last = fold_invert && l == H - 1;
 		fa.n_inv = last ? n_inv_cols : 0;
 		fa.invert_self = last ? 1 : 0;
-		fa.flow_ctl = last ? flow_ctl : nullptr;
+		fa.flow_ctl = last ? flow_ctl.ptr : nullptr;
 		fa.n_ctl = last ? n_flow_ctl : 0;
 		k_corner_factor<<<n + fa.n_inv, CTF, 0, s>>>(fa);
 		NNRT_LAUNCH_CHECK();
 	}
 	if (!fold_invert) {
 		// every diagonal factor's inverse, one workgroup per tile column (the substitutions multiply by them)
-		k_corner_invert<<<T, CT, 0, s>>>(ldiag, minv, flow_ctl, n_flow_ctl);
+		k_corner_invert<<<T, CT, 0, s>>>(ldiag.ptr, minv.ptr, flow_ctl.ptr, n_flow_ctl);
 		NNRT_LAUNCH_CHECK();
 	}
 	return NNRT_OK;
@@ -2350,16 +2304,16 @@ nnrt_status CornerSolver::launch_flow(const FlowStem& st, hipStream_t s) const {
 	a.ld = ld;
 	a.stem_wg = static_cast<int>(ceil_div(std::max(std::max(st.n_update, st.n0), st.mode == 1 ? st.N : 0), CT));
 	a.nxout = 6 * static_cast<int64_t>(nc);
-	a.ctl = flow_ctl;
-	a.chains = d_flow_chains;
-	a.fwd_need = d_flow_need;
-	a.col_chain = d_col_chain;
-	a.node_row = d_node_row;
-	a.back = CornerBackArgs{nullptr, 0.f, tiles, ldiag, minv, cb, xp, d_row_node, st.x + 6 * static_cast<int64_t>(st.n0), nullptr, d_back_cols,
-	                        d_back_ent, zx, 0};
-	a.fwd = CornerFwdArgs{nullptr, 0.f, tiles, ldiag, minv, cb2, nullptr, d_fwd_cols, d_fwd_ent, zx, 0};
-	a.back2 = CornerBackArgs{nullptr, 0.f, tiles, ldiag, minv, cb2, xp2, d_row_node, a.refine ? st.dx + 6 * static_cast<int64_t>(st.n0) : nullptr,
-	                         nullptr, d_back_cols, d_back_ent, zx, 0};
+	a.ctl = flow_ctl.ptr;
+	a.chains = d_flow_chains.ptr;
+	a.fwd_need = d_flow_need.ptr;
+	a.col_chain = d_col_chain.ptr;
+	a.node_row = d_node_row.ptr;
+	a.back = CornerBackArgs{nullptr, 0.f, tiles.ptr, ldiag.ptr, minv.ptr, cb.ptr, xp.ptr, d_row_node.ptr, st.x + 6 * static_cast<int64_t>(st.n0), nullptr, d_back_cols.ptr,
+	                        d_back_ent.ptr, zx.ptr, 0};
+	a.fwd = CornerFwdArgs{nullptr, 0.f, tiles.ptr, ldiag.ptr, minv.ptr, cb2.ptr, nullptr, d_fwd_cols.ptr, d_fwd_ent.ptr, zx.ptr, 0};
+	a.back2 = CornerBackArgs{nullptr, 0.f, tiles.ptr, ldiag.ptr, minv.ptr, cb2.ptr, xp2.ptr, d_row_node.ptr, a.refine ? st.dx + 6 * static_cast<int64_t>(st.n0) : nullptr,
+	                         nullptr, d_back_cols.ptr, d_back_ent.ptr, zx.ptr, 0};
 	a.st = st;
 	const int grid = n_chains + a.stem_wg + (a.refine ? T + 2 * n_chains + 2 * a.stem_wg : 0);
 	k_corner_flow<<<grid, CT, 0, s>>>(a);
@@ -2369,17 +2323,17 @@ nnrt_status CornerSolver::launch_flow(const FlowStem& st, hipStream_t s) const {
 
 // back substitution chains over y (with NNRT_SUBST_PRESUM, each launch preceded by its columns' pre-sums)
 nnrt_status CornerSolver::launch_back(const float* y, float* xout, hipStream_t s, const unsigned* gate, float refine_ratio) const {
-	CornerBackArgs ba{gate, refine_ratio, tiles, ldiag, minv, y, xp, d_row_node, xout, nullptr, d_back_cols, d_back_ent, zx, 0};
+	CornerBackArgs ba{gate, refine_ratio, tiles.ptr, ldiag.ptr, minv.ptr, y, xp.ptr, d_row_node.ptr, xout, nullptr, d_back_cols.ptr, d_back_ent.ptr, zx.ptr, 0};
 	for (size_t l = 0; l + 1 < back_off.size(); l++) {
 		const int n = back_off[l + 1] - back_off[l];
 		const int npre = NNRT_SUBST_PRESUM ? back_pre_off[l + 1] - back_pre_off[l] : 0;
 		if (npre > 0) {
-			ba.chains = d_back_pre + back_pre_off[l];
+			ba.chains = d_back_pre.ptr + back_pre_off[l];
 			ba.mode = 1;
 			k_corner_back<<<npre, CT, 0, s>>>(ba, ld, 6 * static_cast<int64_t>(nc));
 			NNRT_LAUNCH_CHECK();
 		}
-		ba.chains = d_back_chains + back_off[l];
+		ba.chains = d_back_chains.ptr + back_off[l];
 		ba.mode = NNRT_SUBST_PRESUM ? 2 : 0;
 		k_corner_back<<<n, CT, 0, s>>>(ba, ld, 6 * static_cast<int64_t>(nc));
 		NNRT_LAUNCH_CHECK();
@@ -2390,27 +2344,27 @@ nnrt_status CornerSolver::launch_back(const float* y, float* xout, hipStream_t s
 nnrt_status CornerSolver::launch_resolve(float* xout, hipStream_t s, const unsigned* gate, float refine_ratio) const {
 	if (nc == 0) return NNRT_OK;
 	if (walk_ok) {   // forward and back substitution in one single-workgroup launch
-		const CornerWalkArgs wa{gate, refine_ratio, d_walk_fwd, d_walk_back, n_walk_fwd, n_walk_back, cb2, d_row_node, xout, ld, walk_ring};
+		const CornerWalkArgs wa{gate, refine_ratio, d_walk_fwd.ptr, d_walk_back.ptr, n_walk_fwd, n_walk_back, cb2.ptr, d_row_node.ptr, xout, ld, walk_ring};
 		k_corner_walk<<<1, WT, walk_lds, s>>>(wa);
 		NNRT_LAUNCH_CHECK();
 		return NNRT_OK;
 	}
-	CornerFwdArgs fa{gate, refine_ratio, tiles, ldiag, minv, cb2, nullptr, d_fwd_cols, d_fwd_ent, zx, 0};
+	CornerFwdArgs fa{gate, refine_ratio, tiles.ptr, ldiag.ptr, minv.ptr, cb2.ptr, nullptr, d_fwd_cols.ptr, d_fwd_ent.ptr, zx.ptr, 0};
 	for (size_t l = 0; l + 1 < fwd_off.size(); l++) {
 		const int n = fwd_off[l + 1] - fwd_off[l];
 		const int npre = NNRT_SUBST_PRESUM ? fwd_pre_off[l + 1] - fwd_pre_off[l] : 0;
 		if (npre > 0) {
-			fa.chains = d_fwd_pre + fwd_pre_off[l];
+			fa.chains = d_fwd_pre.ptr + fwd_pre_off[l];
 			fa.mode = 1;
 			k_corner_fwd<<<npre, CT, 0, s>>>(fa, ld);
 			NNRT_LAUNCH_CHECK();
 		}
-		fa.chains = d_fwd_chains + fwd_off[l];
+		fa.chains = d_fwd_chains.ptr + fwd_off[l];
 		fa.mode = NNRT_SUBST_PRESUM ? 2 : 0;
 		k_corner_fwd<<<n, CT, 0, s>>>(fa, ld);
 		NNRT_LAUNCH_CHECK();
 	}
-	return launch_back(cb2, xout, s, gate, refine_ratio);
+	return launch_back(cb2.ptr, xout, s, gate, refine_ratio);
 }
 
 #ifdef NNRT_CORNER_STAMPS

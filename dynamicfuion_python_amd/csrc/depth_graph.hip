@@ -35,18 +35,6 @@ constexpr int GB = 256;   // threads per workgroup
 
 unsigned gblocks(int64_t n) { return static_cast<unsigned>(ceil_div(n, GB)); }
 
-template <typename T>
-struct Scratch {
-	T* p = nullptr;
-	~Scratch() {
-		if (p) (void)hipFree(p);
-	}
-	nnrt_status alloc(size_t n) {
-		NNRT_HIP(hipMalloc(&p, sizeof(T) * (n ? n : 1)));
-		return NNRT_OK;
-	}
-};
-
 // the reference's (a - b).norm(): unfused, correctly rounded (the build pins -ffp-contract=off; the pragma keeps it so)
 __device__ inline float edge_length(const float* __restrict__ a, const float* __restrict__ b) {
 #pragma clang fp contract(off)
@@ -174,10 +162,10 @@ __global__ __launch_bounds__(GB) void k_scatter_faces(const uint8_t* __restrict_
 nnrt_status exclusive_sum(const int* in, int* out, int n, hipStream_t s) {
 	size_t bytes = 0;
 	NNRT_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, bytes, in, out, n, s));
-	Scratch<uint8_t> tmp;
-	nnrt_status st = tmp.alloc(std::max<size_t>(bytes, 1));
+	DeviceBuffer<uint8_t> tmp;
+	nnrt_status st = tmp.ensure(std::max<size_t>(bytes, 1));
 	if (st) return st;
-	NNRT_HIP(hipcub::DeviceScan::ExclusiveSum(tmp.p, bytes, in, out, n, s));
+	NNRT_HIP(hipcub::DeviceScan::ExclusiveSum(tmp.ptr, bytes, in, out, n, s));
 	NNRT_HIP(hipStreamSynchronize(s));   // tmp is freed on return
 	return NNRT_OK;
 }
@@ -390,18 +378,18 @@ nnrt_status launch_mesh_from_depth(const float* pts, int H, int W, float limit, 
 	*h_face_count = 0;
 	if (H < 2 || W < 2) return NNRT_OK;
 	const int C = (H - 1) * (W - 1);
-	Scratch<uint8_t> bits;
-	Scratch<int> vcount, fcount, voff, foff, pixel_vertex;
+	DeviceBuffer<uint8_t> bits;
+	DeviceBuffer<int> vcount, fcount, voff, foff, pixel_vertex;
 	nnrt_status st;
-	if ((st = bits.alloc(C)) || (st = vcount.alloc(C + 1)) || (st = fcount.alloc(C + 1)) || (st = voff.alloc(C + 1)) || (st = foff.alloc(C + 1))) return st;
-	k_cell_bits<<<gblocks(C), GB, 0, s>>>(pts, H, W, limit, bits.p);
+	if ((st = bits.ensure(C)) || (st = vcount.ensure(C + 1)) || (st = fcount.ensure(C + 1)) || (st = voff.ensure(C + 1)) || (st = foff.ensure(C + 1))) return st;
+	k_cell_bits<<<gblocks(C), GB, 0, s>>>(pts, H, W, limit, bits.ptr);
 	NNRT_LAUNCH_CHECK();
-	k_cell_counts<<<gblocks(C + 1), GB, 0, s>>>(bits.p, H, W, vcount.p, fcount.p);
+	k_cell_counts<<<gblocks(C + 1), GB, 0, s>>>(bits.ptr, H, W, vcount.ptr, fcount.ptr);
 	NNRT_LAUNCH_CHECK();
-	if ((st = exclusive_sum(vcount.p, voff.p, C + 1, s)) || (st = exclusive_sum(fcount.p, foff.p, C + 1, s))) return st;
+	if ((st = exclusive_sum(vcount.ptr, voff.ptr, C + 1, s)) || (st = exclusive_sum(fcount.ptr, foff.ptr, C + 1, s))) return st;
 	int nv = 0, nf = 0;
-	NNRT_HIP(hipMemcpyAsync(&nv, voff.p + C, sizeof(int), hipMemcpyDeviceToHost, s));
-	NNRT_HIP(hipMemcpyAsync(&nf, foff.p + C, sizeof(int), hipMemcpyDeviceToHost, s));
+	NNRT_HIP(hipMemcpyAsync(&nv, voff.ptr + C, sizeof(int), hipMemcpyDeviceToHost, s));
+	NNRT_HIP(hipMemcpyAsync(&nf, foff.ptr + C, sizeof(int), hipMemcpyDeviceToHost, s));
 	NNRT_HIP(hipStreamSynchronize(s));
 	if (nv > vertex_cap || nf > face_cap) {
 		set_error("invalid argument: the mesh has " + std::to_string(nv) + " vertices and " + std::to_string(nf) + " faces, the capacity is " +
@@ -409,10 +397,10 @@ nnrt_status launch_mesh_from_depth(const float* pts, int H, int W, float limit, 
 		return NNRT_ERROR_ARGUMENT;
 	}
 	if (nf == 0) return NNRT_OK;   // then nv == 0 too: nothing to index
-	if ((st = pixel_vertex.alloc(static_cast<size_t>(H) * W))) return st;
-	k_scatter_vertices<<<gblocks(C), GB, 0, s>>>(pts, bits.p, H, W, voff.p, vertex_cap, vertices, pixels, pixel_vertex.p);
+	if ((st = pixel_vertex.ensure(static_cast<size_t>(H) * W))) return st;
+	k_scatter_vertices<<<gblocks(C), GB, 0, s>>>(pts, bits.ptr, H, W, voff.ptr, vertex_cap, vertices, pixels, pixel_vertex.ptr);
 	NNRT_LAUNCH_CHECK();
-	k_scatter_faces<<<gblocks(C), GB, 0, s>>>(bits.p, H, W, foff.p, face_cap, pixel_vertex.p, faces);
+	k_scatter_faces<<<gblocks(C), GB, 0, s>>>(bits.ptr, H, W, foff.ptr, face_cap, pixel_vertex.ptr, faces);
 	NNRT_LAUNCH_CHECK();
 	NNRT_HIP(hipStreamSynchronize(s));   // the scratch is freed on return
 	*h_vertex_count = nv;
@@ -453,29 +441,29 @@ nnrt_status launch_edges_shortest_path(const float* vertices, int64_t V, const u
 	nnrt_status st;
 	// CSR adjacency over the unique directed vertex pairs of the faces
 	const int64_t P = 6 * F;
-	Scratch<uint64_t> keys, sorted, pairs;
-	Scratch<uint8_t> flags, tmp;
-	Scratch<int> ctrl, d_count, row_start, col, vertex_node;
-	Scratch<float> len;
-	if ((st = keys.alloc(P)) || (st = sorted.alloc(P)) || (st = pairs.alloc(P)) || (st = flags.alloc(P)) || (st = ctrl.alloc(1)) ||
-	    (st = d_count.alloc(1)) || (st = row_start.alloc(V + 1)) || (st = vertex_node.alloc(V)))
+	DeviceBuffer<uint64_t> keys, sorted, pairs;
+	DeviceBuffer<uint8_t> flags, tmp;
+	DeviceBuffer<int> ctrl, d_count, row_start, col, vertex_node;
+	DeviceBuffer<float> len;
+	if ((st = keys.ensure(P)) || (st = sorted.ensure(P)) || (st = pairs.ensure(P)) || (st = flags.ensure(P)) || (st = ctrl.ensure(1)) ||
+	    (st = d_count.ensure(1)) || (st = row_start.ensure(V + 1)) || (st = vertex_node.ensure(V)))
 		return st;
-	NNRT_HIP(hipMemsetAsync(ctrl.p, 0, sizeof(int), s));
+	NNRT_HIP(hipMemsetAsync(ctrl.ptr, 0, sizeof(int), s));
 	int E = 0;
 	if (F > 0) {
-		k_face_pairs<<<gblocks(F), GB, 0, s>>>(faces, F, V, keys.p, ctrl.p);
+		k_face_pairs<<<gblocks(F), GB, 0, s>>>(faces, F, V, keys.ptr, ctrl.ptr);
 		NNRT_LAUNCH_CHECK();
 		size_t bytes = 0, select_bytes = 0;
-		NNRT_HIP(hipcub::DeviceRadixSort::SortKeys(nullptr, bytes, keys.p, sorted.p, static_cast<int>(P), 0, 64, s));
-		NNRT_HIP(hipcub::DeviceSelect::Flagged(nullptr, select_bytes, sorted.p, flags.p, pairs.p, d_count.p, static_cast<int>(P), s));
-		if ((st = tmp.alloc(std::max<size_t>(std::max(bytes, select_bytes), 1)))) return st;
-		NNRT_HIP(hipcub::DeviceRadixSort::SortKeys(tmp.p, bytes, keys.p, sorted.p, static_cast<int>(P), 0, 64, s));
-		k_pair_flags<<<gblocks(P), GB, 0, s>>>(sorted.p, P, flags.p);
+		NNRT_HIP(hipcub::DeviceRadixSort::SortKeys(nullptr, bytes, keys.ptr, sorted.ptr, static_cast<int>(P), 0, 64, s));
+		NNRT_HIP(hipcub::DeviceSelect::Flagged(nullptr, select_bytes, sorted.ptr, flags.ptr, pairs.ptr, d_count.ptr, static_cast<int>(P), s));
+		if ((st = tmp.ensure(std::max<size_t>(std::max(bytes, select_bytes), 1)))) return st;
+		NNRT_HIP(hipcub::DeviceRadixSort::SortKeys(tmp.ptr, bytes, keys.ptr, sorted.ptr, static_cast<int>(P), 0, 64, s));
+		k_pair_flags<<<gblocks(P), GB, 0, s>>>(sorted.ptr, P, flags.ptr);
 		NNRT_LAUNCH_CHECK();
-		NNRT_HIP(hipcub::DeviceSelect::Flagged(tmp.p, select_bytes, sorted.p, flags.p, pairs.p, d_count.p, static_cast<int>(P), s));
+		NNRT_HIP(hipcub::DeviceSelect::Flagged(tmp.ptr, select_bytes, sorted.ptr, flags.ptr, pairs.ptr, d_count.ptr, static_cast<int>(P), s));
 		int err = 0;
-		NNRT_HIP(hipMemcpyAsync(&E, d_count.p, sizeof(int), hipMemcpyDeviceToHost, s));
-		NNRT_HIP(hipMemcpyAsync(&err, ctrl.p, sizeof(int), hipMemcpyDeviceToHost, s));
+		NNRT_HIP(hipMemcpyAsync(&E, d_count.ptr, sizeof(int), hipMemcpyDeviceToHost, s));
+		NNRT_HIP(hipMemcpyAsync(&err, ctrl.ptr, sizeof(int), hipMemcpyDeviceToHost, s));
 		NNRT_HIP(hipStreamSynchronize(s));
 		if (err) {
 			set_error("invalid argument: face index outside [0, vertex_count) in compute_edges_shortest_path");
@@ -483,51 +471,51 @@ nnrt_status launch_edges_shortest_path(const float* vertices, int64_t V, const u
 		}
 	}
 	if (pending.empty()) return NNRT_OK;
-	if ((st = col.alloc(E)) || (st = len.alloc(E))) return st;
-	k_row_starts<<<gblocks(V + 1), GB, 0, s>>>(pairs.p, E, V, row_start.p);
+	if ((st = col.ensure(E)) || (st = len.ensure(E))) return st;
+	k_row_starts<<<gblocks(V + 1), GB, 0, s>>>(pairs.ptr, E, V, row_start.ptr);
 	NNRT_LAUNCH_CHECK();
 	if (E > 0) {
-		k_pair_columns<<<gblocks(E), GB, 0, s>>>(pairs.p, E, vertices, col.p, len.p);
+		k_pair_columns<<<gblocks(E), GB, 0, s>>>(pairs.ptr, E, vertices, col.ptr, len.ptr);
 		NNRT_LAUNCH_CHECK();
 	}
-	NNRT_HIP(hipMemsetAsync(vertex_node.p, 0xff, sizeof(int) * V, s));
-	k_vertex_nodes<<<gblocks(N), GB, 0, s>>>(node_vertex, N, vertex_node.p);
+	NNRT_HIP(hipMemsetAsync(vertex_node.ptr, 0xff, sizeof(int) * V, s));
+	k_vertex_nodes<<<gblocks(N), GB, 0, s>>>(node_vertex, N, vertex_node.ptr);
 	NNRT_LAUNCH_CHECK();
 
 	// B workgroup slots of 20 bytes per vertex and 8 per node each, within 1 GiB
 	const size_t per_slot = 20 * static_cast<size_t>(V) + 8 * static_cast<size_t>(N);
 	const int B = static_cast<int>(std::max<size_t>(1, std::min<size_t>(pending.size(), (size_t(1) << 30) / per_slot)));
 	const size_t BV = static_cast<size_t>(B) * V;
-	Scratch<unsigned> dist;
-	Scratch<int> queued_round, reached, list_a, list_b, batch, found, cut;
-	Scratch<unsigned long long> candidates;
-	if ((st = dist.alloc(BV)) || (st = queued_round.alloc(BV)) || (st = reached.alloc(BV)) || (st = list_a.alloc(BV)) || (st = list_b.alloc(BV)) ||
-	    (st = candidates.alloc(static_cast<size_t>(B) * N)) || (st = batch.alloc(N)) || (st = found.alloc(N)) || (st = cut.alloc(N)))
+	DeviceBuffer<unsigned> dist;
+	DeviceBuffer<int> queued_round, reached, list_a, list_b, batch, found, cut;
+	DeviceBuffer<unsigned long long> candidates;
+	if ((st = dist.ensure(BV)) || (st = queued_round.ensure(BV)) || (st = reached.ensure(BV)) || (st = list_a.ensure(BV)) || (st = list_b.ensure(BV)) ||
+	    (st = candidates.ensure(static_cast<size_t>(B) * N)) || (st = batch.ensure(N)) || (st = found.ensure(N)) || (st = cut.ensure(N)))
 		return st;
-	NNRT_HIP(hipMemsetAsync(dist.p, 0xff, sizeof(unsigned) * BV, s));
-	NNRT_HIP(hipMemsetAsync(queued_round.p, 0, sizeof(int) * BV, s));
+	NNRT_HIP(hipMemsetAsync(dist.ptr, 0xff, sizeof(unsigned) * BV, s));
+	NNRT_HIP(hipMemsetAsync(queued_round.ptr, 0, sizeof(int) * BV, s));
 	GeodesicArgs a;
 	a.node_vertex = node_vertex;
 	a.V = V;
 	a.N = N;
 	a.K = K;
-	a.row_start = row_start.p;
-	a.col = col.p;
-	a.len = len.p;
+	a.row_start = row_start.ptr;
+	a.col = col.ptr;
+	a.len = len.ptr;
 	a.mask = mask;
-	a.vertex_node = vertex_node.p;
+	a.vertex_node = vertex_node.ptr;
 	a.coverage = coverage;
-	a.dist = dist.p;
-	a.queued_round = queued_round.p;
-	a.reached = reached.p;
-	a.list_a = list_a.p;
-	a.list_b = list_b.p;
-	a.candidates = candidates.p;
+	a.dist = dist.ptr;
+	a.queued_round = queued_round.ptr;
+	a.reached = reached.ptr;
+	a.list_a = list_a.ptr;
+	a.list_b = list_b.ptr;
+	a.candidates = candidates.ptr;
 	a.edges = edges;
 	a.weights = weights;
 	a.distances = distances;
-	a.found = found.p;
-	a.cut = cut.p;
+	a.found = found.ptr;
+	a.cut = cut.ptr;
 	// Bounded mode: one pass at R = 2 * coverage (graph_proc.cpp:212, :306). Enforced mode: the reference has no bound. A
 	// pass at R reaches exactly the vertices with D <= R, at their final distances (file header), so a node that found K
 	// other nodes has its K nearest, and one whose frontier met no refusal has everything it can reach; only the others
@@ -537,16 +525,16 @@ nnrt_status launch_edges_shortest_path(const float* vertices, int64_t V, const u
 	int passes = 0;
 	while (!pending.empty()) {
 		a.radius = radius;
-		NNRT_HIP(hipMemcpyAsync(batch.p, pending.data(), sizeof(int) * pending.size(), hipMemcpyHostToDevice, s));
+		NNRT_HIP(hipMemcpyAsync(batch.ptr, pending.data(), sizeof(int) * pending.size(), hipMemcpyHostToDevice, s));
 		for (size_t first = 0; first < pending.size(); first += B) {
 			const int nb = static_cast<int>(std::min<size_t>(B, pending.size() - first));
-			a.batch = batch.p + first;
+			a.batch = batch.ptr + first;
 			k_geodesic<<<nb, GB, 0, s>>>(a);
 			NNRT_LAUNCH_CHECK();
 		}
 		passes++;
-		NNRT_HIP(hipMemcpyAsync(h_found.data(), found.p, sizeof(int) * N, hipMemcpyDeviceToHost, s));
-		NNRT_HIP(hipMemcpyAsync(h_cut.data(), cut.p, sizeof(int) * N, hipMemcpyDeviceToHost, s));
+		NNRT_HIP(hipMemcpyAsync(h_found.data(), found.ptr, sizeof(int) * N, hipMemcpyDeviceToHost, s));
+		NNRT_HIP(hipMemcpyAsync(h_cut.data(), cut.ptr, sizeof(int) * N, hipMemcpyDeviceToHost, s));
 		NNRT_HIP(hipStreamSynchronize(s));   // also: `pending` may change now
 		if (!enforce || std::isinf(radius)) break;
 		std::vector<int> again;

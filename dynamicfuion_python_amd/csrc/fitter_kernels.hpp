@@ -322,7 +322,12 @@ __device__ inline void corner_init_thread(int64_t idx, const CornerInitArgs& a, 
 	*reinterpret_cast<float4*>(a.tiles + static_cast<int64_t>(s) * TE + r * TL + c0) = make_float4(v[0], v[1], v[2], v[3]);
 }
 
-struct WalkElem;   // corner.hip: one tile of a single-workgroup substitution walk
+// one tile of a single-workgroup substitution walk (corner.hip k_corner_walk)
+struct WalkElem {
+	const float* tile;   // 64 x 64 row-major tile
+	int x_off;           // entry: first unknown of the tile whose x (back) / y (forward) it multiplies; head: J * 64
+	int info;            // entry: -1; head: 1 if the tile is L_JJ^-1, 0 if it is L_JJ
+};
 
 // the stem side of a dataflow substitution launch (CornerSolver::launch_flow; arap.hip fills it)
 struct FlowStem {
@@ -347,7 +352,6 @@ __host__ __device__ inline int flow_ctl_words(int nB) { return 4 + 3 * nB; }
 
 class CornerSolver {
 public:
-	~CornerSolver();
 	// host, once per hierarchy (edges [E,2] host, virtual order; corner = nodes >= n0; corner_pos [N - n0, 3] host or
 	// nullptr): ordering (coordinate bisection with positions, graph separators without), symbolic factorisation, launch
 	// plan, device buffers. A repeated call with the same inputs keeps everything (stable pointers for graphs).
@@ -355,7 +359,7 @@ public:
 	// S = C (+ corner off-diagonal blocks) in the stored tiles, cb = b_C (permuted); diag [N,36], rhs [6N], edges / wing device
 	nnrt_status launch_init(int n0, const float* diag, const float* rhs, const int32_t* edges, const float* wing, hipStream_t s) const;
 	// the two halves of launch_init, for callers that run the init threads inside a launch of their own
-	CornerInitArgs init_args(int n0) const { return CornerInitArgs{n0, ld, slots, d_slot_ij, d_row_node, tiles, cb, sdiag, pivot_word}; }
+	CornerInitArgs init_args(int n0) const { return CornerInitArgs{n0, ld, slots, d_slot_ij.ptr, d_row_node.ptr, tiles.ptr, cb.ptr, sdiag.ptr, pivot_word.ptr}; }
 	nnrt_status launch_offdiag(int n0, const int32_t* edges, const float* wing, hipStream_t s) const;   // >= 3 layers
 	// factor S (after the stem's Schur update), solve S x = cb; x -> xout[6 nc] in corner-node order
 	nnrt_status launch_solve(float* xout, int* error_flag, hipStream_t s) const;
@@ -370,12 +374,12 @@ public:
 	// factor S and form the diagonal inverses (the first half of launch_solve; the flow launches do the rest)
 	nnrt_status launch_factor(int* error_flag, hipStream_t s) const;
 	bool flow_ok() const { return use_flow; }
-	float* refine_rhs() const { return cb2; }
+	float* refine_rhs() const { return cb2.ptr; }
 	// the factorization's minimum pivot / diag(S) ratio of the last solve (device word, float bits)
-	const unsigned* pivot_ratio() const { return pivot_word; }
-	unsigned* refine_guard() const { return pivot_word; }   // [REFINE_WORDS]: the gate word, then the safeguard's
+	const unsigned* pivot_ratio() const { return pivot_word.ptr; }
+	unsigned* refine_guard() const { return pivot_word.ptr; }   // [REFINE_WORDS]: the gate word, then the safeguard's
 	CornerMap map() const;
-	float* rhs_perm() const { return cb; }
+	float* rhs_perm() const { return cb.ptr; }
 	int levels() const { return H; }
 	int tile_columns() const { return T; }
 	int back_launches() const { return walk_ok ? 1 : back_off.empty() ? 0 : static_cast<int>(back_off.size()) - 1; }
@@ -388,36 +392,35 @@ public:
 	uint64_t generation = 0;    // bumped whenever the plan (and its buffers) change
 
 private:
-	void release();
+	void release();   // back to the empty solver: the plan and every device buffer
 	std::vector<int32_t> key;
 	int nc = 0, ld = 0, T = 0, H = 0, slots = 0, n_corner_edges = 0;
 	int64_t fill_tiles = 0, dense_tiles = 0, exec_mfma_flops = 0, n_terms = 0, elim_cols = 0;
-	float *tiles = nullptr, *ldiag = nullptr, *minv = nullptr, *cb = nullptr, *cb2 = nullptr, *xp = nullptr, *sdiag = nullptr;
-	float* xp2 = nullptr;   // the refinement's back substitution in a dataflow launch (its own lines: no L1 copy of xp's)
-	float* zx = nullptr;   // [ld] substitution pre-sums (NNRT_SUBST_PRESUM)
-	int2 *d_back_pre = nullptr, *d_fwd_pre = nullptr;
+	DeviceBuffer<float> tiles, ldiag, minv, cb, cb2, xp, sdiag;
+	DeviceBuffer<float> xp2;   // the refinement's back substitution in a dataflow launch (its own lines: no L1 copy of xp's)
+	DeviceBuffer<float> zx;   // [ld] substitution pre-sums (NNRT_SUBST_PRESUM)
+	DeviceBuffer<int2> d_back_pre, d_fwd_pre;
 	std::vector<int> back_pre_off, fwd_pre_off;
-	unsigned* pivot_word = nullptr;
-	int2 *d_fwd_chains = nullptr, *d_fwd_ent = nullptr;
-	int4* d_fwd_cols = nullptr;
+	DeviceBuffer<unsigned> pivot_word;
+	DeviceBuffer<int2> d_fwd_chains, d_fwd_ent;
+	DeviceBuffer<int4> d_fwd_cols;
 	// single-workgroup substitution walks (corner.hip k_corner_walk), when the permuted vector and the descriptors fit in LDS
 	bool walk_ok = false;
 	// dataflow substitution plan (k_corner_flow): per chain (back column first, count, forward column first, parent)
 	bool use_flow = false;
 	int n_chains = 0, n_flow_ctl = 0;
-	int4* d_flow_chains = nullptr;
-	int *d_flow_need = nullptr, *d_col_chain = nullptr;
-	unsigned* flow_ctl = nullptr;
+	DeviceBuffer<int4> d_flow_chains;
+	DeviceBuffer<int> d_flow_need, d_col_chain;
+	DeviceBuffer<unsigned> flow_ctl;
 	bool fold_invert = false;   // the diagonal inverses in the last factor launch (no k_corner_invert launch)
 	int n_inv_cols = 0;         // tile columns inverted by that launch's extra workgroups
-	int* d_inv_cols = nullptr;
+	DeviceBuffer<int> d_inv_cols;
 	int walk_ring = 0, walk_lds = 0, n_walk_back = 0, n_walk_fwd = 0;
-	WalkElem* d_walk_back = nullptr;
-	WalkElem* d_walk_fwd = nullptr;
-	int *d_tile_slot = nullptr, *d_row_node = nullptr, *d_node_row = nullptr, *d_corner_edges = nullptr;
-	int2 *d_slot_ij = nullptr, *d_back_ent = nullptr, *d_back_chains = nullptr;
-	CornerTask* d_tasks = nullptr;
-	int4 *d_srcs = nullptr, *d_back_cols = nullptr;
+	DeviceBuffer<WalkElem> d_walk_back, d_walk_fwd;
+	DeviceBuffer<int> d_tile_slot, d_row_node, d_node_row, d_corner_edges;
+	DeviceBuffer<int2> d_slot_ij, d_back_ent, d_back_chains;
+	DeviceBuffer<CornerTask> d_tasks;
+	DeviceBuffer<int4> d_srcs, d_back_cols;
 	std::vector<int> level_off, level_panel, back_off, fwd_off;
 };
 
@@ -496,6 +499,12 @@ struct ArrowheadWorkspace {
 	int* rhs_off = nullptr;     // [N - n0 + 1] CSR into `rhs_edges` by corner node
 	int* rhs_edges = nullptr;   // stem edges into each corner node
 };
+// host: CSR of the stem edges (source node < n0) by source node: offsets [n0 + 1] into list [E] (its first offsets[n0]
+// entries, edge indices ascending per node) -- the workspace's edge_offsets / edge_list
+struct StemEdgeCsr {
+	std::vector<int> offsets, list;
+};
+StemEdgeCsr build_stem_edge_csr(const int32_t* edges, int E, int n0);
 struct StemSchurLists {
 	std::vector<int> tgt_off, rhs_off, rhs_edges;
 	std::vector<int2> tgt_ab, pairs;

@@ -51,18 +51,6 @@ constexpr double CELL_MAX = static_cast<double>((1 << CELL_BITS) - 3);   // stor
 
 unsigned gblocks(int64_t n) { return static_cast<unsigned>(ceil_div(n, GB)); }
 
-template <typename T>
-struct Scratch {
-	T* p = nullptr;
-	~Scratch() {
-		if (p) (void)hipFree(p);
-	}
-	nnrt_status alloc(size_t n) {
-		NNRT_HIP(hipMalloc(&p, sizeof(T) * (n ? n : 1)));
-		return NNRT_OK;
-	}
-};
-
 // ---------------------------------------------------------------- erosion ----
 __global__ __launch_bounds__(GB) void k_faces_init(const int64_t* __restrict__ faces, int64_t F, int64_t V, uint8_t* __restrict__ alive,
                                                    int* __restrict__ error_flag) {
@@ -254,41 +242,40 @@ __global__ __launch_bounds__(GB) void k_accepted_by_priority(const float4* __res
 }
 
 template <typename In, typename Out>
-nnrt_status select_flagged(In in, const uint8_t* flags, Out out, int64_t* d_count, int64_t n, Scratch<uint8_t>& tmp, size_t& tmp_bytes, hipStream_t s) {
+nnrt_status select_flagged(In in, const uint8_t* flags, Out out, int64_t* d_count, int64_t n, DeviceBuffer<uint8_t>& tmp, size_t& tmp_bytes, hipStream_t s) {
 	size_t bytes = 0;
 	NNRT_HIP(hipcub::DeviceSelect::Flagged(nullptr, bytes, in, flags, out, d_count, static_cast<int>(n), s));
-	if (bytes > tmp_bytes || !tmp.p) {
-		if (tmp.p) {
+	if (bytes > tmp_bytes || !tmp.ptr) {
+		if (tmp.ptr) {
 			NNRT_HIP(hipStreamSynchronize(s));
-			NNRT_HIP(hipFree(tmp.p));
-			tmp.p = nullptr;
+			tmp.release();
 		}
-		nnrt_status st = tmp.alloc(std::max<size_t>(bytes, 1));
+		nnrt_status st = tmp.ensure(std::max<size_t>(bytes, 1));
 		if (st) return st;
 		tmp_bytes = bytes;
 	}
-	NNRT_HIP(hipcub::DeviceSelect::Flagged(tmp.p, bytes, in, flags, out, d_count, static_cast<int>(n), s));
+	NNRT_HIP(hipcub::DeviceSelect::Flagged(tmp.ptr, bytes, in, flags, out, d_count, static_cast<int>(n), s));
 	return NNRT_OK;
 }
 } // namespace
 
 nnrt_status launch_vertex_erosion_mask(int64_t V, const int64_t* faces, int64_t F, int iteration_count, int min_neighbors, uint8_t* mask,
                                        int* error_flag, hipStream_t s) {
-	Scratch<uint8_t> alive;
-	Scratch<int> counts;
+	DeviceBuffer<uint8_t> alive;
+	DeviceBuffer<int> counts;
 	nnrt_status st;
-	if ((st = alive.alloc(F)) || (st = counts.alloc(V))) return st;
+	if ((st = alive.ensure(F)) || (st = counts.ensure(V))) return st;
 	NNRT_HIP(hipMemsetAsync(mask, 0, V, s));
-	k_faces_init<<<gblocks(F), GB, 0, s>>>(faces, F, V, alive.p, error_flag);
+	k_faces_init<<<gblocks(F), GB, 0, s>>>(faces, F, V, alive.ptr, error_flag);
 	NNRT_LAUNCH_CHECK();
 	for (int i = 0; i < iteration_count; i++) {
-		NNRT_HIP(hipMemsetAsync(counts.p, 0, sizeof(int) * V, s));
-		k_faces_count<<<gblocks(F), GB, 0, s>>>(faces, F, alive.p, counts.p);
+		NNRT_HIP(hipMemsetAsync(counts.ptr, 0, sizeof(int) * V, s));
+		k_faces_count<<<gblocks(F), GB, 0, s>>>(faces, F, alive.ptr, counts.ptr);
 		NNRT_LAUNCH_CHECK();
-		k_faces_cull<<<gblocks(F), GB, 0, s>>>(faces, F, counts.p, min_neighbors, alive.p);
+		k_faces_cull<<<gblocks(F), GB, 0, s>>>(faces, F, counts.ptr, min_neighbors, alive.ptr);
 		NNRT_LAUNCH_CHECK();
 	}
-	k_faces_mark<<<gblocks(F), GB, 0, s>>>(faces, F, alive.p, mask);
+	k_faces_mark<<<gblocks(F), GB, 0, s>>>(faces, F, alive.ptr, mask);
 	NNRT_LAUNCH_CHECK();
 	NNRT_HIP(hipStreamSynchronize(s));   // the scratch is freed on return
 	return NNRT_OK;
@@ -298,21 +285,21 @@ nnrt_status launch_sample_nodes(const float* pts, int64_t V, const uint8_t* mask
                                 int64_t* h_count, int32_t* h_rounds, hipStream_t s) {
 	*h_count = 0;
 	if (h_rounds) *h_rounds = 0;
-	Scratch<int64_t> vertex, cand, d_count;
-	Scratch<uint8_t> flags, tmp;
-	Scratch<int> ctrl;
+	DeviceBuffer<int64_t> vertex, cand, d_count;
+	DeviceBuffer<uint8_t> flags, tmp;
+	DeviceBuffer<int> ctrl;
 	size_t tmp_bytes = 0;
 	nnrt_status st;
-	if ((st = vertex.alloc(V)) || (st = cand.alloc(V)) || (st = d_count.alloc(1)) || (st = flags.alloc(V)) || (st = ctrl.alloc(4))) return st;
-	NNRT_HIP(hipMemsetAsync(ctrl.p, 0, 4 * sizeof(int), s));
-	k_candidate_flags<<<gblocks(V), GB, 0, s>>>(pts, V, mask, order, vertex.p, flags.p, ctrl.p);
+	if ((st = vertex.ensure(V)) || (st = cand.ensure(V)) || (st = d_count.ensure(1)) || (st = flags.ensure(V)) || (st = ctrl.ensure(4))) return st;
+	NNRT_HIP(hipMemsetAsync(ctrl.ptr, 0, 4 * sizeof(int), s));
+	k_candidate_flags<<<gblocks(V), GB, 0, s>>>(pts, V, mask, order, vertex.ptr, flags.ptr, ctrl.ptr);
 	NNRT_LAUNCH_CHECK();
 	// stable compaction: a candidate's priority is its position in `cand`
-	if ((st = select_flagged(vertex.p, flags.p, cand.p, d_count.p, V, tmp, tmp_bytes, s))) return st;
+	if ((st = select_flagged(vertex.ptr, flags.ptr, cand.ptr, d_count.ptr, V, tmp, tmp_bytes, s))) return st;
 	int64_t M64 = 0;
 	int err = 0;
-	NNRT_HIP(hipMemcpyAsync(&M64, d_count.p, sizeof(int64_t), hipMemcpyDeviceToHost, s));
-	NNRT_HIP(hipMemcpyAsync(&err, ctrl.p, sizeof(int), hipMemcpyDeviceToHost, s));
+	NNRT_HIP(hipMemcpyAsync(&M64, d_count.ptr, sizeof(int64_t), hipMemcpyDeviceToHost, s));
+	NNRT_HIP(hipMemcpyAsync(&err, ctrl.ptr, sizeof(int), hipMemcpyDeviceToHost, s));
 	NNRT_HIP(hipStreamSynchronize(s));
 	if (err & ERR_ORDER_RANGE) {
 		set_error("invalid argument: d_order holds an index outside [0, point_count)");
@@ -321,31 +308,31 @@ nnrt_status launch_sample_nodes(const float* pts, int64_t V, const uint8_t* mask
 	const int M = static_cast<int>(M64);
 	if (M == 0) return NNRT_OK;
 
-	Scratch<unsigned> lo;
-	Scratch<uint64_t> keys, keys_sorted;
-	Scratch<int> prio, prio_sorted, list_a, list_b;
-	Scratch<float4> pos;
-	Scratch<uint8_t> state, still, sort_tmp;
-	Scratch<int2> runs;
-	if ((st = lo.alloc(4)) || (st = keys.alloc(M)) || (st = keys_sorted.alloc(M)) || (st = prio.alloc(M)) || (st = prio_sorted.alloc(M)) ||
-	    (st = list_a.alloc(M)) || (st = list_b.alloc(M)) || (st = pos.alloc(M)) || (st = state.alloc(M)) || (st = still.alloc(M)) ||
-	    (st = runs.alloc(9 * static_cast<size_t>(M))))
+	DeviceBuffer<unsigned> lo;
+	DeviceBuffer<uint64_t> keys, keys_sorted;
+	DeviceBuffer<int> prio, prio_sorted, list_a, list_b;
+	DeviceBuffer<float4> pos;
+	DeviceBuffer<uint8_t> state, still, sort_tmp;
+	DeviceBuffer<int2> runs;
+	if ((st = lo.ensure(4)) || (st = keys.ensure(M)) || (st = keys_sorted.ensure(M)) || (st = prio.ensure(M)) || (st = prio_sorted.ensure(M)) ||
+	    (st = list_a.ensure(M)) || (st = list_b.ensure(M)) || (st = pos.ensure(M)) || (st = state.ensure(M)) || (st = still.ensure(M)) ||
+	    (st = runs.ensure(9 * static_cast<size_t>(M))))
 		return st;
-	NNRT_HIP(hipMemsetAsync(lo.p, 0xff, 4 * sizeof(unsigned), s));
-	k_bbox_min<<<gblocks(M), GB, 0, s>>>(pts, cand.p, M, lo.p);
+	NNRT_HIP(hipMemsetAsync(lo.ptr, 0xff, 4 * sizeof(unsigned), s));
+	k_bbox_min<<<gblocks(M), GB, 0, s>>>(pts, cand.ptr, M, lo.ptr);
 	NNRT_LAUNCH_CHECK();
 	const double edge = static_cast<double>(coverage) * CELL_MARGIN;
-	k_cell_keys<<<gblocks(M), GB, 0, s>>>(pts, cand.p, M, lo.p, edge, keys.p, prio.p, ctrl.p);
+	k_cell_keys<<<gblocks(M), GB, 0, s>>>(pts, cand.ptr, M, lo.ptr, edge, keys.ptr, prio.ptr, ctrl.ptr);
 	NNRT_LAUNCH_CHECK();
 	size_t sort_bytes = 0;
-	NNRT_HIP(hipcub::DeviceRadixSort::SortPairs(nullptr, sort_bytes, keys.p, keys_sorted.p, prio.p, prio_sorted.p, M, 0, 3 * CELL_BITS, s));
-	if ((st = sort_tmp.alloc(std::max<size_t>(sort_bytes, 1)))) return st;
-	NNRT_HIP(hipcub::DeviceRadixSort::SortPairs(sort_tmp.p, sort_bytes, keys.p, keys_sorted.p, prio.p, prio_sorted.p, M, 0, 3 * CELL_BITS, s));
-	k_gather_sorted<<<gblocks(M), GB, 0, s>>>(pts, cand.p, prio_sorted.p, M, pos.p, state.p, list_a.p);
+	NNRT_HIP(hipcub::DeviceRadixSort::SortPairs(nullptr, sort_bytes, keys.ptr, keys_sorted.ptr, prio.ptr, prio_sorted.ptr, M, 0, 3 * CELL_BITS, s));
+	if ((st = sort_tmp.ensure(std::max<size_t>(sort_bytes, 1)))) return st;
+	NNRT_HIP(hipcub::DeviceRadixSort::SortPairs(sort_tmp.ptr, sort_bytes, keys.ptr, keys_sorted.ptr, prio.ptr, prio_sorted.ptr, M, 0, 3 * CELL_BITS, s));
+	k_gather_sorted<<<gblocks(M), GB, 0, s>>>(pts, cand.ptr, prio_sorted.ptr, M, pos.ptr, state.ptr, list_a.ptr);
 	NNRT_LAUNCH_CHECK();
-	k_cell_runs<<<gblocks(M), GB, 0, s>>>(keys_sorted.p, M, runs.p);
+	k_cell_runs<<<gblocks(M), GB, 0, s>>>(keys_sorted.ptr, M, runs.ptr);
 	NNRT_LAUNCH_CHECK();
-	NNRT_HIP(hipMemcpyAsync(&err, ctrl.p, sizeof(int), hipMemcpyDeviceToHost, s));
+	NNRT_HIP(hipMemcpyAsync(&err, ctrl.ptr, sizeof(int), hipMemcpyDeviceToHost, s));
 	NNRT_HIP(hipStreamSynchronize(s));
 	if (err & ERR_GRID_EXTENT) {
 		set_error("invalid argument: the candidates' extent exceeds 2^21 - 3 cells of node_coverage along an axis");
@@ -353,20 +340,20 @@ nnrt_status launch_sample_nodes(const float* pts, int64_t V, const uint8_t* mask
 	}
 
 	const float coverage_sq = coverage * coverage;
-	int* list = list_a.p;
-	int* next = list_b.p;
+	int* list = list_a.ptr;
+	int* next = list_b.ptr;
 	int undecided = M, rounds = 0;
 	while (undecided > 0) {
 		if (rounds >= M) {
 			set_error("internal error: node sampling did not reach its fixed point within one round per candidate");
 			return NNRT_ERROR_INTERNAL;
 		}
-		k_round<<<gblocks(undecided), GB, 0, s>>>(list, undecided, pos.p, state.p, runs.p, M, coverage_sq, still.p);
+		k_round<<<gblocks(undecided), GB, 0, s>>>(list, undecided, pos.ptr, state.ptr, runs.ptr, M, coverage_sq, still.ptr);
 		NNRT_LAUNCH_CHECK();
 		rounds++;
-		if ((st = select_flagged(list, still.p, next, d_count.p, undecided, tmp, tmp_bytes, s))) return st;
+		if ((st = select_flagged(list, still.ptr, next, d_count.ptr, undecided, tmp, tmp_bytes, s))) return st;
 		int64_t left = 0;
-		NNRT_HIP(hipMemcpyAsync(&left, d_count.p, sizeof(int64_t), hipMemcpyDeviceToHost, s));
+		NNRT_HIP(hipMemcpyAsync(&left, d_count.ptr, sizeof(int64_t), hipMemcpyDeviceToHost, s));
 		NNRT_HIP(hipStreamSynchronize(s));
 		if (left >= undecided) {
 			set_error("internal error: a node sampling round decided no candidate");
@@ -376,10 +363,10 @@ nnrt_status launch_sample_nodes(const float* pts, int64_t V, const uint8_t* mask
 		std::swap(list, next);
 	}
 	// `flags` (capacity V >= M) is free again: accepted flag per priority, then the vertices in priority order
-	k_accepted_by_priority<<<gblocks(M), GB, 0, s>>>(pos.p, state.p, M, flags.p);
+	k_accepted_by_priority<<<gblocks(M), GB, 0, s>>>(pos.ptr, state.ptr, M, flags.ptr);
 	NNRT_LAUNCH_CHECK();
-	if ((st = select_flagged(cand.p, flags.p, out, d_count.p, M, tmp, tmp_bytes, s))) return st;
-	NNRT_HIP(hipMemcpyAsync(h_count, d_count.p, sizeof(int64_t), hipMemcpyDeviceToHost, s));
+	if ((st = select_flagged(cand.ptr, flags.ptr, out, d_count.ptr, M, tmp, tmp_bytes, s))) return st;
+	NNRT_HIP(hipMemcpyAsync(h_count, d_count.ptr, sizeof(int64_t), hipMemcpyDeviceToHost, s));
 	NNRT_HIP(hipStreamSynchronize(s));
 	if (h_rounds) *h_rounds = rounds;
 	return NNRT_OK;

@@ -206,18 +206,6 @@ __global__ __launch_bounds__(HB) void k_node_coverage(const float* __restrict__ 
 	out[i] = d * d;
 }
 
-template <typename T>
-struct Scratch {
-	T* p = nullptr;
-	~Scratch() {
-		if (p) (void)hipFree(p);
-	}
-	nnrt_status alloc(size_t n) {
-		NNRT_HIP(hipMalloc(&p, sizeof(T) * (n ? n : 1)));
-		return NNRT_OK;
-	}
-};
-
 unsigned blocks(int n) { return static_cast<unsigned>(ceil_div(n, HB)); }
 } // namespace
 
@@ -228,19 +216,19 @@ public:
 		const int n = static_cast<int>(pts.size() / 3);
 		flags.assign(n, 0);
 		if (n == 0) return NNRT_OK;
-		Scratch<float> d_pts, d_sums;
-		Scratch<int4> d_keys;
-		Scratch<uint8_t> d_flags;
+		DeviceBuffer<float> d_pts, d_sums;
+		DeviceBuffer<int4> d_keys;
+		DeviceBuffer<uint8_t> d_flags;
 		nnrt_status st;
-		if ((st = d_pts.alloc(3 * static_cast<size_t>(n))) || (st = d_sums.alloc(n)) || (st = d_keys.alloc(n)) || (st = d_flags.alloc(n))) return st;
-		NNRT_HIP(hipMemcpy(d_pts.p, pts.data(), sizeof(float) * pts.size(), hipMemcpyHostToDevice));
-		k_grid_keys<<<blocks(n), HB>>>(d_pts.p, n, cell, d_keys.p);
+		if ((st = d_pts.ensure(3 * static_cast<size_t>(n))) || (st = d_sums.ensure(n)) || (st = d_keys.ensure(n)) || (st = d_flags.ensure(n))) return st;
+		NNRT_HIP(hipMemcpy(d_pts.ptr, pts.data(), sizeof(float) * pts.size(), hipMemcpyHostToDevice));
+		k_grid_keys<<<blocks(n), HB>>>(d_pts.ptr, n, cell, d_keys.ptr);
 		NNRT_LAUNCH_CHECK();
-		k_medoid_sums<<<blocks(n), HB>>>(d_pts.p, d_keys.p, n, d_sums.p);
+		k_medoid_sums<<<blocks(n), HB>>>(d_pts.ptr, d_keys.ptr, n, d_sums.ptr);
 		NNRT_LAUNCH_CHECK();
-		k_medoid_flags<<<blocks(n), HB>>>(d_sums.p, d_keys.p, n, d_flags.p);
+		k_medoid_flags<<<blocks(n), HB>>>(d_sums.ptr, d_keys.ptr, n, d_flags.ptr);
 		NNRT_LAUNCH_CHECK();
-		NNRT_HIP(hipMemcpy(flags.data(), d_flags.p, n, hipMemcpyDeviceToHost));
+		NNRT_HIP(hipMemcpy(flags.data(), d_flags.ptr, n, hipMemcpyDeviceToHost));
 		return NNRT_OK;
 	}
 	nnrt_status knn_rows(const std::vector<float>& fine, const std::vector<float>& coarse, int k, std::vector<int32_t>& rows) override {
@@ -248,15 +236,15 @@ public:
 		const int ns = static_cast<int>(fine.size() / 3), nc = static_cast<int>(coarse.size() / 3);
 		rows.assign(static_cast<size_t>(ns) * k, -1);
 		if (ns == 0) return NNRT_OK;
-		Scratch<float> d_f, d_c;
-		Scratch<int32_t> d_rows;
+		DeviceBuffer<float> d_f, d_c;
+		DeviceBuffer<int32_t> d_rows;
 		nnrt_status st;
-		if ((st = d_f.alloc(fine.size())) || (st = d_c.alloc(coarse.size())) || (st = d_rows.alloc(rows.size()))) return st;
-		NNRT_HIP(hipMemcpy(d_f.p, fine.data(), sizeof(float) * fine.size(), hipMemcpyHostToDevice));
-		if (nc > 0) NNRT_HIP(hipMemcpy(d_c.p, coarse.data(), sizeof(float) * coarse.size(), hipMemcpyHostToDevice));
-		k_knn_rows<<<blocks(ns), HB>>>(d_f.p, ns, d_c.p, nc, k, d_rows.p);
+		if ((st = d_f.ensure(fine.size())) || (st = d_c.ensure(coarse.size())) || (st = d_rows.ensure(rows.size()))) return st;
+		NNRT_HIP(hipMemcpy(d_f.ptr, fine.data(), sizeof(float) * fine.size(), hipMemcpyHostToDevice));
+		if (nc > 0) NNRT_HIP(hipMemcpy(d_c.ptr, coarse.data(), sizeof(float) * coarse.size(), hipMemcpyHostToDevice));
+		k_knn_rows<<<blocks(ns), HB>>>(d_f.ptr, ns, d_c.ptr, nc, k, d_rows.ptr);
 		NNRT_LAUNCH_CHECK();
-		NNRT_HIP(hipMemcpy(rows.data(), d_rows.p, sizeof(int32_t) * rows.size(), hipMemcpyDeviceToHost));
+		NNRT_HIP(hipMemcpy(rows.data(), d_rows.ptr, sizeof(int32_t) * rows.size(), hipMemcpyDeviceToHost));
 		return NNRT_OK;
 	}
 	nnrt_status coverage_weights(const float* nodes, int n, float coverage, std::vector<float>& out) override {
@@ -266,13 +254,13 @@ public:
 			return NNRT_OK;
 		}
 		if (n == 0) return NNRT_OK;
-		Scratch<float> d_n, d_out;
+		DeviceBuffer<float> d_n, d_out;
 		nnrt_status st;
-		if ((st = d_n.alloc(3 * static_cast<size_t>(n))) || (st = d_out.alloc(n))) return st;
-		NNRT_HIP(hipMemcpy(d_n.p, nodes, sizeof(float) * 3 * n, hipMemcpyHostToDevice));
-		k_node_coverage<<<blocks(n), HB>>>(d_n.p, n, d_out.p);
+		if ((st = d_n.ensure(3 * static_cast<size_t>(n))) || (st = d_out.ensure(n))) return st;
+		NNRT_HIP(hipMemcpy(d_n.ptr, nodes, sizeof(float) * 3 * n, hipMemcpyHostToDevice));
+		k_node_coverage<<<blocks(n), HB>>>(d_n.ptr, n, d_out.ptr);
 		NNRT_LAUNCH_CHECK();
-		NNRT_HIP(hipMemcpy(out.data(), d_out.p, sizeof(float) * n, hipMemcpyDeviceToHost));
+		NNRT_HIP(hipMemcpy(out.data(), d_out.ptr, sizeof(float) * n, hipMemcpyDeviceToHost));
 		return NNRT_OK;
 	}
 };
@@ -283,25 +271,25 @@ public:
 nnrt_status launch_median_grid_subsample(const float* pts, int n, float cell, int64_t* out, int64_t* h_count, hipStream_t s) {
 	*h_count = 0;
 	if (n == 0) return NNRT_OK;
-	Scratch<float> d_sums;
-	Scratch<int4> d_keys;
-	Scratch<uint8_t> d_flags;
-	Scratch<int64_t> d_count;
+	DeviceBuffer<float> d_sums;
+	DeviceBuffer<int4> d_keys;
+	DeviceBuffer<uint8_t> d_flags;
+	DeviceBuffer<int64_t> d_count;
 	nnrt_status st;
-	if ((st = d_sums.alloc(n)) || (st = d_keys.alloc(n)) || (st = d_flags.alloc(n)) || (st = d_count.alloc(1))) return st;
-	k_grid_keys<<<blocks(n), HB, 0, s>>>(pts, n, cell, d_keys.p);
+	if ((st = d_sums.ensure(n)) || (st = d_keys.ensure(n)) || (st = d_flags.ensure(n)) || (st = d_count.ensure(1))) return st;
+	k_grid_keys<<<blocks(n), HB, 0, s>>>(pts, n, cell, d_keys.ptr);
 	NNRT_LAUNCH_CHECK();
-	k_medoid_sums<<<blocks(n), HB, 0, s>>>(pts, d_keys.p, n, d_sums.p);
+	k_medoid_sums<<<blocks(n), HB, 0, s>>>(pts, d_keys.ptr, n, d_sums.ptr);
 	NNRT_LAUNCH_CHECK();
-	k_medoid_flags<<<blocks(n), HB, 0, s>>>(d_sums.p, d_keys.p, n, d_flags.p);
+	k_medoid_flags<<<blocks(n), HB, 0, s>>>(d_sums.ptr, d_keys.ptr, n, d_flags.ptr);
 	NNRT_LAUNCH_CHECK();
 	hipcub::CountingInputIterator<int64_t> idx(0);
 	size_t bytes = 0;
-	NNRT_HIP(hipcub::DeviceSelect::Flagged(nullptr, bytes, idx, d_flags.p, out, d_count.p, n, s));
-	Scratch<uint8_t> tmp;
-	if ((st = tmp.alloc(std::max<size_t>(bytes, 1)))) return st;
-	NNRT_HIP(hipcub::DeviceSelect::Flagged(tmp.p, bytes, idx, d_flags.p, out, d_count.p, n, s));
-	NNRT_HIP(hipMemcpyAsync(h_count, d_count.p, sizeof(int64_t), hipMemcpyDeviceToHost, s));
+	NNRT_HIP(hipcub::DeviceSelect::Flagged(nullptr, bytes, idx, d_flags.ptr, out, d_count.ptr, n, s));
+	DeviceBuffer<uint8_t> tmp;
+	if ((st = tmp.ensure(std::max<size_t>(bytes, 1)))) return st;
+	NNRT_HIP(hipcub::DeviceSelect::Flagged(tmp.ptr, bytes, idx, d_flags.ptr, out, d_count.ptr, n, s));
+	NNRT_HIP(hipMemcpyAsync(h_count, d_count.ptr, sizeof(int64_t), hipMemcpyDeviceToHost, s));
 	NNRT_HIP(hipStreamSynchronize(s));
 	return NNRT_OK;
 }

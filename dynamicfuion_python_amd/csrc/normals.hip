@@ -152,16 +152,16 @@ nnrt_status nnrt_compute_triangle_normals(const float* d_vertices, int64_t verte
 	if (face_count == 0) return NNRT_OK;
 	NNRT_CHECK_ARG(d_vertices && d_faces && d_out && face_count > 0 && vertex_count >= 0, "invalid arguments");
 	hipStream_t s = static_cast<hipStream_t>(stream);
-	int* flag = nullptr;
-	NNRT_HIP(hipMallocAsync(reinterpret_cast<void**>(&flag), sizeof(int), s));
-	NNRT_HIP(hipMemsetAsync(flag, 0, sizeof(int), s));
+	StreamScratch<int> flag;
+	nnrt_status st = flag.alloc(1, s);
+	if (st) return st;
+	NNRT_HIP(hipMemsetAsync(flag.ptr, 0, sizeof(int), s));
 	k_triangle_normals<<<static_cast<unsigned>(ceil_div(face_count, 256)), 256, 0, s>>>(d_vertices, vertex_count, d_faces, face_count, normalized,
-	                                                                                    d_out, flag);
+	                                                                                    d_out, flag.ptr);
 	hipError_t le = hipGetLastError();
 	int host_flag = 0;
-	hipError_t ce = hipMemcpyAsync(&host_flag, flag, sizeof(int), hipMemcpyDeviceToHost, s);
-	hipError_t se = hipStreamSynchronize(s);
-	hipFreeAsync(flag, s);
+	hipError_t ce = hipMemcpyAsync(&host_flag, flag.ptr, sizeof(int), hipMemcpyDeviceToHost, s);
+	hipError_t se = hipStreamSynchronize(s);   // also on an error: host_flag outlives the copy
 	NNRT_HIP(le);
 	NNRT_HIP(ce);
 	NNRT_HIP(se);
@@ -177,22 +177,21 @@ nnrt_status nnrt_compute_vertex_normals(const float* d_vertices, int64_t vertex_
 	NNRT_CHECK_ARG(d_vertices && d_out && vertex_count >= 0 && face_count >= 0 && (face_count == 0 || d_faces), "invalid arguments");
 	if (vertex_count == 0) return NNRT_OK;
 	hipStream_t s = static_cast<hipStream_t>(stream);
-	int *count = nullptr, *offsets = nullptr, *list = nullptr, *flag = nullptr;
+	StreamScratch<int> count, offsets, list, flag;
 	const int64_t V = vertex_count, n3 = 3 * face_count;
-	NNRT_HIP(hipMallocAsync(reinterpret_cast<void**>(&count), sizeof(int) * V, s));
-	NNRT_HIP(hipMallocAsync(reinterpret_cast<void**>(&offsets), sizeof(int) * (V + 1), s));
-	NNRT_HIP(hipMallocAsync(reinterpret_cast<void**>(&list), sizeof(int) * (n3 > 0 ? n3 : 1), s));
-	NNRT_HIP(hipMallocAsync(reinterpret_cast<void**>(&flag), sizeof(int), s));
-	NNRT_HIP(hipMemsetAsync(count, 0, sizeof(int) * V, s));
-	NNRT_HIP(hipMemsetAsync(flag, 0, sizeof(int), s));
-	if (n3 > 0) k_vertex_face_count<<<static_cast<unsigned>(ceil_div(n3, 256)), 256, 0, s>>>(d_faces, face_count, V, count, flag);
+	nnrt_status st;
+	if ((st = count.alloc(static_cast<size_t>(V), s)) || (st = offsets.alloc(static_cast<size_t>(V) + 1, s)) ||
+	    (st = list.alloc(static_cast<size_t>(n3), s)) || (st = flag.alloc(1, s)))
+		return st;
+	NNRT_HIP(hipMemsetAsync(count.ptr, 0, sizeof(int) * V, s));
+	NNRT_HIP(hipMemsetAsync(flag.ptr, 0, sizeof(int), s));
+	if (n3 > 0) k_vertex_face_count<<<static_cast<unsigned>(ceil_div(n3, 256)), 256, 0, s>>>(d_faces, face_count, V, count.ptr, flag.ptr);
 	{   // validate every index before anything gathers through the faces (the fill and the sums index by them)
 		hipError_t le = hipGetLastError();
 		int host_flag = 0;
-		hipError_t ce = hipMemcpyAsync(&host_flag, flag, sizeof(int), hipMemcpyDeviceToHost, s);
+		hipError_t ce = hipMemcpyAsync(&host_flag, flag.ptr, sizeof(int), hipMemcpyDeviceToHost, s);
 		hipError_t se = hipStreamSynchronize(s);
 		if (le != hipSuccess || ce != hipSuccess || se != hipSuccess || host_flag) {
-			for (void* p : {static_cast<void*>(count), static_cast<void*>(offsets), static_cast<void*>(list), static_cast<void*>(flag)}) hipFreeAsync(p, s);
 			NNRT_HIP(le);
 			NNRT_HIP(ce);
 			NNRT_HIP(se);
@@ -200,13 +199,12 @@ nnrt_status nnrt_compute_vertex_normals(const float* d_vertices, int64_t vertex_
 			return NNRT_ERROR_ARGUMENT;
 		}
 	}
-	k_exclusive_scan<<<1, 1024, 0, s>>>(count, V, offsets);
-	NNRT_HIP(hipMemsetAsync(count, 0, sizeof(int) * V, s));
-	if (n3 > 0) k_vertex_face_fill<<<static_cast<unsigned>(ceil_div(n3, 256)), 256, 0, s>>>(d_faces, face_count, offsets, count, list);
-	k_vertex_normals<<<static_cast<unsigned>(ceil_div(V, 256)), 256, 0, s>>>(d_vertices, d_faces, V, offsets, list, normalized, d_out);
+	k_exclusive_scan<<<1, 1024, 0, s>>>(count.ptr, V, offsets.ptr);
+	NNRT_HIP(hipMemsetAsync(count.ptr, 0, sizeof(int) * V, s));
+	if (n3 > 0) k_vertex_face_fill<<<static_cast<unsigned>(ceil_div(n3, 256)), 256, 0, s>>>(d_faces, face_count, offsets.ptr, count.ptr, list.ptr);
+	k_vertex_normals<<<static_cast<unsigned>(ceil_div(V, 256)), 256, 0, s>>>(d_vertices, d_faces, V, offsets.ptr, list.ptr, normalized, d_out);
 	hipError_t le = hipGetLastError();
 	hipError_t se = hipStreamSynchronize(s);
-	for (void* p : {static_cast<void*>(count), static_cast<void*>(offsets), static_cast<void*>(list), static_cast<void*>(flag)}) hipFreeAsync(p, s);
 	NNRT_HIP(le);
 	NNRT_HIP(se);
 	return NNRT_OK;

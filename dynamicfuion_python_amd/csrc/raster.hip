@@ -656,33 +656,29 @@ nnrt_status launch_raster_multi(const float* face_ndc, const uint8_t* mask, int6
                                 int64_t* out_face, float* out_depth, float* out_bary, float* out_dist, hipStream_t stream) {
 	const int64_t P = static_cast<int64_t>(o.H) * o.W;
 	NNRT_CHECK_ARG(P < (int64_t(1) << 31), "image too large");
-	int *counts = nullptr, *offsets = nullptr;
-	int32_t* lists = nullptr;
-	void* tmp = nullptr;
+	StreamScratch<int> counts, offsets;
+	StreamScratch<int32_t> lists;
+	StreamScratch<uint8_t> tmp;
 	size_t tmp_bytes = 0;
-	NNRT_HIP(hipMallocAsync(reinterpret_cast<void**>(&counts), sizeof(int) * (P + 1), stream));
-	NNRT_HIP(hipMallocAsync(reinterpret_cast<void**>(&offsets), sizeof(int) * (P + 1), stream));
-	NNRT_HIP(hipMemsetAsync(counts, 0, sizeof(int) * (P + 1), stream));
+	nnrt_status st;
+	if ((st = counts.alloc(static_cast<size_t>(P) + 1, stream)) || (st = offsets.alloc(static_cast<size_t>(P) + 1, stream))) return st;
+	NNRT_HIP(hipMemsetAsync(counts.ptr, 0, sizeof(int) * (P + 1), stream));
 	const unsigned fg = static_cast<unsigned>(ceil_div(F > 0 ? F : 1, 256));
-	if (F > 0) k_hit_lists<false><<<fg, 256, 0, stream>>>(face_ndc, mask, F, o, counts, nullptr, nullptr);
+	if (F > 0) k_hit_lists<false><<<fg, 256, 0, stream>>>(face_ndc, mask, F, o, counts.ptr, nullptr, nullptr);
 	NNRT_LAUNCH_CHECK();
-	NNRT_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, tmp_bytes, counts, offsets, static_cast<int>(P + 1), stream));
-	NNRT_HIP(hipMallocAsync(&tmp, tmp_bytes, stream));
-	NNRT_HIP(hipcub::DeviceScan::ExclusiveSum(tmp, tmp_bytes, counts, offsets, static_cast<int>(P + 1), stream));
+	NNRT_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, tmp_bytes, counts.ptr, offsets.ptr, static_cast<int>(P + 1), stream));
+	if ((st = tmp.alloc(tmp_bytes, stream))) return st;
+	NNRT_HIP(hipcub::DeviceScan::ExclusiveSum(tmp.ptr, tmp_bytes, counts.ptr, offsets.ptr, static_cast<int>(P + 1), stream));
 	int total = 0;
-	NNRT_HIP(hipMemcpyAsync(&total, offsets + P, sizeof(int), hipMemcpyDeviceToHost, stream));
-	NNRT_HIP(hipMemsetAsync(counts, 0, sizeof(int) * (P + 1), stream));
+	NNRT_HIP(hipMemcpyAsync(&total, offsets.ptr + P, sizeof(int), hipMemcpyDeviceToHost, stream));
+	NNRT_HIP(hipMemsetAsync(counts.ptr, 0, sizeof(int) * (P + 1), stream));
 	NNRT_HIP(hipStreamSynchronize(stream));
-	NNRT_HIP(hipMallocAsync(reinterpret_cast<void**>(&lists), sizeof(int32_t) * (total > 0 ? total : 1), stream));
-	if (F > 0) k_hit_lists<true><<<fg, 256, 0, stream>>>(face_ndc, mask, F, o, counts, offsets, lists);
+	if ((st = lists.alloc(static_cast<size_t>(total > 0 ? total : 1), stream))) return st;
+	if (F > 0) k_hit_lists<true><<<fg, 256, 0, stream>>>(face_ndc, mask, F, o, counts.ptr, offsets.ptr, lists.ptr);
 	NNRT_LAUNCH_CHECK();
-	k_hit_resolve<<<static_cast<unsigned>(ceil_div(P, 256)), 256, 0, stream>>>(face_ndc, o, faces_per_pixel, offsets, lists, out_face, out_depth,
+	k_hit_resolve<<<static_cast<unsigned>(ceil_div(P, 256)), 256, 0, stream>>>(face_ndc, o, faces_per_pixel, offsets.ptr, lists.ptr, out_face, out_depth,
 	                                                                          out_bary, out_dist);
 	NNRT_LAUNCH_CHECK();
-	NNRT_HIP(hipFreeAsync(counts, stream));
-	NNRT_HIP(hipFreeAsync(offsets, stream));
-	NNRT_HIP(hipFreeAsync(lists, stream));
-	NNRT_HIP(hipFreeAsync(tmp, stream));
 	return NNRT_OK;
 }
 

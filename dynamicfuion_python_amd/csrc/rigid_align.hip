@@ -223,9 +223,9 @@ nnrt_status launch_rigid_align(const float* points, const float* normals, int64_
 	const int G = static_cast<int>(std::min<int64_t>(ceil_div(V, RA_BLOCK), RA_MAX_BLOCKS));   // from V alone: reproducible sums
 	const size_t row_bytes = sizeof(double) * RA_SUMS * G, log_bytes = sizeof(double) * 2 * iterations;
 	// one allocation: rows [G, 29], pose [12], log [iterations, 2] (doubles), then the status word
-	char* work = nullptr;
-	NNRT_HIP(hipMallocAsync(reinterpret_cast<void**>(&work), row_bytes + sizeof(double) * 12 + log_bytes + sizeof(int32_t), stream));
-	double* rows = reinterpret_cast<double*>(work);
+	StreamScratch<char> work;
+	if (nnrt_status st = work.alloc(row_bytes + sizeof(double) * 12 + log_bytes + sizeof(int32_t), stream)) return st;
+	double* rows = reinterpret_cast<double*>(work.ptr);
 	double* pose = rows + static_cast<size_t>(RA_SUMS) * G;
 	double* log = pose + 12;
 	int32_t* status = reinterpret_cast<int32_t*>(log + 2 * static_cast<size_t>(iterations));
@@ -246,7 +246,6 @@ nnrt_status launch_rigid_align(const float* points, const float* normals, int64_
 	if (e == hipSuccess) e = hipMemcpyAsync(host_log.data(), log, log_bytes, hipMemcpyDeviceToHost, stream);
 	if (e == hipSuccess) e = hipMemcpyAsync(&host_status, status, sizeof(int32_t), hipMemcpyDeviceToHost, stream);
 	const hipError_t se = hipStreamSynchronize(stream);   // also on an error: the host buffers above outlive every copy
-	(void)hipFreeAsync(work, stream);
 	NNRT_HIP(e);
 	NNRT_HIP(se);
 	for (int k = 0; k < 12; k++) h_T_out[k] = host_pose[k];

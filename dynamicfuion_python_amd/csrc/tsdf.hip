@@ -994,30 +994,6 @@ __global__ void k_mc_triangles(MeshGridView m, int64_t nb, const uint8_t* __rest
 // =====================================================================================================================
 namespace nnrt {
 namespace {
-template <typename T>
-struct DevBuf {
-	T* ptr = nullptr;
-	size_t count = 0;
-	nnrt_status ensure(size_t n) {
-		if (n <= count && ptr) return NNRT_OK;
-		if (ptr) hipFree(ptr);
-		ptr = nullptr;
-		count = 0;
-		if (hipMalloc(reinterpret_cast<void**>(&ptr), sizeof(T) * std::max<size_t>(n, 1)) != hipSuccess) {
-			ptr = nullptr;
-			set_error("hipMalloc failed (voxel block grid)");
-			return NNRT_ERROR_HIP;
-		}
-		count = std::max<size_t>(n, 1);
-		return NNRT_OK;
-	}
-	void release() {
-		if (ptr) hipFree(ptr);
-		ptr = nullptr;
-		count = 0;
-	}
-	~DevBuf() { release(); }
-};
 inline unsigned grid_of(int64_t n, int block = 256) { return static_cast<unsigned>((n + block - 1) / block); }
 size_t store_bytes(int type) { return type == ST_F32 ? 4 : type == ST_U16 ? 2 : type == ST_U8 ? 1 : 0; }
 } // namespace
@@ -1033,27 +1009,27 @@ struct nnrt_voxel_grid {
 	int weight_type = ST_F32, color_type = ST_NONE;
 	uint64_t table_size = 0;
 	bool grow_surface = false;   // nnrt_voxel_grid_set_non_rigid_surface_growth
-	DevBuf<float> tsdf;
-	DevBuf<uint8_t> weight, color;
-	DevBuf<int32_t> keys;
-	DevBuf<uint64_t> hkeys;
-	DevBuf<int> hblock, hfirst;
+	DeviceBuffer<float> tsdf;
+	DeviceBuffer<uint8_t> weight, color;
+	DeviceBuffer<int32_t> keys;
+	DeviceBuffer<uint64_t> hkeys;
+	DeviceBuffer<int> hblock, hfirst;
 	// scratch
-	DevBuf<uint64_t> s_slot, s_packed;
-	DevBuf<int> s_flag, s_rank, s_nbr, s_ntri, s_toff, s_vidx, s_eflag, s_found, s_blocks;
-	DevBuf<uint8_t> s_cube, s_mask;
-	DevBuf<unsigned char> s_cub;
-	DevBuf<int32_t> s_coords;
-	DevBuf<float> s_boxes, s_rows_all;
-	DevBuf<Seg> s_segs;
+	DeviceBuffer<uint64_t> s_slot, s_packed;
+	DeviceBuffer<int> s_flag, s_rank, s_nbr, s_ntri, s_toff, s_vidx, s_eflag, s_found, s_blocks;
+	DeviceBuffer<uint8_t> s_cube, s_mask;
+	DeviceBuffer<unsigned char> s_cub;
+	DeviceBuffer<int32_t> s_coords;
+	DeviceBuffer<float> s_boxes, s_rows_all;
+	DeviceBuffer<Seg> s_segs;
 	// results awaiting a copy-out
-	DevBuf<int32_t> r_coords;
+	DeviceBuffer<int32_t> r_coords;
 	int64_t r_coord_count = 0;
-	DevBuf<float> r_rows;
+	DeviceBuffer<float> r_rows;
 	int64_t r_row_count = 0;
 	int r_row_channels = 0;
-	DevBuf<float> r_vpos, r_vnrm, r_vcol;
-	DevBuf<int64_t> r_tris;
+	DeviceBuffer<float> r_vpos, r_vnrm, r_vcol;
+	DeviceBuffer<int64_t> r_tris;
 	int64_t r_nv = 0, r_nt = 0;
 
 	GridView view() {
@@ -1074,15 +1050,6 @@ struct nnrt_voxel_grid {
 };
 
 namespace {
-struct GridGuard {
-	int prev = 0;
-	explicit GridGuard(int dev) {
-		hipGetDevice(&prev);
-		if (prev != dev) hipSetDevice(dev);
-	}
-	~GridGuard() { hipSetDevice(prev); }
-};
-
 // exclusive prefix sum of n ints; returns the total on the host (synchronizes the stream)
 nnrt_status scan_total(nnrt_voxel_grid* vg, const int* in, int* out, int64_t n, hipStream_t s, int64_t* total) {
 	*total = 0;
@@ -1120,17 +1087,13 @@ nnrt_status ensure_capacity(nnrt_voxel_grid* vg, int64_t need, hipStream_t s) {
 	const size_t vox_old = static_cast<size_t>(vg->capacity) * vg->res3, vox_new = static_cast<size_t>(cap) * vg->res3;
 	auto grow = [&](auto& buf, size_t elem_old, size_t elem_new) -> nnrt_status {
 		using T = std::remove_pointer_t<decltype(buf.ptr)>;
-		T* fresh = nullptr;
-		if (hipMalloc(reinterpret_cast<void**>(&fresh), sizeof(T) * std::max<size_t>(elem_new, 1)) != hipSuccess) {
-			set_error("hipMalloc failed growing the voxel block grid");
-			return NNRT_ERROR_HIP;
-		}
-		NNRT_HIP(hipMemsetAsync(fresh, 0, sizeof(T) * elem_new, s));
-		if (buf.ptr && elem_old) NNRT_HIP(hipMemcpyAsync(fresh, buf.ptr, sizeof(T) * elem_old, hipMemcpyDeviceToDevice, s));
+		DeviceBuffer<T> fresh;
+		nnrt_status gs = fresh.ensure(elem_new);
+		if (gs) return gs;
+		NNRT_HIP(hipMemsetAsync(fresh.ptr, 0, sizeof(T) * elem_new, s));
+		if (buf.ptr && elem_old) NNRT_HIP(hipMemcpyAsync(fresh.ptr, buf.ptr, sizeof(T) * elem_old, hipMemcpyDeviceToDevice, s));
 		NNRT_HIP(hipStreamSynchronize(s));
-		buf.release();
-		buf.ptr = fresh;
-		buf.count = std::max<size_t>(elem_new, 1);
+		buf = std::move(fresh);
 		return NNRT_OK;
 	};
 	nnrt_status st;
@@ -1183,8 +1146,8 @@ nnrt_status unique_packed(nnrt_voxel_grid* vg, const uint64_t* packed, int64_t n
 	if (n == 0) return NNRT_OK;
 	uint64_t tsize = 16;
 	while (tsize < static_cast<uint64_t>(2 * n)) tsize <<= 1;
-	DevBuf<uint64_t> tk;
-	DevBuf<int> tb, tf;
+	DeviceBuffer<uint64_t> tk;
+	DeviceBuffer<int> tb, tf;
 	nnrt_status st;
 	if ((st = tk.ensure(tsize)) || (st = tb.ensure(tsize)) || (st = tf.ensure(tsize)) || (st = vg->s_slot.ensure(n)) || (st = vg->s_flag.ensure(n)) ||
 	    (st = vg->s_rank.ensure(n)))
@@ -1242,7 +1205,7 @@ nnrt_status take_error(int* d_error, hipStream_t s) {
 
 nnrt_status activate_coords(nnrt_voxel_grid* vg, const int32_t* d_coords, int64_t n, hipStream_t s) {
 	if (n == 0) return NNRT_OK;
-	DevBuf<int> err;
+	DeviceBuffer<int> err;
 	nnrt_status st;
 	if ((st = err.ensure(1))) return st;
 	NNRT_HIP(hipMemsetAsync(err.ptr, 0, sizeof(int), s));
@@ -1301,7 +1264,7 @@ nnrt_status nnrt_voxel_grid_create(float voxel_size, int32_t block_resolution, i
 	NNRT_CHECK_ARG(color_dtype == NNRT_DTYPE_NONE || color_dtype == NNRT_DTYPE_FLOAT32 || color_dtype == NNRT_DTYPE_UINT16 ||
 	                   color_dtype == NNRT_DTYPE_UINT8,
 	               "color dtype must be none, float32, uint16 or uint8");
-	GridGuard guard(device);
+	DeviceGuard guard(device);
 	std::unique_ptr<nnrt_voxel_grid> vg(new nnrt_voxel_grid());
 	vg->device = device;
 	vg->voxel_size = voxel_size;
@@ -1319,7 +1282,7 @@ nnrt_status nnrt_voxel_grid_create(float voxel_size, int32_t block_resolution, i
 
 void nnrt_voxel_grid_destroy(nnrt_voxel_grid* vg) {
 	if (!vg) return;
-	GridGuard guard(vg->device);
+	DeviceGuard guard(vg->device);
 	hipDeviceSynchronize();
 	delete vg;
 }
@@ -1336,13 +1299,13 @@ nnrt_status nnrt_voxel_grid_get_info(const nnrt_voxel_grid* vg, int64_t* h_activ
 
 nnrt_status nnrt_voxel_grid_activate(nnrt_voxel_grid* vg, const int32_t* d_block_coords, int64_t count, void* stream) {
 	NNRT_CHECK_ARG(vg && (count == 0 || d_block_coords) && count >= 0, "invalid arguments");
-	GridGuard guard(vg->device);
+	DeviceGuard guard(vg->device);
 	return activate_coords(vg, d_block_coords, count, static_cast<hipStream_t>(stream));
 }
 
 nnrt_status nnrt_voxel_grid_get_block_coordinates(const nnrt_voxel_grid* vg, int32_t* d_out, void* stream) {
 	NNRT_CHECK_ARG(vg && d_out, "invalid arguments");
-	GridGuard guard(vg->device);
+	DeviceGuard guard(vg->device);
 	if (vg->active) NNRT_HIP(hipMemcpyAsync(d_out, vg->keys.ptr, sizeof(int32_t) * 3 * vg->active, hipMemcpyDeviceToDevice, static_cast<hipStream_t>(stream)));
 	return NNRT_OK;
 }
@@ -1352,7 +1315,7 @@ nnrt_status nnrt_voxel_grid_unique_block_coordinates(nnrt_voxel_grid* vg, const 
                                                      float trunc_voxel_multiplier, int64_t* h_count, void* stream) {
 	NNRT_CHECK_ARG(vg && d_depth && h_K && h_count && height > 0 && width > 0, "invalid arguments");
 	NNRT_CHECK_ARG(depth_dtype == NNRT_DTYPE_UINT16 || depth_dtype == NNRT_DTYPE_FLOAT32, "depth must be uint16 or float32");
-	GridGuard guard(vg->device);
+	DeviceGuard guard(vg->device);
 	hipStream_t s = static_cast<hipStream_t>(stream);
 	double Einv[16];
 	static const double I4[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
@@ -1375,7 +1338,7 @@ nnrt_status nnrt_voxel_grid_unique_block_coordinates(nnrt_voxel_grid* vg, const 
 
 nnrt_status nnrt_voxel_grid_copy_result_coordinates(const nnrt_voxel_grid* vg, int32_t* d_out, void* stream) {
 	NNRT_CHECK_ARG(vg && (d_out || vg->r_coord_count == 0), "invalid arguments");
-	GridGuard guard(vg->device);
+	DeviceGuard guard(vg->device);
 	if (vg->r_coord_count)
 		NNRT_HIP(hipMemcpyAsync(d_out, vg->r_coords.ptr, sizeof(int32_t) * 3 * vg->r_coord_count, hipMemcpyDeviceToDevice, static_cast<hipStream_t>(stream)));
 	return NNRT_OK;
@@ -1387,7 +1350,7 @@ nnrt_status nnrt_voxel_grid_integrate(nnrt_voxel_grid* vg, const int32_t* d_bloc
                                       float trunc_voxel_multiplier, void* stream) {
 	NNRT_CHECK_ARG(vg && d_depth && h_depth_K && height > 0 && width > 0 && count >= 0 && (count == 0 || d_block_coords), "invalid arguments");
 	NNRT_CHECK_ARG(depth_dtype == NNRT_DTYPE_UINT16 || depth_dtype == NNRT_DTYPE_FLOAT32, "depth must be uint16 or float32");
-	GridGuard guard(vg->device);
+	DeviceGuard guard(vg->device);
 	hipStream_t s = static_cast<hipStream_t>(stream);
 	nnrt_status st;
 	if ((st = activate_coords(vg, d_block_coords, count, s))) return st;
@@ -1418,7 +1381,7 @@ nnrt_status nnrt_voxel_grid_integrate_non_rigid(nnrt_voxel_grid* vg, const int32
 	                   (count == 0 || d_block_coords),
 	               "invalid arguments");
 	NNRT_CHECK_ARG(depth_dtype == NNRT_DTYPE_UINT16 || depth_dtype == NNRT_DTYPE_FLOAT32, "depth must be uint16 or float32");
-	GridGuard guard(vg->device);
+	DeviceGuard guard(vg->device);
 	hipStream_t s = static_cast<hipStream_t>(stream);
 	nnrt_status st;
 	if ((st = activate_coords(vg, d_block_coords, count, s))) return st;
@@ -1458,7 +1421,7 @@ nnrt_status nnrt_voxel_grid_integrate_non_rigid(nnrt_voxel_grid* vg, const int32
 
 nnrt_status nnrt_voxel_grid_extract_voxel_values_and_coordinates(const nnrt_voxel_grid* vg, float* d_out, int32_t* h_channels, void* stream) {
 	NNRT_CHECK_ARG(vg && (d_out || vg->active == 0), "invalid arguments");
-	GridGuard guard(vg->device);
+	DeviceGuard guard(vg->device);
 	if (h_channels) *h_channels = vg->channels();
 	const int64_t n = vg->active * vg->res3;
 	if (n > 0)
@@ -1470,7 +1433,7 @@ nnrt_status nnrt_voxel_grid_extract_voxel_values_and_coordinates(const nnrt_voxe
 nnrt_status nnrt_voxel_grid_extract_voxel_values_at(nnrt_voxel_grid* vg, const int32_t* d_query, int64_t count, int64_t* h_rows, int32_t* h_channels,
                                                     void* stream) {
 	NNRT_CHECK_ARG(vg && h_rows && (count == 0 || d_query) && count >= 0, "invalid arguments");
-	GridGuard guard(vg->device);
+	DeviceGuard guard(vg->device);
 	hipStream_t s = static_cast<hipStream_t>(stream);
 	const int C = vg->channels();
 	if (h_channels) *h_channels = C;
@@ -1497,7 +1460,7 @@ nnrt_status nnrt_voxel_grid_extract_voxel_values_at(nnrt_voxel_grid* vg, const i
 
 nnrt_status nnrt_voxel_grid_copy_result_rows(const nnrt_voxel_grid* vg, float* d_out, void* stream) {
 	NNRT_CHECK_ARG(vg && (d_out || vg->r_row_count == 0), "invalid arguments");
-	GridGuard guard(vg->device);
+	DeviceGuard guard(vg->device);
 	if (vg->r_row_count)
 		NNRT_HIP(hipMemcpyAsync(d_out, vg->r_rows.ptr, sizeof(float) * vg->r_row_count * vg->r_row_channels, hipMemcpyDeviceToDevice,
 		                        static_cast<hipStream_t>(stream)));
@@ -1507,7 +1470,7 @@ nnrt_status nnrt_voxel_grid_copy_result_rows(const nnrt_voxel_grid* vg, float* d
 nnrt_status nnrt_voxel_grid_warped_block_boxes(const nnrt_voxel_grid* vg, const int32_t* d_block_keys, int64_t count, const nnrt_warp_field* wf,
                                                const double* h_E, float* d_boxes, void* stream) {
 	NNRT_CHECK_ARG(vg && wf && (count == 0 || (d_block_keys && d_boxes)) && count >= 0, "invalid arguments");
-	GridGuard guard(vg->device);
+	DeviceGuard guard(vg->device);
 	const WarpFieldView wv = warp_field_view(wf);
 	NNRT_CHECK_ARG(wv.anchor_count >= 1 && wv.anchor_count <= TSDF_MAX_ANCHORS, "anchor_count must be in [1, 8]");
 	if (count == 0) return NNRT_OK;
@@ -1533,14 +1496,13 @@ nnrt_status nnrt_boxes_intersecting_surface_mask(const float* d_boxes, int64_t c
 	hipStream_t s = static_cast<hipStream_t>(stream);
 	if (count == 0) return NNRT_OK;
 	const int64_t nseg = static_cast<int64_t>(height / stride) * (width / stride);
-	Seg* segs = nullptr;
-	NNRT_HIP(hipMallocAsync(reinterpret_cast<void**>(&segs), sizeof(Seg) * std::max<int64_t>(nseg, 1), s));
+	StreamScratch<Seg> segs;
+	nnrt_status st = segs.alloc(static_cast<size_t>(std::max<int64_t>(nseg, 1)), s);
+	if (st) return st;
 	const ImageView im = make_image(d_depth, depth_dtype, height, width, nullptr, 0, 0, depth_scale, depth_max);
-	if (nseg > 0) k_make_segments<<<grid_of(nseg), 256, 0, s>>>(im, stride, make_xform(h_K, nullptr), truncation_distance, segs);
-	k_boxes_mask<<<grid_of(count), 256, 0, s>>>(d_boxes, count, segs, nseg, d_mask);
-	hipError_t le = hipGetLastError();
-	hipFreeAsync(segs, s);
-	NNRT_HIP(le);
+	if (nseg > 0) k_make_segments<<<grid_of(nseg), 256, 0, s>>>(im, stride, make_xform(h_K, nullptr), truncation_distance, segs.ptr);
+	k_boxes_mask<<<grid_of(count), 256, 0, s>>>(d_boxes, count, segs.ptr, nseg, d_mask);
+	NNRT_LAUNCH_CHECK();
 	return NNRT_OK;
 }
 
@@ -1549,7 +1511,7 @@ nnrt_status nnrt_voxel_grid_find_blocks_intersecting_truncation_region(nnrt_voxe
                                                                        float depth_scale, float depth_max, float trunc_voxel_multiplier,
                                                                        int64_t* h_count, void* stream) {
 	NNRT_CHECK_ARG(vg && wf && d_depth && h_K && h_count, "invalid arguments");
-	GridGuard guard(vg->device);
+	DeviceGuard guard(vg->device);
 	hipStream_t s = static_cast<hipStream_t>(stream);
 	int64_t n = 0;
 	nnrt_status st;
@@ -1576,7 +1538,7 @@ nnrt_status nnrt_voxel_grid_find_blocks_intersecting_truncation_region(nnrt_voxe
 
 nnrt_status nnrt_voxel_grid_activate_sleeve_blocks(nnrt_voxel_grid* vg, int64_t* h_count, void* stream) {
 	NNRT_CHECK_ARG(vg && h_count, "invalid arguments");
-	GridGuard guard(vg->device);
+	DeviceGuard guard(vg->device);
 	hipStream_t s = static_cast<hipStream_t>(stream);
 	int64_t n = 0;
 	nnrt_status st;
@@ -1593,7 +1555,7 @@ nnrt_status nnrt_voxel_grid_activate_sleeve_blocks(nnrt_voxel_grid* vg, int64_t*
 nnrt_status nnrt_voxel_grid_extract_triangle_mesh(nnrt_voxel_grid* vg, float weight_threshold, int64_t* h_vertex_count, int64_t* h_triangle_count,
                                                   void* stream) {
 	NNRT_CHECK_ARG(vg && h_vertex_count && h_triangle_count, "invalid arguments");
-	GridGuard guard(vg->device);
+	DeviceGuard guard(vg->device);
 	hipStream_t s = static_cast<hipStream_t>(stream);
 	nnrt_status st;
 	if ((st = upload_mc_tables())) return st;
@@ -1629,7 +1591,7 @@ nnrt_status nnrt_voxel_grid_extract_triangle_mesh(nnrt_voxel_grid* vg, float wei
 
 nnrt_status nnrt_voxel_grid_copy_mesh(const nnrt_voxel_grid* vg, float* d_vertices, float* d_normals, float* d_colors, int64_t* d_triangles, void* stream) {
 	NNRT_CHECK_ARG(vg, "null grid");
-	GridGuard guard(vg->device);
+	DeviceGuard guard(vg->device);
 	hipStream_t s = static_cast<hipStream_t>(stream);
 	const size_t nv = static_cast<size_t>(vg->r_nv), nt = static_cast<size_t>(vg->r_nt);
 	if (nv && d_vertices) NNRT_HIP(hipMemcpyAsync(d_vertices, vg->r_vpos.ptr, sizeof(float) * 3 * nv, hipMemcpyDeviceToDevice, s));

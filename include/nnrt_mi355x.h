@@ -43,6 +43,10 @@ const char* nnrt_last_error(void);
 /* HIP runtime version the library was built against and the number of visible devices (-1 on error). */
 int32_t nnrt_runtime_version(void);
 int32_t nnrt_device_count(void);
+/* Bytes of device memory the library's handles and temporaries hold at this moment, process-wide (diagnostic: a handle
+ * that is destroyed returns what it took, so a leak shows as a count that does not come back; stream-ordered temporaries
+ * leave the count when their entry point returns). */
+int64_t nnrt_device_bytes_in_use(void);
 /* Pixel-node Jacobian arithmetic of this build: 0 = the reference CPU path's unfused expressions (the product), 1 = FMA
  * form (a development build, -DNNRT_JAC_FMA=1). Both are the reference's expression (PixelVertexAnchorJacobiansImpl.h
  * :179-363, WarpedSurfaceJacobiansImpl.h:117-156); the test checker selects its matching mode from this. */
