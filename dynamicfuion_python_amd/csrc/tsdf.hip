@@ -645,7 +645,7 @@ __global__ void k_values_all(GridView g, int64_t nb, int C, float* __restrict__ 
 // The reference indexes the voxel inside its block with the GLOBAL coordinate (CoordToWorkload of x, y, z, :619-620),
 // which is the local index only for block (0, 0, 0); reproduced, rows whose index leaves the voxel storage keep -2.
 // Query blocks are x / res with C++ integer division (toward zero), as the tensor division at :239.
-__global__ void k_values_at(GridView g, int64_t capacity, const int32_t* __restrict__ q, int64_t n, int C, float* __restrict__ out) {
+__global__ void k_values_at(GridView g, int64_t active, const int32_t* __restrict__ q, int64_t n, int C, float* __restrict__ out) {
 	const int64_t i = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
 	if (i >= n) return;
 	float* o = out + i * C;
@@ -655,7 +655,7 @@ __global__ void k_values_at(GridView g, int64_t capacity, const int32_t* __restr
 	if (b < 0) return;
 	const int64_t vib = static_cast<int64_t>(x) + static_cast<int64_t>(g.res) * (y + static_cast<int64_t>(g.res) * z);
 	const int64_t lin = static_cast<int64_t>(b) * g.res3 + vib;
-	if (lin < 0 || lin >= capacity * g.res3) return;
+	if (lin < 0 || lin >= active * g.res3) return;
 	o[0] = static_cast<float>(x) * g.voxel_size;
 	o[1] = static_cast<float>(y) * g.voxel_size;
 	o[2] = static_cast<float>(z) * g.voxel_size;
@@ -1108,6 +1108,18 @@ nnrt_status ensure_capacity(nnrt_voxel_grid* vg, int64_t need, hipStream_t s) {
 	return NNRT_OK;
 }
 
+// check + clear the device error word used by activation (out-of-range block coordinates)
+nnrt_status take_error(int* d_error, hipStream_t s) {
+	int h = 0;
+	NNRT_HIP(hipMemcpyAsync(&h, d_error, sizeof(int), hipMemcpyDeviceToHost, s));
+	NNRT_HIP(hipStreamSynchronize(s));
+	if (h) {
+		set_error("block coordinate out of range (|coordinate| must stay below 2^20)");
+		return NNRT_ERROR_ARGUMENT;
+	}
+	return NNRT_OK;
+}
+
 // Activate (Open3D HashMap::Activate): coordinates [n,3] (or packed keys, HASH_EMPTY entries skipped) -> blocks;
 // `n_new` receives the number of blocks created
 nnrt_status activate_keys(nnrt_voxel_grid* vg, const int32_t* coords, const uint64_t* packed, int64_t n, hipStream_t s, int64_t* n_new,
@@ -1125,6 +1137,12 @@ nnrt_status activate_keys(nnrt_voxel_grid* vg, const int32_t* coords, const uint
 	NNRT_LAUNCH_CHECK();
 	int64_t total = 0;
 	if ((st = scan_total(vg, vg->s_flag.ptr, vg->s_rank.ptr, n, s, &total))) return st;
+	// a call with an out-of-range coordinate is refused as a whole: its in-range keys already sit in the table (without
+	// a block), so the table is rebuilt from the block keys and the grid is as it was before the call
+	if (d_error && (st = take_error(d_error, s))) {
+		const nnrt_status rs = rebuild_table(vg, vg->table_size, s);
+		return rs ? rs : st;
+	}
 	if (total > 0) {
 		k_assign_blocks<<<grid_of(n), 256, 0, s>>>(g.hash, vg->s_slot.ptr, vg->s_flag.ptr, vg->s_rank.ptr, n, vg->active, vg->keys.ptr);
 		NNRT_LAUNCH_CHECK();
@@ -1191,18 +1209,6 @@ int store_type_of(int dtype) {
 	}
 }
 
-// check + clear the device error word used by activation (out-of-range block coordinates)
-nnrt_status take_error(int* d_error, hipStream_t s) {
-	int h = 0;
-	NNRT_HIP(hipMemcpyAsync(&h, d_error, sizeof(int), hipMemcpyDeviceToHost, s));
-	NNRT_HIP(hipStreamSynchronize(s));
-	if (h) {
-		set_error("block coordinate out of range (|coordinate| must stay below 2^20)");
-		return NNRT_ERROR_ARGUMENT;
-	}
-	return NNRT_OK;
-}
-
 nnrt_status activate_coords(nnrt_voxel_grid* vg, const int32_t* d_coords, int64_t n, hipStream_t s) {
 	if (n == 0) return NNRT_OK;
 	DeviceBuffer<int> err;
@@ -1210,8 +1216,7 @@ nnrt_status activate_coords(nnrt_voxel_grid* vg, const int32_t* d_coords, int64_
 	if ((st = err.ensure(1))) return st;
 	NNRT_HIP(hipMemsetAsync(err.ptr, 0, sizeof(int), s));
 	int64_t created = 0;
-	if ((st = activate_keys(vg, d_coords, nullptr, n, s, &created, err.ptr))) return st;
-	return take_error(err.ptr, s);
+	return activate_keys(vg, d_coords, nullptr, n, s, &created, err.ptr);   // reads the error word before it assigns blocks
 }
 
 // inactive neighbours of every active block (neighbour-major, duplicates kept) -> s_coords [27 active, 3] + keep flags
@@ -1444,7 +1449,8 @@ nnrt_status nnrt_voxel_grid_extract_voxel_values_at(nnrt_voxel_grid* vg, const i
 	nnrt_status st;
 	if ((st = vg->s_rows_all.ensure(static_cast<size_t>(count) * C)) || (st = vg->s_found.ensure(count)) || (st = vg->s_rank.ensure(count))) return st;
 	const GridView g = vg->view();
-	k_values_at<<<grid_of(count), 256, 0, s>>>(g, vg->capacity, d_query, count, C, vg->s_rows_all.ptr);
+	// the storage of the active blocks bounds the quirk index: rows do not depend on how far the capacity has grown
+	k_values_at<<<grid_of(count), 256, 0, s>>>(g, vg->active, d_query, count, C, vg->s_rows_all.ptr);
 	k_found_mask<<<grid_of(count), 256, 0, s>>>(g, d_query, count, vg->s_found.ptr);
 	NNRT_LAUNCH_CHECK();
 	int64_t total = 0;

@@ -656,7 +656,8 @@ class OracleGrid:
                                  ctypes.c_float(trunc_mult))
 
     def integrate_non_rigid(self, coords, nodes, R, t, coverage, K, min_valid, depth, color, normals, Kd, Kc, E, scale, dmax, trunc_mult,
-                            node_coverage_sq=None, apply_oblique_test=True):
+                            node_coverage_sq=None, apply_oblique_test=True, grow_surface=False):
+        """grow_surface: the product's growth mode (NonRigidSurfaceVoxelBlockGrid.set_non_rigid_surface_growth)."""
         c = _i32(coords).reshape(-1, 3)
         d, dt = _depth_arg(depth)
         col = None if color is None else np.ascontiguousarray(color, dtype=np.uint8 if dt == 1 else np.float32)
@@ -667,7 +668,8 @@ class OracleGrid:
         lib().orc_grid_integrate_non_rigid(self.h, _p(c), ctypes.c_int64(len(c)), _p(nodes), _p(R), _p(t), _p(c2), len(nodes),
                                            ctypes.c_float(coverage), int(K), int(min_valid), _p(d), dt, d.shape[0], d.shape[1], _p(col), Hc,
                                            Wc, _p(nrm), _p(_f64(Kd)), _p(_f64(Kc)), _p(None if E is None else _f64(E)), ctypes.c_float(scale),
-                                           ctypes.c_float(dmax), ctypes.c_float(trunc_mult), _p(cos), int(bool(apply_oblique_test)))
+                                           ctypes.c_float(dmax), ctypes.c_float(trunc_mult), _p(cos), int(bool(apply_oblique_test)),
+                                           int(bool(grow_surface)))
         return cos
 
     def channels(self):

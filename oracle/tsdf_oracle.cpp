@@ -109,6 +109,10 @@ float store_cast(int dt, float v) {   // typed store (C++ float -> integer trunc
 }
 
 using Key = std::tuple<int, int, int>;
+constexpr int KEY_DOMAIN = 1 << 20;   // block coordinates live in [-2^20, 2^20) (specification shared with the HIP path)
+bool key_in_domain(int x, int y, int z) {
+	return x >= -KEY_DOMAIN && x < KEY_DOMAIN && y >= -KEY_DOMAIN && y < KEY_DOMAIN && z >= -KEY_DOMAIN && z < KEY_DOMAIN;
+}
 
 struct Grid {
 	float voxel;
@@ -353,10 +357,14 @@ ORC_API void orc_grid_integrate(void* h, const int32_t* coords, int64_t n, const
 
 // IntegrateNonRigid (NonRigidSurfaceVoxelBlockGridImpl.h:52-229) over all active blocks (after activating `coords`).
 // apply_oblique_test = 0 drops the `cosine > 0.5` skip (used only to check the reference KAT, see tests).
+// grow_surface = 1 restates the product's growth mode (no counterpart in the reference): the oblique
+// test keeps surface seen head-on and skips `!(cosine >= 0.5)` instead (grazing views and pixels without a normal), and
+// the observation is counted in the voxel weight (stored through store_cast, as the rigid integration does).
 ORC_API void orc_grid_integrate_non_rigid(void* h, const int32_t* coords, int64_t n, const float* nodes, const float* R, const float* t,
                                           const float* c2, int N, float coverage, int K, int min_valid, const void* depth, int dtype, int H, int W,
                                           const void* color, int Hc, int Wc, const float* normals, const double* Kd, const double* Kc,
-                                          const double* E, float scale, float dmax, float trunc_mult, float* cos_out, int apply_oblique_test) {
+                                          const double* E, float scale, float dmax, float trunc_mult, float* cos_out, int apply_oblique_test,
+                                          int grow_surface) {
 	Grid* g = static_cast<Grid*>(h);
 	g->activate(coords, n);
 	const Field f{N, K, min_valid, nodes, R, t, c2, coverage};
@@ -398,7 +406,7 @@ ORC_API void orc_grid_integrate_non_rigid(void* h, const int32_t* coords, int64_
 			const int64_t pix = static_cast<int64_t>(vr) * W + ui;
 			const float cosine = (vd[0] * normals[3 * pix] + vd[1] * normals[3 * pix + 1]) + vd[2] * normals[3 * pix + 2];
 			cos_out[pix] = cosine;   // racy in the reference; the serial last writer (highest voxel index) here and on the GPU
-			if (psdf <= -trunc || (apply_oblique_test && cosine > 0.5f)) continue;
+			if (psdf <= -trunc || (apply_oblique_test && (grow_surface ? !(cosine >= 0.5f) : cosine > 0.5f))) continue;
 			const int64_t lin = static_cast<int64_t>(b) * g->res3 + vi;
 			const float tn = (psdf < trunc ? psdf : trunc) / trunc;
 			const float wt = g->weight[lin], inv = 1.0f / (wt + 1);
@@ -414,6 +422,7 @@ ORC_API void orc_grid_integrate_non_rigid(void* h, const int32_t* coords, int64_
 						g->color[3 * lin + ch] = store_cast(g->cdt, (wt * g->color[3 * lin + ch] + im.c(ui, vr, ch) * mult) * inv);
 				}
 			}
+			if (grow_surface) g->weight[lin] = store_cast(g->wdt, wt + 1);
 		}
 }
 
@@ -542,14 +551,16 @@ ORC_API void orc_boxes_mask(const float* boxes, int64_t n, const void* depth, in
 	}
 }
 
-// inactive neighbours of the active blocks, neighbour-major (NonRigidSurfaceVoxelBlockGrid.cpp:68-96), duplicates kept
+// inactive neighbours of the active blocks, neighbour-major (NonRigidSurfaceVoxelBlockGrid.cpp:68-96), duplicates kept;
+// neighbours outside the grid's block-coordinate domain [-2^20, 2^20) are no candidates (the product's key domain,
+// the reference's hash map has no such bound)
 ORC_API int64_t orc_grid_inactive_neighbors(void* h, int32_t* out, int64_t cap) {
 	const Grid* g = static_cast<Grid*>(h);
 	int64_t n = 0;
 	for (int nb = 0; nb < 27; nb++)
 		for (size_t b = 0; b < g->keys.size(); b++) {
 			const int x = std::get<0>(g->keys[b]) + nb % 3 - 1, y = std::get<1>(g->keys[b]) + (nb % 9) / 3 - 1, z = std::get<2>(g->keys[b]) + nb / 9 - 1;
-			if (g->find(x, y, z) >= 0) continue;
+			if (!key_in_domain(x, y, z) || g->find(x, y, z) >= 0) continue;
 			if (n < cap) {
 				out[3 * n] = x;
 				out[3 * n + 1] = y;

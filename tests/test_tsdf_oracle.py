@@ -160,3 +160,69 @@ def test_marching_cubes_table_is_the_published_one(oracle_mod):
     fn = np.cross(V[T[:, 1]] - V[T[:, 0]], V[T[:, 2]] - V[T[:, 0]])
     assert (np.einsum("ij,ij->i", fn, V[T].mean(1) - 9.5) > 0).all()
     assert len(seen) >= 250
+
+
+def _growth_case(O, grow_surface):
+    """One block (0, 0, 6) of 8^3 voxels (z = 0.48 ... 0.55), a flat depth of 0.515 m, one node at the origin with identity
+    motion and a coverage that reaches every voxel (so a voxel warps onto itself, exactly), camera-facing normals except
+    on the image rows below 8, which have none. Returns the voxel rows, the cosine map and the numpy expectation."""
+    f32 = np.float32
+    K = TU.simple_intrinsics(100.0, 4.0, 4.0)
+    depth = np.full((24, 24), 0.515, f32)
+    normals = np.tile(f32([0, 0, -1]), (24, 24, 1))
+    normals[:8] = 0
+    g = O.OracleGrid(0.01, 8)
+    cos = g.integrate_non_rigid(np.array([[0, 0, 6]], np.int32), np.zeros((1, 3), f32), np.eye(3, dtype=f32)[None], np.zeros((1, 3), f32), 1.0,
+                                1, 1, depth, None, normals.reshape(-1, 3), K, K, np.eye(4), 1.0, 3.0, 3.0, grow_surface=grow_surface)
+    rows = g.values_all()
+    x, y, z = rows[:, 0], rows[:, 1], rows[:, 2]
+    assert z.min() == f32(48) * f32(0.01) and z.max() == f32(55) * f32(0.01)
+    iz = f32(1) / z
+    u, v = np.floor((f32(100) * x) * iz + f32(4) + f32(0.5)).astype(int), np.floor((f32(100) * y) * iz + f32(4) + f32(0.5)).astype(int)
+    assert u.max() < 24 and v.max() < 24
+    trunc = f32(0.01) * f32(3.0)
+    psdf = f32(0.515) - z
+    in_band = psdf > -trunc
+    assert in_band.sum() == 7 * 64 and (psdf[in_band] < trunc).any() and (psdf[in_band] >= trunc).any()
+    tsdf = np.where(psdf < trunc, psdf, trunc) / trunc
+    return rows, cos, u, v, in_band, tsdf, v >= 8
+
+
+def test_growth_mode_off_keeps_the_reference_rule(oracle_mod):
+    """Growth off (the default): the weight is never counted and voxels seen head-on (cosine > 0.5) are skipped; only
+    pixels without a normal (cosine 0) pass the reference's oblique test."""
+    rows, cos, u, v, in_band, tsdf, has_normal = _growth_case(oracle_mod, False)
+    assert (rows[:, 4] == 0).all()
+    assert has_normal.any() and (~has_normal).any()
+    assert (cos[v[has_normal], u[has_normal]] > 0.9).all()
+    assert (rows[has_normal, 3] == 0).all()
+    upd = in_band & ~has_normal
+    assert np.array_equal(rows[upd, 3], tsdf[upd]) and (rows[~in_band, 3] == 0).all()
+
+
+def test_growth_mode_on_counts_head_on_observations(oracle_mod):
+    """Growth on: exactly the voxels within the truncation band that see a camera-facing normal get weight 1 and
+    tsdf = min(psdf, trunc) / trunc; pixels with a zero normal (cosine 0) are skipped."""
+    rows, cos, u, v, in_band, tsdf, has_normal = _growth_case(oracle_mod, True)
+    upd = in_band & has_normal
+    assert 0 < upd.sum() < in_band.sum()
+    assert np.array_equal(rows[:, 4], upd.astype(np.float32))
+    assert np.array_equal(rows[:, 3], np.where(upd, tsdf, np.float32(0)))
+    assert (cos[v[~has_normal], u[~has_normal]] == 0).all() and (rows[~has_normal, 3:5] == 0).all()
+
+
+def test_growth_mode_counts_weights_through_the_typed_store(oracle_mod):
+    """uint16 weights and uint8 color: two growth-mode passes leave weight 2 and the truncated running color average."""
+    O = oracle_mod
+    K = TU.simple_intrinsics(100.0, 4.0, 4.0)
+    depth = np.full((24, 24), 515, np.uint16)
+    normals = np.tile(np.float32([0, 0, -1]), (24 * 24, 1))
+    g = O.OracleGrid(0.01, 8, "uint16", "uint8")
+    for value in (100, 201):
+        g.integrate_non_rigid(np.array([[0, 0, 6]], np.int32), np.zeros((1, 3), np.float32), np.eye(3, dtype=np.float32)[None],
+                              np.zeros((1, 3), np.float32), 1.0, 1, 1, depth, np.full((24, 24, 3), value, np.uint8), normals, K, K, np.eye(4),
+                              1000.0, 3.0, 3.0, grow_surface=True)
+    rows = g.values_all()
+    seen = rows[:, 4] > 0
+    assert seen.sum() == 7 * 64 and (rows[seen, 4] == 2).all()
+    assert (rows[seen, 5:] == 150).all()   # (1 * 100 + 201) / 2 = 150.5, truncated by the uint8 store
