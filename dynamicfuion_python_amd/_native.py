@@ -178,6 +178,8 @@ _SIGNATURES = {
     "nnrt_voxel_grid_activate_sleeve_blocks": (c_int32, [c_void_p, c_void_p, c_void_p]),
     "nnrt_voxel_grid_extract_triangle_mesh": (c_int32, [c_void_p, c_float, c_void_p, c_void_p, c_void_p]),
     "nnrt_voxel_grid_copy_mesh": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "nnrt_voxel_grid_ray_cast": (c_int32, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_float, c_float, c_float,
+                                           c_float, c_float, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "nnrt_marching_cubes_table": (c_int32, [c_void_p, c_void_p]),
     # include/nnrt_dlpack.h
     "nnrt_warp_field_create_dlpack": (c_int32, [c_void_p, c_float, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p, c_int32,

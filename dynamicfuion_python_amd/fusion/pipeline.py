@@ -346,6 +346,17 @@ class FusionPipeline:
         mesh = self.volume.extract_triangle_mesh(float(self.mesh_extraction_threshold()), -1)
         return mesh
 
+    def render_canonical_model(self, render_attributes=("depth", "normal"), extrinsics=None, weight_threshold=None):
+        """Ray-cast the canonical volume over all of its blocks with the sequence's intrinsics and image size
+        (VoxelBlockGrid.ray_cast): a dict of device tensors, "range" and one map per attribute. `extrinsics`
+        defaults to the loop's current camera, `weight_threshold` to mesh_extraction_threshold(); the truncation
+        multiplier, depth scale and far limit are the loop's own. Nothing in the loop calls this."""
+        E = self.extrinsics if extrinsics is None else extrinsics
+        threshold = self.mesh_extraction_threshold() if weight_threshold is None else weight_threshold
+        return self.volume.ray_cast(self.volume.get_block_coordinates(), self.K, E, self.intrinsics.width, self.intrinsics.height,
+                                    render_attributes, depth_scale=self.parameters.depth_scale, depth_max=self._depth_max(),
+                                    weight_threshold=float(threshold), trunc_voxel_multiplier=self.truncation_voxel_multiplier)
+
     # -- the loop -----------------------------------------------------------------------------------------------
     def process_frame(self, frame) -> FrameResult:
         t0 = time.perf_counter()

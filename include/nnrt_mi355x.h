@@ -649,6 +649,27 @@ nnrt_status nnrt_voxel_grid_extract_triangle_mesh(nnrt_voxel_grid* grid, float w
                                                   int64_t* h_triangle_count, void* stream);
 nnrt_status nnrt_voxel_grid_copy_mesh(const nnrt_voxel_grid* grid, float* d_vertices, float* d_normals, float* d_colors,
                                       int64_t* d_triangles, void* stream);
+/* RayCast(block_coords, intrinsic, extrinsic, width, height, render_attributes, depth_scale, depth_min, depth_max,
+ * weight_threshold, trunc_voxel_multiplier, range_map_down_factor) (VoxelBlockGrid.cpp:353-427, Open3D
+ * voxel_grid::EstimateRange + RayCast as restated in DESIGN.md section 19, with its two deviations): a depth range per
+ * image tile from the active blocks among d_block_coords [count,3], then one ray per pixel marched through the hashed
+ * blocks to the first crossing from positive to negative tsdf. attribute_mask selects the maps (NNRT_RAY_CAST_* bits);
+ * map pointers the mask leaves out may be NULL. Outputs (float32, every pixel written on every call, 0 at a miss):
+ * d_range [ceil(H/f), ceil(W/f), 2] (always), d_depth [H,W,1] = camera-space depth * depth_scale, d_vertex [H,W,3] and
+ * d_normal [H,W,3] in world coordinates (the normal points into free space), d_color [H,W,3] in [0,1]. h_E (world ->
+ * camera) may be NULL: identity. count == 0 or an empty grid is no error: every ray misses. NNRT_ERROR_ARGUMENT: a null
+ * grid, h_K or d_range; width, height or range_map_down_factor < 1; depth_min < 0, depth_min >= depth_max or
+ * depth_scale <= 0; a requested map that is NULL; color on a grid without color storage; a singular extrinsic;
+ * a step bound ceil(2 (depth_max - depth_min) / voxel_size) + 2 above 2^20. */
+#define NNRT_RAY_CAST_DEPTH 1
+#define NNRT_RAY_CAST_VERTEX 2
+#define NNRT_RAY_CAST_NORMAL 4
+#define NNRT_RAY_CAST_COLOR 8
+nnrt_status nnrt_voxel_grid_ray_cast(nnrt_voxel_grid* grid, const int32_t* d_block_coords, int64_t count, const double* h_K,
+                                     const double* h_E, int32_t width, int32_t height, int32_t attribute_mask, float depth_scale,
+                                     float depth_min, float depth_max, float weight_threshold, float trunc_voxel_multiplier,
+                                     int32_t range_map_down_factor, float* d_range, float* d_depth, float* d_vertex, float* d_normal,
+                                     float* d_color, void* stream);
 /* the marching-cubes tables (host): tri [256][31] int8 edge triples in emission order (-1 terminated; the published
  * Lorensen-Cline / Bourke table Open3D indexes, each triangle (a, b, c) emitted as (c, b, a), Open3D's slot 2 - v), edge mask [256] */
 nnrt_status nnrt_marching_cubes_table(int8_t* h_tri, uint16_t* h_edge_mask);
