@@ -120,6 +120,9 @@ _SIGNATURES = {
     "nnrt_backproject_depth_ushort": (c_int32, [c_void_p, c_int32, c_int32, c_float, c_float, c_float, c_float, c_float, c_void_p,
                                                 c_void_p]),
     "nnrt_backproject_depth_float": (c_int32, [c_void_p, c_int32, c_int32, c_float, c_float, c_float, c_float, c_void_p, c_void_p]),
+    "nnrt_filter_depth": (c_int32, [c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p]),
+    "nnrt_bilateral_filter_depth": (c_int32, [c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_int32, c_float, c_float,
+                                              c_void_p, c_void_p]),
     "nnrt_matmul3d": (c_int32, [c_void_p, c_void_p, c_int64, c_int32, c_int32, c_int32, c_void_p, c_void_p]),
     "nnrt_median_grid_subsample_3d_points": (c_int32, [c_void_p, c_int64, c_float, c_void_p, c_void_p, c_void_p]),
     "nnrt_get_vertex_erosion_mask": (c_int32, [c_int64, c_void_p, c_int64, c_int32, c_int32, c_void_p, c_void_p]),

@@ -1682,7 +1682,49 @@ nnrt_status nnrt_backproject_depth_float(const float* d_depth, int32_t height, i
 	                                    static_cast<hipStream_t>(stream));
 }
 
-nnrt_status nnrt_matmul3d(const float* d_a, const float* d_b, int64_t batch, int32_t m, int32_t k, int32_t n, float* d_c, void* stream) {
+nnrt_status nnrt_filter_depth(const uint16_t* d_in, int32_t height, int32_t width, int32_t radius, int32_t preserve_zero, uint16_t* d_out,
+                              void* stream) {
+	NNRT_CHECK_ARG(radius >= 0 && radius <= NNRT_DEPTH_FILTER_MAX_RADIUS, "radius must be in [0, 8]");
+	NNRT_CHECK_ARG(height >= 0 && width >= 0, "negative height or width");
+	if (height * static_cast<int64_t>(width) == 0) return NNRT_OK;
+	NNRT_CHECK_ARG(d_in, "null d_in");
+	NNRT_CHECK_ARG(d_out, "null d_out");
+	NNRT_CHECK_ARG(d_out != d_in, "d_out must not be d_in (the filter reads every pixel's neighbours)");
+	return launch_filter_depth_median(d_in, height, width, radius, preserve_zero != 0, d_out, static_cast<hipStream_t>(stream));
+}
+
+nnrt_status nnrt_bilateral_filter_depth(const void* d_in, int32_t in_dtype, int32_t height, int32_t width, int32_t radius,
+                                        const float* h_spatial_weights, const float* h_range_weights, int32_t range_weight_count,
+                                        float range_index_scale, float depth_scale, float* d_out, void* stream) {
+	NNRT_CHECK_ARG(in_dtype == NNRT_DTYPE_UINT16 || in_dtype == NNRT_DTYPE_FLOAT32, "in_dtype must be uint16 or float32");
+	NNRT_CHECK_ARG(radius >= 0 && radius <= NNRT_DEPTH_FILTER_MAX_RADIUS, "radius must be in [0, 8]");
+	NNRT_CHECK_ARG(height >= 0 && width >= 0, "negative height or width");
+	NNRT_CHECK_ARG(range_weight_count >= 1 && range_weight_count <= NNRT_BILATERAL_MAX_RANGE_WEIGHTS, "range_weight_count must be in [1, 4096]");
+	NNRT_CHECK_ARG(std::isfinite(range_index_scale) && range_index_scale > 0.f, "range_index_scale must be finite and positive");
+	NNRT_CHECK_ARG(std::isfinite(depth_scale) && depth_scale > 0.f, "depth_scale must be finite and positive");
+	NNRT_CHECK_ARG(h_spatial_weights, "null h_spatial_weights");
+	NNRT_CHECK_ARG(h_range_weights, "null h_range_weights");
+	const int spatial_count = (2 * radius + 1) * (2 * radius + 1);
+	for (int i = 0; i < spatial_count; i++) {
+		NNRT_CHECK_ARG(std::isfinite(h_spatial_weights[i]) && h_spatial_weights[i] >= 0.f, "h_spatial_weights holds a negative or non-finite entry");
+	}
+	for (int i = 0; i < range_weight_count; i++) {
+		NNRT_CHECK_ARG(std::isfinite(h_range_weights[i]) && h_range_weights[i] >= 0.f, "h_range_weights holds a negative or non-finite entry");
+	}
+	if (height * static_cast<int64_t>(width) == 0) return NNRT_OK;
+	NNRT_CHECK_ARG(d_in, "null d_in");
+	NNRT_CHECK_ARG(d_out, "null d_out");
+	NNRT_CHECK_ARG(static_cast<const void*>(d_out) != d_in, "d_out must not be d_in (the filter reads every pixel's neighbours)");
+	hipStream_t s = static_cast<hipStream_t>(stream);
+	StreamScratch<float> tables;   // spatial, then range
+	if (nnrt_status st = tables.alloc(static_cast<size_t>(spatial_count) + range_weight_count, s)) return st;
+	NNRT_HIP(hipMemcpyAsync(tables.ptr, h_spatial_weights, sizeof(float) * spatial_count, hipMemcpyHostToDevice, s));
+	NNRT_HIP(hipMemcpyAsync(tables.ptr + spatial_count, h_range_weights, sizeof(float) * range_weight_count, hipMemcpyHostToDevice, s));
+	return launch_filter_depth_bilateral(d_in, in_dtype, height, width, radius, tables.ptr, tables.ptr + spatial_count, range_weight_count,
+	                                     range_index_scale, depth_scale, d_out, s);
+}
+
+nnrt_status nnrt_matmul3d(const float* d_a,const float* d_b, int64_t batch, int32_t m, int32_t k, int32_t n, float* d_c, void* stream) {
 	NNRT_CHECK_ARG(batch >= 0 && m >= 0 && k >= 0 && n >= 0, "negative dimension");
 	NNRT_CHECK_ARG((d_a && d_b && d_c) || batch * m * n == 0, "null pointer");
 	return launch_matmul3d(d_a, d_b, batch, m, k, n, d_c, static_cast<hipStream_t>(stream));

@@ -112,6 +112,11 @@ struct BackprojectCamera {
 };
 nnrt_status launch_backproject_depth_u16(const uint16_t* depth, int H, int W, const BackprojectCamera& c, float* out, hipStream_t stream);
 nnrt_status launch_backproject_depth_f32(const float* depth, int H, int W, const BackprojectCamera& c, float* out, hipStream_t stream);
+// depth_filter.hip: zero-skipping median (cpp/cpu/image_proc.cpp:837-887) and table-driven bilateral filter of a depth image
+// (arguments checked by the caller; spatial / range are device tables)
+nnrt_status launch_filter_depth_median(const uint16_t* in, int H, int W, int radius, bool preserve_zero, uint16_t* out, hipStream_t stream);
+nnrt_status launch_filter_depth_bilateral(const void* in, int in_dtype, int H, int W, int radius, const float* spatial, const float* range,
+                                          int range_count, float index_scale, float depth_scale, float* out, hipStream_t stream);
 nnrt_status launch_unproject(const void* depth, int depth_dtype, int H, int W, const Camera& K, const WarpExtrinsics& pose, float scale,
                              float depth_max, float* pts, uint8_t* mask, hipStream_t stream);
 nnrt_status launch_warp_points(const float* points, const float* normals, int64_t V, const float* node_state, const int32_t* anchors,

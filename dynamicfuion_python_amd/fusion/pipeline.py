@@ -146,6 +146,15 @@ class FusionParameters:
     warp_field_extension: bool = False
     warp_field_extension_support_ratio: float = 1.0
     warp_field_extension_minimum_new_node_count: int = 1
+    # depth filters ahead of tracking: with either radius positive, tracked frames back-project a filtered
+    # copy of the depth for the rigid alignment, the fit and the normals; TSDF integration always takes the raw frame.
+    # Median first (zero-skipping, holes kept), then the bilateral smoother on its result. Radii up to 8; 0: off.
+    # depth_bilateral_spatial_sigma 0 means depth_bilateral_radius / 2. depth_bilateral_range_sigma is in sensor units:
+    # 30 is KinectFusion's conventional 30 mm and has not been tuned on any sequence here.
+    depth_median_radius: int = 0
+    depth_bilateral_radius: int = 0
+    depth_bilateral_spatial_sigma: float = 0.0
+    depth_bilateral_range_sigma: float = 30.0
     alignment: RenderingAlignmentParameters = field(default_factory=_default_alignment)
 
 
@@ -163,6 +172,7 @@ class FrameResult:
     extrinsics: Optional[np.ndarray] = None   # a copy of the world -> camera matrix this frame was tracked and fused with
     node_count: int = 0       # nodes of the motion graph after this frame
     new_node_count: int = 0   # of them, added by this frame's warp field extension
+    depth_filtered: bool = False   # tracked against filtered depth (depth_median_radius / depth_bilateral_radius)
 
 
 def remap_edges_to_node_order(edges, order) -> np.ndarray:
@@ -199,6 +209,9 @@ class FusionPipeline:
                                       "anchors along; use AnchorComputationMode.EUCLIDEAN")
         if p.graph_generation_mode == GraphGenerationMode.PROVIDED_NODES and nodes is None:
             raise ValueError("GraphGenerationMode.PROVIDED_NODES needs nodes=")
+        for name in ("depth_median_radius", "depth_bilateral_radius"):
+            if not 0 <= getattr(p, name) <= 8:
+                raise ValueError(f"FusionParameters.{name} must be in [0, 8], got {getattr(p, name)}")
         self.sequence = sequence if sequence._loaded else sequence.load()
         self.device = torch.cuda.current_device() if device is None else int(device)
         first = self.sequence.get_frame_at(self.sequence.start_frame_index)
@@ -233,6 +246,8 @@ class FusionPipeline:
         self.optimizer = RenderingAlignmentOptimizer((self.intrinsics.height, self.intrinsics.width), self.device, self.K, p.alignment)
         self.canonical_mesh = None
         self.warped_mesh = None
+        # the point image the last tracked frame was aligned and fitted to, and whose normals gated its integration
+        self.tracking_point_image = None
         self.processed_frames = 0
         self.results: List[FrameResult] = []
 
@@ -357,6 +372,19 @@ class FusionPipeline:
                                     render_attributes, depth_scale=self.parameters.depth_scale, depth_max=self._depth_max(),
                                     weight_threshold=float(threshold), trunc_voxel_multiplier=self.truncation_voxel_multiplier)
 
+    def filtered_point_image(self, depth):
+        """The point image tracked frames use when a depth filter is on: the median with holes kept, then the bilateral
+        smoother on its result, back-projected. `depth`: the frame's uint16 depth on the device, which is
+        left as it is: the volume integrates the raw frame."""
+        p = self.parameters
+        filtered = image_proc.filter_depth(depth, p.depth_median_radius, preserve_zero=True) if p.depth_median_radius > 0 else depth
+        if p.depth_bilateral_radius == 0:
+            return image_proc.backproject_depth_ushort(filtered, self.fx, self.fy, self.cx, self.cy, p.depth_scale)
+        spatial_sigma = p.depth_bilateral_spatial_sigma if p.depth_bilateral_spatial_sigma > 0 else p.depth_bilateral_radius / 2.0
+        metres = image_proc.bilateral_filter_depth(filtered, p.depth_bilateral_radius, spatial_sigma, p.depth_bilateral_range_sigma,
+                                                   depth_scale=p.depth_scale)
+        return image_proc.backproject_depth_float(metres, self.fx, self.fy, self.cx, self.cy)
+
     # -- the loop -----------------------------------------------------------------------------------------------
     def process_frame(self, frame) -> FrameResult:
         t0 = time.perf_counter()
@@ -377,7 +405,12 @@ class FusionPipeline:
             # track: fit the canonical mesh extracted at the end of the previous frame to this frame's depth (the
             # tracking-method switch, pipeline.py:356-365)
             canonical = self.canonical_mesh
-            points = image_proc.backproject_depth_ushort(depth, self.fx, self.fy, self.cx, self.cy, p.depth_scale)
+            if p.depth_median_radius > 0 or p.depth_bilateral_radius > 0:
+                points = self.filtered_point_image(depth)
+                res.depth_filtered = True
+            else:
+                points = image_proc.backproject_depth_ushort(depth, self.fx, self.fy, self.cx, self.cy, p.depth_scale)
+            self.tracking_point_image = points
             res.canonical_vertex_count, res.canonical_triangle_count = canonical.vertex_positions.shape[0], canonical.triangle_indices.shape[0]
             if p.rigid_alignment and self.warped_mesh is not None and self.warped_mesh.triangle_indices.shape[0] > 0:
                 # the camera's motion since the previous frame, before the non-rigid fit (pipeline.py:338-354): the warped

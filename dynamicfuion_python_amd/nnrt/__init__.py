@@ -5,6 +5,7 @@ and the new nnrt.alignment (DeformableMeshToImageFitter, IterationMode) that the
 """
 from . import core, geometry, rendering, alignment, image_proc  # noqa: F401
 from .image_proc import backproject_depth_ushort, backproject_depth_float  # noqa: F401  (nnrt_pybind.cpp:52-67)
+from .image_proc import filter_depth  # noqa: F401  (nnrt_pybind.cpp:97-104)
 from . import graph_proc  # noqa: F401
 from .graph_proc import get_vertex_erosion_mask, sample_nodes  # noqa: F401  (nnrt_pybind.cpp:121-126)
 from .image_proc import compute_mesh_from_depth  # noqa: F401  (nnrt_pybind.cpp:79-80)

@@ -1,12 +1,17 @@
-"""Top-level `nnrt` image functions on the fusion app's input path (cpp/pybind/nnrt_pybind.cpp:50-67): depth image ->
-ordered point image, on the GPU. Inputs may be numpy or torch; outputs are device tensors [H, W, 3] float32."""
+"""Top-level `nnrt` image functions on the fusion app's input path (cpp/pybind/nnrt_pybind.cpp:50-67, :97-104): depth image ->
+ordered point image, and the depth filters ahead of it, on the GPU. Inputs may be numpy or torch; outputs are device
+tensors ([H, W, 3] float32 point images, [H, W] uint16 or float32 depth)."""
 from __future__ import annotations
+
+import math
 
 import numpy as np
 import torch
 
 from .. import _native as N
+from ._overloads import Overloaded, is_int, is_tensor
 from ._tensors import device_of
+from .voxel_grid import DTYPE_FLOAT32, DTYPE_UINT16
 
 
 def _depth_on_device(image_in, dtype: torch.dtype):
@@ -89,6 +94,90 @@ def compute_mesh_from_depth(point_image, max_triangle_edge_distance):
                                                  N.stream_ptr()))
     nv, nf = int(counts[0]), int(counts[1])
     return vertices[:nv].clone(), pixels[:nv].clone(), faces[:nf].clone()
+
+
+def _is_depth_u16(image) -> bool:
+    return (isinstance(image, np.ndarray) and image.dtype == np.uint16) or \
+           (isinstance(image, torch.Tensor) and image.dtype in (torch.uint16, torch.int16))
+
+
+def _median(depth_image_in, depth_image_out, radius, preserve_zero) -> torch.Tensor:
+    N.require_gpu()
+    if not _is_depth_u16(depth_image_in):
+        raise ValueError("depth_image_in must be uint16 (numpy or torch; a torch.int16 tensor is taken as the uint16 bit pattern)")
+    d = _depth_on_device(depth_image_in, torch.int16)
+    H, W = d.shape
+    if depth_image_out is None:
+        out = torch.empty((H, W), dtype=torch.int16, device=d.device)
+    else:
+        out = depth_image_out
+        if not isinstance(out, torch.Tensor) or out.device != d.device or out.dtype not in (torch.uint16, torch.int16) \
+                or tuple(out.shape) != (H, W) or not out.is_contiguous():
+            raise ValueError(f"depth_image_out must be a contiguous uint16 [{H}, {W}] tensor on {d.device}")
+    N.check(N.lib().nnrt_filter_depth(N.ptr(d), H, W, int(radius), int(bool(preserve_zero)), N.ptr(out), N.stream_ptr()))
+    return out if out.dtype == torch.uint16 else out.view(torch.uint16)
+
+
+filter_depth = Overloaded(
+    "filter_depth",
+    "filter_depth (nnrt_pybind.cpp:97-104 -> image_proc.cpp:837-887; csrc/depth_filter.hip): zero-skipping median of a uint16 depth "
+    "image over a (2 radius + 1)^2 window clipped to the image, 0 <= radius <= 8. The output is the element of index n / 2 of the n "
+    "window values > 0 in ascending order, exactly. Deviations: an empty window gives 0 (the reference indexes an empty vector); "
+    "preserve_zero=True (ours) keeps a pixel that is 0 at 0, where the reference fills it from its neighbours. The result is a "
+    "device tensor viewed as torch.uint16; depth_image_out must be a contiguous device tensor of the input's shape.")
+
+
+@filter_depth.overload(lambda a: is_tensor(a["depth_image_in"]) and is_tensor(a["depth_image_out"]) and is_int(a["radius"]))
+def _filter_depth_into(depth_image_in, depth_image_out, radius, *, preserve_zero=False):
+    _median(depth_image_in, depth_image_out, radius, preserve_zero)
+
+
+@filter_depth.overload(lambda a: is_tensor(a["depth_image_in"]) and is_int(a["radius"]))
+def _filter_depth_new(depth_image_in, radius, *, preserve_zero=False):
+    return _median(depth_image_in, None, radius, preserve_zero)
+
+
+def bilateral_weight_tables(radius: int, spatial_sigma: float, range_sigma: float, range_cutoff=None):
+    """The two float32 tables of bilateral_filter_depth: spatial [(2 radius + 1), (2 radius + 1)] over (dy, dx),
+    exp(-(dx^2 + dy^2) / (2 spatial_sigma^2)), and range [range_cutoff + 1], exp(-i^2 / (2 range_sigma^2)) for a depth
+    difference of i units; range_cutoff defaults to ceil(3 range_sigma). Computed in float64 and rounded once."""
+    if not is_int(radius) or radius < 0:
+        raise ValueError(f"radius must be a non-negative integer, got {radius!r}")
+    if not (spatial_sigma > 0 and math.isfinite(spatial_sigma)) or not (range_sigma > 0 and math.isfinite(range_sigma)):
+        raise ValueError("spatial_sigma and range_sigma must be positive")
+    if range_cutoff is None:
+        range_cutoff = int(math.ceil(3.0 * range_sigma))
+    if not is_int(range_cutoff) or range_cutoff < 0:
+        raise ValueError(f"range_cutoff must be a non-negative integer, got {range_cutoff!r}")
+    offsets = np.arange(-radius, radius + 1, dtype=np.float64)
+    squared = offsets[:, None] ** 2 + offsets[None, :] ** 2
+    spatial = np.exp(-squared / (2.0 * float(spatial_sigma) ** 2)).astype(np.float32)
+    steps = np.arange(range_cutoff + 1, dtype=np.float64)
+    weights = np.exp(-steps ** 2 / (2.0 * float(range_sigma) ** 2)).astype(np.float32)
+    return np.ascontiguousarray(spatial), np.ascontiguousarray(weights)
+
+
+def bilateral_filter_depth(depth, radius: int, spatial_sigma: float, range_sigma: float, range_cutoff=None,
+                           depth_scale: float = 1000.0) -> torch.Tensor:
+    """Edge-preserving smoothing of a depth image (csrc/depth_filter.hip; the reference has no such filter):
+    [H, W] uint16 in sensor units or float32 in metres -> [H, W] float32 metres on the device, 0 where the input is not a
+    positive finite depth. A neighbour contributes with bilateral_weight_tables' spatial weight times the range weight of
+    its truncated depth difference in sensor units (float32 input: metres * depth_scale), and not at all beyond
+    range_cutoff units, so a depth step larger than that is not blurred. range_sigma and range_cutoff are in sensor units
+    for both input types; 0 <= radius <= 8, range_cutoff <= 4095."""
+    N.require_gpu()
+    spatial, weights = bilateral_weight_tables(radius, spatial_sigma, range_sigma, range_cutoff)
+    if _is_depth_u16(depth):
+        d, code, index_scale, out_scale = _depth_on_device(depth, torch.int16), DTYPE_UINT16, 1.0, float(depth_scale)
+    elif (isinstance(depth, np.ndarray) and depth.dtype == np.float32) or (isinstance(depth, torch.Tensor) and depth.dtype == torch.float32):
+        d, code, index_scale, out_scale = _depth_on_device(depth, torch.float32), DTYPE_FLOAT32, float(depth_scale), 1.0
+    else:
+        raise ValueError("depth must be a uint16 or float32 image (numpy or torch)")
+    H, W = d.shape
+    out = torch.empty((H, W), dtype=torch.float32, device=d.device)
+    N.check(N.lib().nnrt_bilateral_filter_depth(N.ptr(d), code, H, W, int(radius), N.ptr(spatial), N.ptr(weights), int(weights.shape[0]),
+                                                index_scale, out_scale, N.ptr(out), N.stream_ptr()))
+    return out
 
 
 def backproject_depth(depth_image, fx, fy, cx, cy, depth_scale: float = 1000.0) -> torch.Tensor:

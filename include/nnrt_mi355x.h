@@ -355,6 +355,35 @@ nnrt_status nnrt_backproject_depth_ushort(const uint16_t* d_depth, int32_t heigh
  * depth in metres [H,W] -> [H,W,3], as above with normalizer 1. */
 nnrt_status nnrt_backproject_depth_float(const float* d_depth, int32_t height, int32_t width, float fx, float fy, float cx, float cy,
                                          float* d_points, void* stream);
+/* nnrt.filter_depth(depth_image_in, depth_image_out, radius) / (depth_image_in, radius) (nnrt_pybind.cpp:97-104 ->
+ * image_proc.cpp:837-887): zero-skipping median of a uint16 depth image [H,W]. For every pixel the values > 0 of the
+ * (2 radius + 1)^2 window, clipped to the image, are put in ascending order; with n of them the output is the one of
+ * index n / 2 (integer division: the upper median of an even count). The result is exact. Two deviations from the
+ * reference: n == 0 gives 0 (the reference indexes an empty vector); with preserve_zero != 0 a pixel whose own value is
+ * 0 stays 0, while preserve_zero == 0 keeps the reference's behaviour, in which a hole takes the median of its valid
+ * neighbours and silhouettes grow by `radius`. 0 <= radius <= NNRT_DEPTH_FILTER_MAX_RADIUS; radius 0 copies the input.
+ * NNRT_ERROR_ARGUMENT for a radius outside that range, a negative height or width, null images of a non-empty size, and
+ * d_out == d_in (the stencil reads its neighbours). An empty image is no error. */
+#define NNRT_DEPTH_FILTER_MAX_RADIUS 8
+nnrt_status nnrt_filter_depth(const uint16_t* d_in, int32_t height, int32_t width, int32_t radius, int32_t preserve_zero, uint16_t* d_out,
+                              void* stream);
+/* Bilateral filter of a depth image, an edge-preserving smoother the reference does not have (its only depth filter is
+ * filter_depth, nnrt_pybind.cpp:97-104 -> image_proc.cpp:837-887, above). d_in [H,W] uint16 (NNRT_DTYPE_UINT16) or
+ * float32 (NNRT_DTYPE_FLOAT32), d_out [H,W] float32. The weights are two host tables, copied to the device on `stream`
+ * ahead of the launch: h_spatial_weights (2 radius + 1)^2 floats, row-major over (dy, dx); h_range_weights
+ * range_weight_count floats. float32 arithmetic in this order: c = float(in[y][x]); a value is invalid unless it is
+ * > 0 and finite, and an invalid pixel gives 0. Otherwise, over dy = -radius..radius (outer) and dx = -radius..radius
+ * (inner), skipping positions outside the image: v = float(in[y+dy][x+dx]), skipped if invalid;
+ * i = int(fabsf(v - c) * range_index_scale), truncated, skipped if i >= range_weight_count;
+ * w = spatial[dy+radius][dx+radius] * range[i]; S_w = S_w + w; S_v = S_v + w * v. out = (S_v / S_w) / depth_scale if
+ * S_w > 0, else 0. 0 <= radius <= NNRT_DEPTH_FILTER_MAX_RADIUS, 1 <= range_weight_count <=
+ * NNRT_BILATERAL_MAX_RANGE_WEIGHTS. NNRT_ERROR_ARGUMENT, before anything is launched, for values outside those ranges,
+ * a depth_scale or range_index_scale that is not finite and positive, null tables, a table entry that is negative or
+ * not finite, an unknown dtype, a negative height or width, and null images of a non-empty size. */
+#define NNRT_BILATERAL_MAX_RANGE_WEIGHTS 4096
+nnrt_status nnrt_bilateral_filter_depth(const void* d_in, int32_t in_dtype, int32_t height, int32_t width, int32_t radius,
+                                        const float* h_spatial_weights, const float* h_range_weights, int32_t range_weight_count,
+                                        float range_index_scale, float depth_scale, float* d_out, void* stream);
 /* nnrt.geometry.functional.compute_triangle_normals(mesh, normalized=True) (cpp/geometry/functional/NormalsOperations.cpp:36-46,
  * kernel NormalsOperationsImpl.h:39-68): d_out [F,3] = (v1 - v0) x (v2 - v0), optionally normalized (zero stays zero,
  * NaN -> (0,0,1)) */
