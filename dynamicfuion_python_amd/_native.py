@@ -125,6 +125,15 @@ _SIGNATURES = {
                                               c_void_p, c_void_p]),
     "nnrt_matmul3d": (c_int32, [c_void_p, c_void_p, c_int64, c_int32, c_int32, c_int32, c_void_p, c_void_p]),
     "nnrt_median_grid_subsample_3d_points": (c_int32, [c_void_p, c_int64, c_float, c_void_p, c_void_p, c_void_p]),
+    "nnrt_mean_grid_downsample_3d_points": (c_int32, [c_void_p, c_int64, c_float, c_float, c_float, c_float, c_void_p, c_void_p, c_void_p]),
+    "nnrt_closest_to_mean_grid_subsample_3d_points": (c_int32, [c_void_p, c_int64, c_float, c_float, c_float, c_float, c_void_p, c_void_p,
+                                                                c_void_p]),
+    "nnrt_median_grid_subsample_3d_points_binned": (c_int32, [c_void_p, c_int64, c_float, c_float, c_float, c_float, c_void_p, c_void_p,
+                                                              c_void_p]),
+    "nnrt_point_index_create": (c_int32, [c_void_p, c_int64, c_int32, c_void_p, ctypes.POINTER(c_void_p)]),
+    "nnrt_point_index_destroy": (None, [c_void_p]),
+    "nnrt_point_index_get_info": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "nnrt_point_index_find_k_nearest": (c_int32, [c_void_p, c_void_p, c_int64, c_int32, c_int32, c_void_p, c_void_p, c_void_p]),
     "nnrt_get_vertex_erosion_mask": (c_int32, [c_int64, c_void_p, c_int64, c_int32, c_int32, c_void_p, c_void_p]),
     "nnrt_sample_nodes": (c_int32, [c_void_p, c_int64, c_void_p, c_void_p, c_float, c_void_p, c_int64, c_void_p, c_void_p, c_void_p]),
     "nnrt_compute_vertex_support": (c_int32, [c_void_p, c_int64, c_void_p, c_int32, c_float, c_void_p, c_void_p, c_void_p, c_void_p]),

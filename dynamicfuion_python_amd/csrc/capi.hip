@@ -1737,6 +1737,78 @@ nnrt_status nnrt_median_grid_subsample_3d_points(const float* d_points, int64_t 
 	return launch_median_grid_subsample(d_points, static_cast<int>(n), cell, d_out, h_count, static_cast<hipStream_t>(stream));
 }
 
+// shared argument checks of the grid functions over the cell index (spatial_grid.hip)
+static nnrt_status check_grid_arguments(const void* d_points, int64_t n, float cell, float ox, float oy, float oz, const void* d_out,
+                                        const int64_t* h_count) {
+	NNRT_CHECK_ARG(h_count, "null h_cell_count");
+	NNRT_CHECK_ARG(n >= 0 && n < (int64_t(1) << 31) / 3, "point count out of range");
+	NNRT_CHECK_ARG(cell > 0.f && std::isfinite(cell), "grid_cell_size must be positive and finite");
+	NNRT_CHECK_ARG(std::isfinite(ox) && std::isfinite(oy) && std::isfinite(oz), "the grid offset must be finite");
+	NNRT_CHECK_ARG(n == 0 || d_points, "null d_points");
+	NNRT_CHECK_ARG(n == 0 || d_out, "null output");
+	return NNRT_OK;
+}
+
+nnrt_status nnrt_mean_grid_downsample_3d_points(const float* d_points, int64_t n, float cell, float ox, float oy, float oz, float* d_out,
+                                                int64_t* h_count, void* stream) {
+	if (nnrt_status st = check_grid_arguments(d_points, n, cell, ox, oy, oz, d_out, h_count)) return st;
+	const float offset[3] = {ox, oy, oz};
+	return launch_mean_grid_downsample(d_points, static_cast<int>(n), cell, offset, d_out, h_count, static_cast<hipStream_t>(stream));
+}
+
+nnrt_status nnrt_closest_to_mean_grid_subsample_3d_points(const float* d_points, int64_t n, float cell, float ox, float oy, float oz,
+                                                          int64_t* d_out, int64_t* h_count, void* stream) {
+	if (nnrt_status st = check_grid_arguments(d_points, n, cell, ox, oy, oz, d_out, h_count)) return st;
+	const float offset[3] = {ox, oy, oz};
+	return launch_closest_to_mean_grid_subsample(d_points, static_cast<int>(n), cell, offset, d_out, h_count, static_cast<hipStream_t>(stream));
+}
+
+nnrt_status nnrt_median_grid_subsample_3d_points_binned(const float* d_points, int64_t n, float cell, float ox, float oy, float oz, int64_t* d_out,
+                                                        int64_t* h_count, void* stream) {
+	if (nnrt_status st = check_grid_arguments(d_points, n, cell, ox, oy, oz, d_out, h_count)) return st;
+	const float offset[3] = {ox, oy, oz};
+	return launch_median_grid_subsample_binned(d_points, static_cast<int>(n), cell, offset, d_out, h_count, static_cast<hipStream_t>(stream));
+}
+
+nnrt_status nnrt_point_index_create(const float* d_points, int64_t point_count, int32_t dimension_count, void* stream, nnrt_point_index** out) {
+	NNRT_CHECK_ARG(out, "null output");
+	*out = nullptr;
+	NNRT_CHECK_ARG(dimension_count == 3, "points must be [point_count, 3]: only 3-D points are indexed");
+	NNRT_CHECK_ARG(point_count >= 1 && point_count < (int64_t(1) << 31) / 3, "point_count must be at least 1 (and below 2^31 / 3)");
+	NNRT_CHECK_ARG(d_points, "null d_points");
+	PointIndex* index = nullptr;
+	if (nnrt_status st = point_index_create(d_points, static_cast<int>(point_count), static_cast<hipStream_t>(stream), &index)) return st;
+	*out = reinterpret_cast<nnrt_point_index*>(index);
+	return NNRT_OK;
+}
+
+void nnrt_point_index_destroy(nnrt_point_index* index) {
+	if (!index) return;
+	hipDeviceSynchronize();   // queries still in flight read the index
+	point_index_destroy(reinterpret_cast<PointIndex*>(index));
+}
+
+nnrt_status nnrt_point_index_get_info(const nnrt_point_index* index, int64_t* h_point_count, float* h_cell_size, int64_t* h_cell_count,
+                                      int32_t* h_build_count) {
+	NNRT_CHECK_ARG(index, "null index");
+	point_index_info(reinterpret_cast<const PointIndex*>(index), h_point_count, h_cell_size, h_cell_count, h_build_count);
+	return NNRT_OK;
+}
+
+nnrt_status nnrt_point_index_find_k_nearest(const nnrt_point_index* index, const float* d_query_points, int64_t query_count,
+                                            int32_t dimension_count, int32_t k, int32_t* d_out_indices, float* d_out_distances, void* stream) {
+	NNRT_CHECK_ARG(index, "null index");
+	NNRT_CHECK_ARG(dimension_count == 3, "query_points must be [query_count, 3]: only 3-D points are indexed");
+	NNRT_CHECK_ARG(k >= 1 && k <= NNRT_POINT_INDEX_MAX_K, "k must be in [1, 16]");
+	NNRT_CHECK_ARG(query_count >= 0 && query_count < (int64_t(1) << 31) / NNRT_POINT_INDEX_MAX_K, "query count out of range");
+	if (query_count == 0) return NNRT_OK;
+	NNRT_CHECK_ARG(d_query_points, "null d_query_points");
+	NNRT_CHECK_ARG(d_out_indices, "null d_out_indices");
+	NNRT_CHECK_ARG(d_out_distances, "null d_out_distances");
+	return point_index_find_k_nearest(reinterpret_cast<const PointIndex*>(index), d_query_points, static_cast<int>(query_count), k, d_out_indices,
+	                                  d_out_distances, static_cast<hipStream_t>(stream));
+}
+
 nnrt_status nnrt_axis_angle_to_matrices_rodrigues(const float* d_vectors, int32_t count, float* d_matrices, void* stream) {
 	return launch_rodrigues(d_vectors, count, d_matrices, static_cast<hipStream_t>(stream));
 }

@@ -124,6 +124,18 @@ nnrt_status launch_warp_points(const float* points, const float* normals, int64_
                                hipStream_t stream);
 nnrt_status launch_matmul3d(const float* A, const float* B, int64_t batch, int m, int k, int n, float* C, hipStream_t stream);
 nnrt_status launch_median_grid_subsample(const float* pts, int n, float cell, int64_t* out, int64_t* h_count, hipStream_t s);
+// spatial_grid.hip: grid down-samplers over a sorted cell index and the K-NN point index (arguments checked by the caller;
+// offset is three host floats; the grid functions synchronize `s`)
+nnrt_status launch_mean_grid_downsample(const float* pts, int n, float cell, const float* offset, float* out, int64_t* h_count, hipStream_t s);
+nnrt_status launch_closest_to_mean_grid_subsample(const float* pts, int n, float cell, const float* offset, int64_t* out, int64_t* h_count,
+                                                  hipStream_t s);
+nnrt_status launch_median_grid_subsample_binned(const float* pts, int n, float cell, const float* offset, int64_t* out, int64_t* h_count,
+                                                hipStream_t s);
+struct PointIndex;
+nnrt_status point_index_create(const float* pts, int n, hipStream_t s, PointIndex** out);
+void point_index_destroy(PointIndex* index);
+void point_index_info(const PointIndex* index, int64_t* point_count, float* cell_size, int64_t* cell_count, int32_t* build_count);
+nnrt_status point_index_find_k_nearest(const PointIndex* index, const float* queries, int Q, int k, int32_t* out_i, float* out_d, hipStream_t s);
 // graph_sampling.hip: motion-graph node selection (cpp/cpu/graph_proc.cpp:27-155)
 nnrt_status launch_vertex_erosion_mask(int64_t V, const int64_t* faces, int64_t F, int iteration_count, int min_neighbors, uint8_t* mask,
                                        int* error_flag, hipStream_t s);

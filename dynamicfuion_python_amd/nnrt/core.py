@@ -1,8 +1,10 @@
-"""nnrt.core / nnrt.core.linalg mirror (cpp/pybind/core/linalg/linalg.cpp)."""
+"""nnrt.core / nnrt.core.linalg mirror (cpp/pybind/core/core.cpp: matmul3d, KDTree; cpp/pybind/core/linalg/linalg.cpp)."""
 from __future__ import annotations
 
+import ctypes
 import types
 
+import numpy as np
 import torch
 
 from .. import _native as N
@@ -76,6 +78,70 @@ def matmul3d(array_of_matrices_a, array_of_matrices_b) -> torch.Tensor:
     out = torch.empty((A.shape[0], A.shape[1], n), dtype=torch.float32, device=dev)
     N.check(N.lib().nnrt_matmul3d(N.ptr(A), N.ptr(B), A.shape[0], A.shape[1], A.shape[2], n, N.ptr(out), N.stream_ptr()))
     return out
+
+
+def _shape_of(x):
+    return tuple(x.shape) if hasattr(x, "shape") else tuple(np.asarray(x).shape)
+
+
+class KDTree:
+    """nnrt.core.KDTree (cpp/pybind/core/core.cpp -> cpp/core/KdTree.h): exact K nearest neighbours of 3-D points. The index is
+    a uniform grid of cells on the device (csrc/spatial_grid.hip), not the reference's tree; it holds its own copy of the
+    points. close() (or garbage collection) frees it."""
+    MAX_K = 16
+
+    def __init__(self, points):
+        self._handle = None
+        shape = _shape_of(points)
+        if len(shape) != 2 or shape[1] != 3:
+            raise RuntimeError(f"points must be [n, 3] (3-D points only), got {shape}")
+        if shape[0] < 1:
+            raise RuntimeError("KDTree needs at least one point")
+        N.require_gpu()
+        self._device = torch.device("cuda", N.current_device())
+        p = to_device(points, torch.float32, self._device)
+        handle = ctypes.c_void_p()
+        N.check(N.lib().nnrt_point_index_create(N.ptr(p), p.shape[0], p.shape[1], N.stream_ptr(), ctypes.byref(handle)))
+        self._handle = handle
+        self.point_count = int(p.shape[0])
+
+    def find_k_nearest_to_points(self, query_points, k, sort_output=False):
+        """(indices [Q, k] int32, distances [Q, k] float32), each row ascending by (distance, index); Euclidean distances.
+        Slots past the point count hold -1 and +inf. Rows are always sorted, so sort_output changes nothing (the
+        reference's unsorted order is unspecified)."""
+        if self._handle is None:
+            raise RuntimeError("the KDTree has been closed")
+        shape = _shape_of(query_points)
+        if len(shape) != 2 or shape[1] != 3:
+            raise RuntimeError(f"query_points must be [q, 3] (3-D points only), got {shape}")
+        k = int(k)
+        if not 1 <= k <= self.MAX_K:
+            raise RuntimeError(f"k must be in [1, {self.MAX_K}], got {k}")
+        q = to_device(query_points, torch.float32, self._device)
+        indices = torch.empty((q.shape[0], k), dtype=torch.int32, device=self._device)
+        distances = torch.empty((q.shape[0], k), dtype=torch.float32, device=self._device)
+        N.check(N.lib().nnrt_point_index_find_k_nearest(self._handle, N.ptr(q), q.shape[0], q.shape[1], k, N.ptr(indices), N.ptr(distances),
+                                                        N.stream_ptr()))
+        return indices, distances
+
+    def info(self) -> dict:
+        """The grid behind the index: cell size chosen, occupied cells, and how many times it was built while refining."""
+        if self._handle is None:
+            raise RuntimeError("the KDTree has been closed")
+        count, cells, size, builds = ctypes.c_int64(), ctypes.c_int64(), ctypes.c_float(), ctypes.c_int32()
+        N.check(N.lib().nnrt_point_index_get_info(self._handle, ctypes.byref(count), ctypes.byref(size), ctypes.byref(cells), ctypes.byref(builds)))
+        return {"point_count": count.value, "cell_size": size.value, "cell_count": cells.value, "build_count": builds.value}
+
+    def close(self) -> None:
+        handle, self._handle = self._handle, None
+        if handle is not None:
+            N.lib().nnrt_point_index_destroy(handle)
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:   # interpreter shutdown: the library may be gone
+            pass
 
 
 class MatrixPreprocessingOperation:

@@ -537,6 +537,92 @@ def median_grid_subsample_3d_points(points, grid_cell_size):
     return out[: int(count[0])]
 
 
+_NO_OFFSET = (0., 0., 0.)
+_HALF_CELL = (0.5, 0.5, 0.5)
+
+
+def _points3(points, dev):
+    p = to_device(points, torch.float32, dev)
+    if p.dim() != 2 or p.shape[1] != 3:
+        raise RuntimeError(f"points must be [n, 3], got {tuple(p.shape)}")
+    return p
+
+
+def _grid_offset(grid_offset):
+    o = [float(v) for v in grid_offset]
+    if len(o) != 3:
+        raise RuntimeError(f"grid_offset must hold three values, got {len(o)}")
+    return o
+
+
+def _grid_indices(entry, p, grid_cell_size, grid_offset):
+    """One int64 point index per occupied cell, ascending, through one of the index-returning grid entry points."""
+    o = _grid_offset(grid_offset)
+    out = torch.empty(max(p.shape[0], 1), dtype=torch.int64, device=p.device)
+    count = np.zeros(1, np.int64)
+    N.check(entry(N.ptr(p), p.shape[0], float(grid_cell_size), o[0], o[1], o[2], N.ptr(out), N.ptr(count), N.stream_ptr()))
+    return out[: int(count[0])]
+
+
+def _grid_means(p, grid_cell_size, grid_offset):
+    o = _grid_offset(grid_offset)
+    out = torch.empty((max(p.shape[0], 1), 3), dtype=torch.float32, device=p.device)
+    count = np.zeros(1, np.int64)
+    N.check(N.lib().nnrt_mean_grid_downsample_3d_points(N.ptr(p), p.shape[0], float(grid_cell_size), o[0], o[1], o[2], N.ptr(out), N.ptr(count),
+                                                        N.stream_ptr()))
+    return out[: int(count[0])]
+
+
+def mean_grid_downsample_3d_points(points, grid_cell_size, grid_offset=_NO_OFFSET):
+    """MeanGridDownsample3dPoints (functional.cpp:143-145 -> GeometrySamplingImpl.h:48-54): [cells, 3] float32, the mean of the
+    points of every occupied grid cell (cell = floor(p / grid_cell_size + grid_offset)). Cells are ordered by their smallest
+    member index; the reference's order is its hash map's."""
+    return _grid_means(_points3(points, _dev()), grid_cell_size, grid_offset)
+
+
+def closest_to_mean_grid_subsample_3d_points(points, grid_cell_size, grid_offset=_NO_OFFSET):
+    """ClosestToGridMeanSubsample3dPoints (functional.cpp:146-148 -> GeometrySamplingImpl.h:56-62): int64 indices, ascending,
+    of the point nearest to the mean of every occupied grid cell (ties to the lower index)."""
+    return _grid_indices(N.lib().nnrt_closest_to_mean_grid_subsample_3d_points, _points3(points, _dev()), grid_cell_size, grid_offset)
+
+
+def _binned_medoids(p, grid_cell_size, grid_offset):
+    return _grid_indices(N.lib().nnrt_median_grid_subsample_3d_points_binned, p, grid_cell_size, grid_offset)
+
+
+def median_grid_subsample_3d_points_binned(points, grid_cell_size, grid_offset=_NO_OFFSET):
+    """median_grid_subsample_3d_points over the sorted cell index, with the grid offset of MedianGridSamplePoints
+    (GeometrySamplingMedian.h:264-296): the same indices, bit for bit at offset 0, in O(n log n + sum of squared cell sizes)
+    instead of O(n^2). An MI355X extension: the reference binds no offset."""
+    return _binned_medoids(_points3(points, _dev()), grid_cell_size, grid_offset)
+
+
+def _extended_cell(radius) -> float:
+    """GeometrySamplingImpl.h:70: extended_radius * 2 with extended_radius = sqrtf(2 * (radius * radius)), in float32."""
+    r = np.float32(radius)
+    return float(np.sqrt(np.float32(2) * (r * r), dtype=np.float32) * np.float32(2))
+
+
+def fast_mean_radius_downsample_3d_points(points, grid_cell_size):
+    """FastMeanRadiusDownsample3dPoints (functional.cpp:149-151 -> GeometrySamplingImpl.h:65-75). The second argument is the
+    down-sampling radius: the reference's binding names it grid_cell_size, and the name is kept. Cell means over cells of
+    size 2 * sqrt(2 * radius^2), then the means of those means over the same grid shifted by half a cell."""
+    cell = _extended_cell(grid_cell_size)
+    stage_1 = _grid_means(_points3(points, _dev()), cell, _NO_OFFSET)
+    return _grid_means(stage_1, cell, _HALF_CELL)
+
+
+def fast_median_radius_subsample_3d_points(points, grid_cell_size):
+    """FastMedianRadiusSubsample3dPoints (functional.cpp:155-157 -> GeometrySamplingImpl.h:104-118), int64 indices into
+    `points`. The second argument is the radius (named grid_cell_size as in the reference's binding). Cell medoids over cells
+    of size 2 * sqrt(2 * radius^2), then the medoids of those points over the same grid shifted by half a cell."""
+    cell = _extended_cell(grid_cell_size)
+    p = _points3(points, _dev())
+    stage_1 = _binned_medoids(p, cell, _NO_OFFSET)
+    stage_2 = _binned_medoids(p[stage_1].contiguous(), cell, _HALF_CELL)
+    return stage_1[stage_2]
+
+
 def _mesh_vf(mesh: TriangleMesh, dev):
     if mesh.vertex_positions is None or mesh.triangle_indices is None:
         raise RuntimeError("Mesh needs to have both vertex positions and triangle indices to compute normals.")
@@ -591,6 +677,11 @@ functional = types.SimpleNamespace(
     warp_triangle_mesh=warp_triangle_mesh,
     warp_point_cloud=warp_point_cloud,
     median_grid_subsample_3d_points=median_grid_subsample_3d_points,
+    median_grid_subsample_3d_points_binned=median_grid_subsample_3d_points_binned,
+    mean_grid_downsample_3d_points=mean_grid_downsample_3d_points,
+    closest_to_mean_grid_subsample_3d_points=closest_to_mean_grid_subsample_3d_points,
+    fast_mean_radius_downsample_3d_points=fast_mean_radius_downsample_3d_points,
+    fast_median_radius_subsample_3d_points=fast_median_radius_subsample_3d_points,
     unproject_raster_depth_without_filtering=unproject_raster_depth_without_filtering,
     compute_point_to_plane_distances=compute_point_to_plane_distances,
     compute_vertex_support=compute_vertex_support,

@@ -431,6 +431,49 @@ nnrt_status nnrt_matmul3d(const float* d_a, const float* d_b, int64_t batch, int
  * *h_sample_count receives the number written. Synchronizes `stream`. */
 nnrt_status nnrt_median_grid_subsample_3d_points(const float* d_points, int64_t point_count, float grid_cell_size, int64_t* d_out_indices,
                                                  int64_t* h_sample_count, void* stream);
+/* Grid down-samplers over a sorted cell index. The cell of a point is floorf(p / grid_cell_size +
+ * offset) per component in float32 (GridBinPoints, cpp/geometry/functional/kernel/GeometrySamplingGridBinning.h:39-40);
+ * cells are numbered by their smallest member index (the reference's order is its hash map's bin order). All three take
+ * d_points [point_count,3] float32, need room for point_count output rows, write the number of occupied cells to
+ * *h_cell_count and synchronize `stream`. NNRT_ERROR_ARGUMENT, before anything is launched, for a grid_cell_size that is
+ * not finite and positive, a non-finite offset, a negative point_count and null pointers; after the first kernel, for a
+ * non-finite coordinate and for a cell coordinate outside [-2^20, 2^20). point_count == 0 gives 0 cells.
+ *
+ * nnrt.geometry.functional.mean_grid_downsample_3d_points(points, grid_cell_size) (functional.cpp:143-145 ->
+ * GeometrySamplingImpl.h:48-54, GeometrySamplingMean.h): d_out_points [cells,3] float32, row r the mean of the members of
+ * cell r, summed in float64 and rounded once. */
+nnrt_status nnrt_mean_grid_downsample_3d_points(const float* d_points, int64_t point_count, float grid_cell_size, float offset_x, float offset_y,
+                                                float offset_z, float* d_out_points, int64_t* h_cell_count, void* stream);
+/* nnrt.geometry.functional.closest_to_mean_grid_subsample_3d_points(points, grid_cell_size) (functional.cpp:146-148 ->
+ * GeometrySamplingImpl.h:56-62): per cell the member with the smallest (dx*dx + dy*dy) + dz*dz (float32) to the cell's
+ * float32 mean, ties to the lower index; d_out_indices int64, ascending. */
+nnrt_status nnrt_closest_to_mean_grid_subsample_3d_points(const float* d_points, int64_t point_count, float grid_cell_size, float offset_x,
+                                                          float offset_y, float offset_z, int64_t* d_out_indices, int64_t* h_cell_count,
+                                                          void* stream);
+/* MedianGridSamplePoints with a grid offset (GeometrySamplingMedian.h:264-296, the stages of FastMedianRadiusSubsample3dPoints,
+ * GeometrySamplingImpl.h:104-118): the medoids of nnrt_median_grid_subsample_3d_points, bit for bit at offset 0, found per
+ * cell of the index instead of by all-pairs scans; d_out_indices int64, ascending. */
+nnrt_status nnrt_median_grid_subsample_3d_points_binned(const float* d_points, int64_t point_count, float grid_cell_size, float offset_x,
+                                                        float offset_y, float offset_z, int64_t* d_out_indices, int64_t* h_cell_count,
+                                                        void* stream);
+/* nnrt.core.KDTree(points) and KDTree.find_k_nearest_to_points(query_points, k, sort_output=false) (cpp/pybind/core/core.cpp ->
+ * cpp/core/KdTree.h): an exact K-nearest-neighbour index over d_points [point_count, 3] float32, held as a uniform grid of
+ * cells (not the reference's tree), with its own copy of the points. point_count >= 1; dimension_count must be 3; a
+ * non-finite coordinate is refused. Creation synchronizes `stream`; the handle owns its device memory.
+ * nnrt_point_index_find_k_nearest: d_out_indices [query_count, k] int32 and d_out_distances [query_count, k] float32,
+ * each row ordered by ((dx*dx + dy*dy) + dz*dz in float32 with d = point - query, point index) ascending; the distance
+ * written is sqrtf of that sum (Euclidean, as the reference returns). Slots past point_count hold -1 and +inf.
+ * 1 <= k <= NNRT_POINT_INDEX_MAX_K; anything else is NNRT_ERROR_ARGUMENT and nothing is launched. query_count == 0
+ * launches nothing. Does not synchronize. */
+#define NNRT_POINT_INDEX_MAX_K 16
+typedef struct nnrt_point_index nnrt_point_index;
+nnrt_status nnrt_point_index_create(const float* d_points, int64_t point_count, int32_t dimension_count, void* stream, nnrt_point_index** out);
+void nnrt_point_index_destroy(nnrt_point_index* index);
+/* any of the outputs may be null: the point count, the cell size chosen, the occupied cells and how often the index was built */
+nnrt_status nnrt_point_index_get_info(const nnrt_point_index* index, int64_t* h_point_count, float* h_cell_size, int64_t* h_cell_count,
+                                      int32_t* h_build_count);
+nnrt_status nnrt_point_index_find_k_nearest(const nnrt_point_index* index, const float* d_query_points, int64_t query_count,
+                                            int32_t dimension_count, int32_t k, int32_t* d_out_indices, float* d_out_distances, void* stream);
 /* nnrt.get_vertex_erosion_mask(vertex_positions, face_indices, iteration_count, min_neighbors) (nnrt_pybind.cpp:121-123 ->
  * cpp/cpu/graph_proc.cpp:27-90): faces start alive; iteration_count times, every alive face with a vertex touched by fewer
  * than min_neighbors alive faces dies. d_out_mask [vertex_count] uint8 = 1 where an alive face touches the vertex.
