@@ -111,6 +111,9 @@ _SIGNATURES = {
                                              c_void_p]),
     "nnrt_get_meshes_ndc_face_vertices_and_clip_mask": (c_int32, [c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_int32, c_int32, c_float,
                                                                   c_float, c_void_p, c_void_p, c_void_p]),
+    "nnrt_get_meshes_ndc_face_vertices_and_clip_mask_in_convention": (c_int32, [c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_int32,
+                                                                                c_int32, c_float, c_float, c_int32, c_void_p, c_void_p,
+                                                                                c_void_p]),
     "nnrt_get_mesh_ndc_face_vertices_and_clip_mask": (c_int32, [c_void_p, c_void_p, c_int64, c_void_p, c_int32, c_int32, c_float,
                                                                 c_float, c_void_p, c_void_p, c_void_p]),
     "nnrt_rasterize_ndc_triangles": (c_int32, [c_void_p, c_void_p, c_int64, c_int32, c_int32, c_float, c_int32, c_int32, c_int32,
@@ -123,6 +126,10 @@ _SIGNATURES = {
     "nnrt_filter_depth": (c_int32, [c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p]),
     "nnrt_bilateral_filter_depth": (c_int32, [c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_int32, c_float, c_float,
                                               c_void_p, c_void_p]),
+    "nnrt_shade_pixels": (c_int32, [c_int32, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p, c_int64, c_void_p, c_void_p,
+                                    c_int64, c_void_p, c_float, c_float, c_void_p, c_void_p]),
+    "nnrt_compare_depth_to_raster": (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p, c_int32, c_float, c_float, c_float,
+                                               c_void_p, c_void_p, c_void_p]),
     "nnrt_matmul3d": (c_int32, [c_void_p, c_void_p, c_int64, c_int32, c_int32, c_int32, c_void_p, c_void_p]),
     "nnrt_median_grid_subsample_3d_points": (c_int32, [c_void_p, c_int64, c_float, c_void_p, c_void_p, c_void_p]),
     "nnrt_mean_grid_downsample_3d_points": (c_int32, [c_void_p, c_int64, c_float, c_float, c_float, c_float, c_void_p, c_void_p, c_void_p]),

@@ -1575,10 +1575,20 @@ nnrt_status nnrt_get_meshes_ndc_face_vertices_and_clip_mask(const float* const* 
                                                             const int64_t* h_face_counts, int32_t mesh_count, const double* h_K, int32_t H,
                                                             int32_t W, float near_clip, float far_clip, float* d_face_ndc, uint8_t* d_clip_mask,
                                                             void* stream) {
+	return nnrt_get_meshes_ndc_face_vertices_and_clip_mask_in_convention(h_vertex_sets, h_face_sets, h_face_counts, mesh_count, h_K, H, W, near_clip,
+	                                                                     far_clip, NNRT_NDC_REFERENCE, d_face_ndc, d_clip_mask, stream);
+}
+
+nnrt_status nnrt_get_meshes_ndc_face_vertices_and_clip_mask_in_convention(const float* const* h_vertex_sets, const int64_t* const* h_face_sets,
+                                                                          const int64_t* h_face_counts, int32_t mesh_count, const double* h_K,
+                                                                          int32_t H, int32_t W, float near_clip, float far_clip,
+                                                                          int32_t ndc_convention, float* d_face_ndc, uint8_t* d_clip_mask,
+                                                                          void* stream) {
 	NNRT_CHECK_ARG(h_K && h_vertex_sets && h_face_sets && h_face_counts && mesh_count >= 0, "null pointer");
 	NNRT_CHECK_ARG(near_clip >= 0.f, "near_clipping_distance cannot be less than 0 (ExtractFaceVertices.cpp:40-44)");
 	NNRT_CHECK_ARG(near_clip <= far_clip, "near_clipping_distance cannot be greater than far_clipping_distance");
-	const NdcSetup ndc = make_ndc_setup(h_K, H, W, false);
+	NNRT_CHECK_ARG(ndc_convention == NNRT_NDC_REFERENCE || ndc_convention == NNRT_NDC_CONSISTENT, "unknown ndc_convention");
+	const NdcSetup ndc = make_ndc_setup(h_K, H, W, ndc_convention == NNRT_NDC_CONSISTENT);
 	int64_t offset = 0;
 	for (int m = 0; m < mesh_count; m++) {   // face f of mesh m -> output row offset(m) + f (ExtractClippedFaceVerticesImpl.h:111-116)
 		const int64_t F = h_face_counts[m];
@@ -1722,6 +1732,81 @@ nnrt_status nnrt_bilateral_filter_depth(const void* d_in, int32_t in_dtype, int3
 	NNRT_HIP(hipMemcpyAsync(tables.ptr + spatial_count, h_range_weights, sizeof(float) * range_weight_count, hipMemcpyHostToDevice, s));
 	return launch_filter_depth_bilateral(d_in, in_dtype, height, width, radius, tables.ptr, tables.ptr + spatial_count, range_weight_count,
 	                                     range_index_scale, depth_scale, d_out, s);
+}
+
+nnrt_status nnrt_shade_pixels(int32_t mode, const int64_t* d_pixel_face_indices, const float* d_pixel_barycentric_coordinates,
+                              const float* d_pixel_face_distances, int32_t height, int32_t width, int32_t faces_per_pixel,
+                              const int64_t* d_triangle_indices, int64_t face_count, const float* d_vertex_colors,
+                              const float* d_vertex_normals, int64_t vertex_count, const float* h_color, float pixel_line_width,
+                              float ambient, uint8_t* d_out_pixels, void* stream) {
+	NNRT_CHECK_ARG(mode == NNRT_SHADE_VERTEX_COLOR || mode == NNRT_SHADE_FLAT_EDGE || mode == NNRT_SHADE_HEADLIGHT,
+	               "mode must be NNRT_SHADE_VERTEX_COLOR, NNRT_SHADE_FLAT_EDGE or NNRT_SHADE_HEADLIGHT");
+	NNRT_CHECK_ARG(height >= 0 && width >= 0, "negative height or width");
+	NNRT_CHECK_ARG(faces_per_pixel >= 1, "faces_per_pixel must be at least 1");
+	NNRT_CHECK_ARG(face_count >= 0, "negative face_count");
+	NNRT_CHECK_ARG(vertex_count >= 0, "negative vertex_count");
+	const bool flat = mode == NNRT_SHADE_FLAT_EDGE;
+	if (flat) NNRT_CHECK_ARG(pixel_line_width > 0.f, "pixel_line_width must be positive");
+	if (mode == NNRT_SHADE_HEADLIGHT) NNRT_CHECK_ARG(ambient >= 0.f && ambient <= 1.f, "ambient must be in [0, 1]");
+	if (mode != NNRT_SHADE_VERTEX_COLOR) NNRT_CHECK_ARG(h_color, "null h_color");
+	if (mode == NNRT_SHADE_VERTEX_COLOR) NNRT_CHECK_ARG(d_vertex_colors || vertex_count == 0, "null d_vertex_colors (NNRT_SHADE_VERTEX_COLOR reads them)");
+	if (mode == NNRT_SHADE_HEADLIGHT) NNRT_CHECK_ARG(d_vertex_normals || vertex_count == 0, "null d_vertex_normals (NNRT_SHADE_HEADLIGHT reads them)");
+	if (!flat) NNRT_CHECK_ARG(d_triangle_indices || face_count == 0, "null d_triangle_indices");
+	const size_t pixels = static_cast<size_t>(height) * static_cast<size_t>(width);
+	if (pixels == 0) return NNRT_OK;
+	NNRT_CHECK_ARG(d_pixel_face_indices, "null d_pixel_face_indices");
+	if (flat) NNRT_CHECK_ARG(d_pixel_face_distances, "null d_pixel_face_distances");
+	if (!flat) NNRT_CHECK_ARG(d_pixel_barycentric_coordinates, "null d_pixel_barycentric_coordinates");
+	NNRT_CHECK_ARG(d_out_pixels, "null d_out_pixels");
+	const size_t fragments = pixels * static_cast<size_t>(faces_per_pixel), out_bytes = 3 * pixels;
+	const size_t nf = static_cast<size_t>(face_count), nv = static_cast<size_t>(vertex_count);
+	NNRT_CHECK_ARG(!(ranges_overlap(d_out_pixels, out_bytes, d_pixel_face_indices, sizeof(int64_t) * fragments) ||
+	                 ranges_overlap(d_out_pixels, out_bytes, d_pixel_barycentric_coordinates, sizeof(float) * 3 * fragments) ||
+	                 ranges_overlap(d_out_pixels, out_bytes, d_pixel_face_distances, sizeof(float) * fragments) ||
+	                 ranges_overlap(d_out_pixels, out_bytes, d_triangle_indices, sizeof(int64_t) * 3 * nf) ||
+	                 ranges_overlap(d_out_pixels, out_bytes, d_vertex_colors, sizeof(float) * 3 * nv) ||
+	                 ranges_overlap(d_out_pixels, out_bytes, d_vertex_normals, sizeof(float) * 3 * nv)),
+	               "d_out_pixels must not overlap an input");
+	const float ndc_line_width = flat ? pixel_line_width / (static_cast<float>(std::min(height, width)) / 2.0f) : 0.f;
+	return launch_shade_pixels(mode, d_pixel_face_indices, d_pixel_barycentric_coordinates, d_pixel_face_distances, height, width,
+	                           faces_per_pixel, d_triangle_indices, face_count, d_vertex_colors, d_vertex_normals, vertex_count, h_color,
+	                           ndc_line_width, ambient, d_out_pixels, static_cast<hipStream_t>(stream));
+}
+
+nnrt_status nnrt_compare_depth_to_raster(const int64_t* d_pixel_face_indices, const float* d_pixel_depths, int32_t height, int32_t width,
+                                         int32_t faces_per_pixel, const void* d_depth, int32_t depth_dtype, float depth_scale,
+                                         float depth_max, float inlier_threshold, float* d_out_difference,
+                                         nnrt_depth_agreement* h_out_statistics, void* stream) {
+	NNRT_CHECK_ARG(h_out_statistics, "null h_out_statistics");
+	NNRT_CHECK_ARG(height >= 0 && width >= 0, "negative height or width");
+	NNRT_CHECK_ARG(faces_per_pixel >= 1, "faces_per_pixel must be at least 1");
+	NNRT_CHECK_ARG(depth_dtype == NNRT_DTYPE_UINT16 || depth_dtype == NNRT_DTYPE_FLOAT32, "depth_dtype must be uint16 or float32");
+	NNRT_CHECK_ARG(std::isfinite(depth_scale) && depth_scale > 0.f, "depth_scale must be finite and positive");
+	NNRT_CHECK_ARG(!std::isnan(depth_max), "depth_max must not be NaN");
+	NNRT_CHECK_ARG(inlier_threshold >= 0.f, "inlier_threshold must not be negative or NaN");
+	std::memset(h_out_statistics, 0, sizeof(*h_out_statistics));
+	const size_t pixels = static_cast<size_t>(height) * static_cast<size_t>(width);
+	if (pixels == 0) return NNRT_OK;
+	NNRT_CHECK_ARG(d_pixel_face_indices, "null d_pixel_face_indices");
+	NNRT_CHECK_ARG(d_pixel_depths, "null d_pixel_depths");
+	NNRT_CHECK_ARG(d_depth, "null d_depth");
+	NNRT_CHECK_ARG(d_out_difference, "null d_out_difference");
+	const size_t fragments = pixels * static_cast<size_t>(faces_per_pixel), out_bytes = sizeof(float) * pixels;
+	NNRT_CHECK_ARG(!(ranges_overlap(d_out_difference, out_bytes, d_pixel_face_indices, sizeof(int64_t) * fragments) ||
+	                 ranges_overlap(d_out_difference, out_bytes, d_pixel_depths, sizeof(float) * fragments) ||
+	                 ranges_overlap(d_out_difference, out_bytes, d_depth, (depth_dtype == NNRT_DTYPE_UINT16 ? 2 : 4) * pixels)),
+	               "d_out_difference must not overlap an input");
+	hipStream_t s = static_cast<hipStream_t>(stream);
+	const size_t groups = static_cast<size_t>(depth_agreement_partial_count(height, width));
+	StreamScratch<nnrt_depth_agreement> records;   // one per workgroup, then the total
+	if (nnrt_status st = records.alloc(groups + 1, s)) return st;
+	if (nnrt_status st = launch_depth_agreement(d_pixel_face_indices, d_pixel_depths, height, width, faces_per_pixel, d_depth, depth_dtype,
+	                                            depth_scale, depth_max, inlier_threshold, d_out_difference, records.ptr,
+	                                            records.ptr + groups, s))
+		return st;
+	NNRT_HIP(hipMemcpyAsync(h_out_statistics, records.ptr + groups, sizeof(*h_out_statistics), hipMemcpyDeviceToHost, s));
+	NNRT_HIP(hipStreamSynchronize(s));
+	return NNRT_OK;
 }
 
 nnrt_status nnrt_matmul3d(const float* d_a,const float* d_b, int64_t batch, int32_t m, int32_t k, int32_t n, float* d_c, void* stream) {

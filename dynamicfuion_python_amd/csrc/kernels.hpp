@@ -117,6 +117,16 @@ nnrt_status launch_backproject_depth_f32(const float* depth, int H, int W, const
 nnrt_status launch_filter_depth_median(const uint16_t* in, int H, int W, int radius, bool preserve_zero, uint16_t* out, hipStream_t stream);
 nnrt_status launch_filter_depth_bilateral(const void* in, int in_dtype, int H, int W, int radius, const float* spatial, const float* range,
                                           int range_count, float index_scale, float depth_scale, float* out, hipStream_t stream);
+// shading.hip: rasterizer fragments -> uint8 RGB [H,W,3] (color: three host floats), and the model depth against a depth
+// frame (arguments checked by the caller, H * W > 0; partials holds depth_agreement_partial_count(H, W) records, result
+// one, both on the device)
+nnrt_status launch_shade_pixels(int mode, const int64_t* pixel_faces, const float* barycentrics, const float* distances, int H, int W, int K,
+                                const int64_t* triangles, int64_t face_count, const float* colors, const float* normals, int64_t vertex_count,
+                                const float* color, float ndc_line_width, float ambient, uint8_t* out, hipStream_t stream);
+int64_t depth_agreement_partial_count(int H, int W);
+nnrt_status launch_depth_agreement(const int64_t* pixel_faces, const float* pixel_depths, int H, int W, int K, const void* frame, int frame_dtype,
+                                   float depth_scale, float depth_max, float inlier_threshold, float* difference,
+                                   nnrt_depth_agreement* partials, nnrt_depth_agreement* result, hipStream_t stream);
 nnrt_status launch_unproject(const void* depth, int depth_dtype, int H, int W, const Camera& K, const WarpExtrinsics& pose, float scale,
                              float depth_max, float* pts, uint8_t* mask, hipStream_t stream);
 nnrt_status launch_warp_points(const float* points, const float* normals, int64_t V, const float* node_state, const int32_t* anchors,

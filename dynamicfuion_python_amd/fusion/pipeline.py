@@ -62,6 +62,7 @@ from ..data import camera as dcam
 from ..data.frame import FrameSequenceDataset
 from ..nnrt import geometry as G
 from ..nnrt import image_proc
+from ..nnrt import rendering
 from ..nnrt.alignment import NDC_CONSISTENT, align_rigid_point_to_plane
 from ..warp_field.graph_warp_field import build_graph_nodes_from_depth_image, extend_warp_field, sample_graph_nodes_from_mesh
 
@@ -155,6 +156,11 @@ class FusionParameters:
     depth_bilateral_radius: int = 0
     depth_bilateral_spatial_sigma: float = 0.0
     depth_bilateral_range_sigma: float = 30.0
+    # score every tracked frame: after the fit and before integration the freshly warped canonical mesh is
+    # rasterized in the live camera and its depth compared with the raw depth frame; FrameResult.model_* hold the result.
+    # Reads the graph and the canonical mesh only.
+    model_agreement: bool = False
+    model_agreement_inlier_threshold: float = 0.01   # metres
     alignment: RenderingAlignmentParameters = field(default_factory=_default_alignment)
 
 
@@ -173,6 +179,15 @@ class FrameResult:
     node_count: int = 0       # nodes of the motion graph after this frame
     new_node_count: int = 0   # of them, added by this frame's warp field extension
     depth_filtered: bool = False   # tracked against filtered depth (depth_median_radius / depth_bilateral_radius)
+    # FusionParameters.model_agreement: the warped model's rasterized depth against the raw frame (0 when not measured):
+    # pixels valid on both sides, on the model's only, on the frame's only; over the first, mean |difference| and RMS
+    # difference in metres and the share within model_agreement_inlier_threshold
+    model_overlap_count: int = 0
+    model_only_count: int = 0
+    frame_only_count: int = 0
+    model_depth_mean_abs: float = 0.0
+    model_depth_rmse: float = 0.0
+    model_inlier_ratio: float = 0.0
 
 
 def remap_edges_to_node_order(edges, order) -> np.ndarray:
@@ -372,6 +387,32 @@ class FusionPipeline:
                                     render_attributes, depth_scale=self.parameters.depth_scale, depth_max=self._depth_max(),
                                     weight_threshold=float(threshold), trunc_voxel_multiplier=self.truncation_voxel_multiplier)
 
+    def _warped_model_in_camera(self, extrinsics=None):
+        if self.active_graph is None or self.canonical_mesh is None or self.canonical_mesh.triangle_indices.shape[0] == 0:
+            raise RuntimeError("there is no canonical mesh to warp yet: process a frame first")
+        E = self.extrinsics if extrinsics is None else extrinsics
+        return self.active_graph.warp_mesh(self.canonical_mesh, extrinsics=E)
+
+    def render_warped_model(self, shader=None, extrinsics=None):
+        """Draw the canonical mesh warped by the current graph with the sequence's intrinsics and image size:
+        (image uint8 [H, W, 3], fragments), raster pixel (u, v) being pixel (u, v) of the depth frames. `extrinsics`
+        defaults to the loop's current camera, `shader` to VertexColorShader when the mesh has colours, else
+        HeadlightShader. Nothing in the default loop calls this."""
+        mesh = self._warped_model_in_camera(extrinsics)
+        if shader is None:
+            shader = rendering.VertexColorShader() if mesh.vertex_colors is not None else rendering.HeadlightShader()
+        return rendering.render_meshes(mesh, self.K, (self.intrinsics.height, self.intrinsics.width), shader,
+                                       ndc_convention=rendering.NDC_CONSISTENT)
+
+    def measure_model_agreement(self, depth):
+        """(DepthAgreement, difference image) of the warped canonical mesh's rasterized depth against `depth`, a raw depth
+        frame, in the loop's current camera and with its depth scale and far limit."""
+        p = self.parameters
+        fragments, _ = rendering.rasterize_meshes(self._warped_model_in_camera(), self.K, (self.intrinsics.height, self.intrinsics.width),
+                                                  ndc_convention=rendering.NDC_CONSISTENT)
+        return rendering.compare_depth_to_raster(fragments[0], fragments[1], depth, p.depth_scale, self._depth_max(),
+                                                 p.model_agreement_inlier_threshold)
+
     def filtered_point_image(self, depth):
         """The point image tracked frames use when a depth filter is on: the median with holes kept, then the bilateral
         smoother on its result, back-projected. `depth`: the frame's uint16 depth on the device, which is
@@ -425,6 +466,11 @@ class FusionPipeline:
             if res.canonical_triangle_count > 0:
                 self.optimizer.optimize_graph(self.active_graph, canonical, points, extrinsics=self.extrinsics)
                 res.tracked = True
+                if p.model_agreement:
+                    agreement, _ = self.measure_model_agreement(depth)
+                    res.model_overlap_count, res.model_only_count, res.frame_only_count = agreement.both, agreement.model_only, agreement.frame_only
+                    res.model_depth_mean_abs, res.model_depth_rmse = agreement.mean_abs, agreement.rmse
+                    res.model_inlier_ratio = agreement.inlier_ratio
             # fuse: blocks the warped surface's truncation band touches, then non-rigid integration (:371-417)
             blocks = self.volume.find_blocks_intersecting_truncation_region(depth, self.active_graph, self.K, self.extrinsics,
                                                                             p.depth_scale, depth_max, self.truncation_voxel_multiplier)

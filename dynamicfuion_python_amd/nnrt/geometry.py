@@ -666,7 +666,37 @@ def compute_ordered_point_cloud_normals(point_cloud, source_image_size) -> torch
     return out
 
 
+def join_triangle_meshes(meshes) -> TriangleMesh:
+    """JoinTriangleMeshes (cpp/geometry/functional/JoinTriangleMeshes.cpp): one mesh of all of them in order. Positions,
+    normals and colours are concatenated, triangle indices offset by the vertices ahead of their mesh; an attribute that
+    not all meshes carry is dropped. Face f of mesh m becomes face (faces ahead of m) + f, the numbering of
+    get_mesh_ndc_face_vertices_and_clip_mask over the same list. Tensors stay where the first mesh's positions are (numpy:
+    the host); no kernel runs."""
+    meshes = list(meshes)
+    if not meshes:
+        raise RuntimeError("join_triangle_meshes needs at least one mesh.")
+    for m in meshes:
+        if m.vertex_positions is None or m.triangle_indices is None:
+            raise RuntimeError("Every mesh needs both vertex positions and triangle indices to be joined.")
+    first = meshes[0].vertex_positions
+    dev = first.device if isinstance(first, torch.Tensor) else torch.device("cpu")
+
+    def column(name, dtype, width=3):
+        parts = [getattr(m, name) for m in meshes]
+        if any(p is None for p in parts):
+            return None
+        return torch.cat([to_device(p, dtype, dev).reshape(-1, width) for p in parts])
+
+    counts = [int(to_device(m.vertex_positions, torch.float32, dev).reshape(-1, 3).shape[0]) for m in meshes]
+    offsets = np.concatenate([[0], np.cumsum(counts)[:-1]])
+    triangles = torch.cat([to_device(m.triangle_indices, torch.int64, dev).reshape(-1, 3) + int(o) for m, o in zip(meshes, offsets)])
+    return TriangleMesh(column("vertex_positions", torch.float32), column("vertex_normals", torch.float32), triangles,
+                        column("triangle_normals", torch.float32), column("vertex_colors", torch.float32),
+                        column("triangle_colors", torch.float32))
+
+
 functional = types.SimpleNamespace(
+    join_triangle_meshes=join_triangle_meshes,
     compute_triangle_normals=compute_triangle_normals,
     compute_vertex_normals=compute_vertex_normals,
     compute_ordered_point_cloud_normals=compute_ordered_point_cloud_normals,

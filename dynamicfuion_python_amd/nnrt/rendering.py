@@ -2,12 +2,16 @@
 from __future__ import annotations
 
 import ctypes
+import math
 import types
+from dataclasses import dataclass
 
 import numpy as np
 import torch
 
 from .. import _native as N
+from . import geometry as _geometry
+from . import image_proc
 from ._overloads import Overloaded
 from ._tensors import to_device, to_host_f64
 
@@ -107,3 +111,217 @@ def interpolate_vertex_attributes(pixel_face_indices, barycentric_coordinates, f
 
 functional = types.SimpleNamespace(get_mesh_ndc_face_vertices_and_clip_mask=get_mesh_ndc_face_vertices_and_clip_mask,
                                    interpolate_vertex_attributes=interpolate_vertex_attributes)
+
+
+# ---- shaders (csrc/shading.hip) --------------------------------------------------------------------------
+SHADE_VERTEX_COLOR, SHADE_FLAT_EDGE, SHADE_HEADLIGHT = 0, 1, 2
+NDC_REFERENCE, NDC_CONSISTENT = 0, 1   # nnrt_fitter_params.ndc_convention
+
+
+def _one_mesh(meshes):
+    """None, a mesh or a list of meshes -> None or one mesh, the list joined in mesh order."""
+    if meshes is None:
+        return None
+    if isinstance(meshes, (list, tuple)):
+        if len(meshes) == 0:
+            return None
+        return meshes[0] if len(meshes) == 1 else _geometry.join_triangle_meshes(meshes)
+    return meshes
+
+
+def _color3(color, name):
+    c = np.ascontiguousarray(np.asarray(color, np.float32).reshape(-1))
+    if c.shape != (3,):
+        raise ValueError(f"{name} must have three components, got {c.shape[0]}")
+    return c
+
+
+def _shade(mode, pixel_face_indices, pixel_barycentric_coordinates, pixel_face_distances, mesh, color, pixel_line_width, ambient):
+    dev = _dev()
+    pf = to_device(pixel_face_indices, torch.int64, dev)
+    if pf.dim() != 3:
+        raise ValueError(f"pixel_face_indices must be [H, W, K], got {tuple(pf.shape)}")
+    H, W, K = pf.shape
+    bary = to_device(pixel_barycentric_coordinates, torch.float32, dev)
+    dist = to_device(pixel_face_distances, torch.float32, dev)
+    if tuple(bary.shape) != (H, W, K, 3) or tuple(dist.shape) != (H, W, K):
+        raise ValueError(f"fragment shapes disagree: faces {tuple(pf.shape)}, barycentrics {tuple(bary.shape)}, distances {tuple(dist.shape)}")
+    tri = colors = normals = None
+    face_count = vertex_count = 0
+    if mesh is not None and mode != SHADE_FLAT_EDGE:
+        tri = to_device(mesh.triangle_indices, torch.int64, dev).reshape(-1, 3)
+        face_count = tri.shape[0]
+        attribute = to_device(mesh.vertex_colors if mode == SHADE_VERTEX_COLOR else mesh.vertex_normals, torch.float32, dev).reshape(-1, 3)
+        vertex_count = attribute.shape[0]
+        colors, normals = (attribute, None) if mode == SHADE_VERTEX_COLOR else (None, attribute)
+    out = torch.empty((H, W, 3), dtype=torch.uint8, device=dev)
+    N.check(N.lib().nnrt_shade_pixels(mode, N.ptr(pf), N.ptr(bary), N.ptr(dist), H, W, K, N.ptr(tri), face_count, N.ptr(colors), N.ptr(normals),
+                                      vertex_count, N.ptr(color), float(pixel_line_width), float(ambient), N.ptr(out), N.stream_ptr()))
+    return out
+
+
+class VertexColorShader:
+    """VertexColorShader (cpp/rendering/VertexColorShader.cpp:29-61): the front fragment's barycentric mix of its face's
+    vertex colours, times 255, as uint8 (values outside [0, 255] are clamped: DESIGN §22)."""
+
+    def shade_meshes(self, pixel_face_indices, pixel_depths, pixel_barycentric_coordinates, pixel_face_distances, meshes=None):
+        mesh = _one_mesh(meshes)
+        if mesh is None:
+            raise RuntimeError("VertexColorShader requires meshes argument to be filled with meshes that were used during rasterization "
+                               "resulting in its other arguments, in order to retrieve and interpolate the vertex colors.")
+        if mesh.vertex_colors is None:
+            raise RuntimeError("VertexColorShader requires every mesh to have vertex_colors.")
+        return _shade(SHADE_VERTEX_COLOR, pixel_face_indices, pixel_barycentric_coordinates, pixel_face_distances, mesh, None, 0.0, 0.0)
+
+
+class FlatEdgeShader:
+    """FlatEdgeShader (cpp/rendering/FlatEdgeShader.cpp, kernel/FlatEdgeShaderImpl.h:66-98): pixels whose front fragment lies
+    within the line width of its face's edge, fading from line_color at the edge to black; needs a rasterization with a
+    blur radius of at least the line width to see both sides of an edge. Needs no meshes."""
+
+    def __init__(self, pixel_line_width, line_color):
+        self.set_pixel_line_width(pixel_line_width)
+        self.set_line_color(line_color)
+
+    def set_pixel_line_width(self, width):
+        self.pixel_line_width = float(width)
+
+    def set_line_color(self, color):
+        self.line_color = tuple(float(c) for c in _color3(color, "line_color"))
+
+    def get_ndc_line_width(self, image_height, image_width) -> float:
+        """ImageSpaceDistanceToNdc (CoordinateSystemConversions.h:98-101), in float32."""
+        return float(np.float32(self.pixel_line_width) / (np.float32(min(int(image_height), int(image_width))) / np.float32(2.0)))
+
+    def shade_meshes(self, pixel_face_indices, pixel_depths, pixel_barycentric_coordinates, pixel_face_distances, meshes=None):
+        return _shade(SHADE_FLAT_EDGE, pixel_face_indices, pixel_barycentric_coordinates, pixel_face_distances, None,
+                      _color3(self.line_color, "line_color"), self.pixel_line_width, 0.0)
+
+
+class HeadlightShader:
+    """Lambertian shading under a light along the optical axis (the reference has no lit shader): color times
+    ambient + (1 - ambient) max(0, -n_z / |n|) of the interpolated camera-space vertex normal."""
+
+    def __init__(self, color=(0.8, 0.8, 0.8), ambient=0.1):
+        self.color = tuple(float(c) for c in _color3(color, "color"))
+        self.ambient = float(ambient)
+
+    def shade_meshes(self, pixel_face_indices, pixel_depths, pixel_barycentric_coordinates, pixel_face_distances, meshes=None):
+        mesh = _one_mesh(meshes)
+        if mesh is None:
+            raise RuntimeError("HeadlightShader requires the meshes that were rasterized, for their vertex normals.")
+        if mesh.vertex_normals is None:
+            raise RuntimeError("HeadlightShader requires every mesh to have vertex_normals.")
+        return _shade(SHADE_HEADLIGHT, pixel_face_indices, pixel_barycentric_coordinates, pixel_face_distances, mesh,
+                      _color3(self.color, "color"), 0.0, self.ambient)
+
+
+def _to_camera_space(mesh, extrinsics, dev):
+    """World-space mesh -> camera space on the device: p' = R p + t, n' = R n (float32); the identity changes nothing."""
+    E = to_host_f64(extrinsics).reshape(4, 4)
+    p = to_device(mesh.vertex_positions, torch.float32, dev).reshape(-1, 3)
+    n = None if mesh.vertex_normals is None else to_device(mesh.vertex_normals, torch.float32, dev).reshape(-1, 3)
+    if not np.array_equal(E, np.eye(4)):
+        R = torch.as_tensor(E[:3, :3], dtype=torch.float32, device=dev)
+        t = torch.as_tensor(E[:3, 3], dtype=torch.float32, device=dev)
+        p = p @ R.T + t
+        n = None if n is None else n @ R.T
+    return _geometry.TriangleMesh(p, n, to_device(mesh.triangle_indices, torch.int64, dev).reshape(-1, 3), None,
+                                  None if mesh.vertex_colors is None else to_device(mesh.vertex_colors, torch.float32, dev).reshape(-1, 3))
+
+
+def rasterize_meshes(meshes, intrinsic_matrix, image_size, extrinsics=np.eye(4), blur_radius_pixels=0.0, faces_per_pixel=1,
+                     near_clipping_distance=0.0, far_clipping_distance=float("inf"), cull_back_faces=True, ndc_convention=NDC_REFERENCE):
+    """render_meshes without the shader: (fragments, the meshes in camera space on the device)."""
+    _check_clipping(image_size, near_clipping_distance, far_clipping_distance)
+    dev = _dev()
+    mesh_list = list(meshes) if isinstance(meshes, (list, tuple)) else [meshes]
+    camera = [_to_camera_space(m, extrinsics, dev) for m in mesh_list]
+    H, W = int(image_size[0]), int(image_size[1])
+    consistent = int(ndc_convention) == NDC_CONSISTENT
+    # the consistent mapping does not mirror y, which turns the winding in NDC: extract with two vertices swapped, as the
+    # fitter does, and swap the barycentrics back
+    faces = [m.triangle_indices[:, [0, 2, 1]].contiguous() if consistent else m.triangle_indices for m in camera]
+    counts = np.array([f.shape[0] for f in faces], np.int64)
+    total = int(counts.sum())
+    K = to_host_f64(intrinsic_matrix)
+    ndc = torch.empty((total, 3, 3), dtype=torch.float32, device=dev)
+    mask = torch.empty(total, dtype=torch.uint8, device=dev)
+    vptr = (ctypes.c_void_p * max(len(camera), 1))(*[m.vertex_positions.data_ptr() for m in camera])
+    fptr = (ctypes.c_void_p * max(len(camera), 1))(*[f.data_ptr() for f in faces])
+    N.check(N.lib().nnrt_get_meshes_ndc_face_vertices_and_clip_mask_in_convention(
+        vptr, fptr, N.ptr(counts), len(camera), N.ptr(K), H, W, float(near_clipping_distance), float(far_clipping_distance),
+        NDC_CONSISTENT if consistent else NDC_REFERENCE, N.ptr(ndc), N.ptr(mask), N.stream_ptr()))
+    fi, depths, bary, dist = rasterize_ndc_triangles(ndc, mask, (H, W), blur_radius_pixels, faces_per_pixel, cull_back_faces=cull_back_faces)
+    if consistent:
+        bary = bary[..., [0, 2, 1]].contiguous()
+    return (fi, depths, bary, dist), camera
+
+
+def render_meshes(meshes, intrinsic_matrix, image_size, shader, extrinsics=np.eye(4), blur_radius_pixels=0.0, faces_per_pixel=1,
+                  near_clipping_distance=0.0, far_clipping_distance=float("inf"), cull_back_faces=True, ndc_convention=NDC_REFERENCE):
+    """World-space mesh or meshes -> (image uint8 [H, W, 3], fragments): to camera space by `extrinsics` (world -> camera),
+    NDC extraction, rasterization, `shader`.shade_meshes. `fragments` are the rasterizer's four tensors (face indices,
+    depths, barycentrics, distances), faces numbered over the meshes in order. ndc_convention: NDC_REFERENCE is
+    get_mesh_ndc_face_vertices_and_clip_mask's mapping (reference quirk A11: rows mirrored about cy); NDC_CONSISTENT puts
+    pixel (u, v) of the intrinsics on raster pixel (u, v), which a render compared with a depth frame needs. The
+    barycentrics refer to the meshes' own triangles in both."""
+    fragments, camera = rasterize_meshes(meshes, intrinsic_matrix, image_size, extrinsics, blur_radius_pixels, faces_per_pixel,
+                                         near_clipping_distance, far_clipping_distance, cull_back_faces, ndc_convention)
+    return shader.shade_meshes(*fragments, camera), fragments
+
+
+@dataclass
+class DepthAgreement:
+    """Statistics of rasterized model depth minus frame depth over the pixels valid on both sides (`both`); `model_only` and
+    `frame_only` count the pixels valid on one side; `inliers` those of `both` with |d| <= the inlier threshold."""
+    both: int = 0
+    model_only: int = 0
+    frame_only: int = 0
+    inliers: int = 0
+    sum_abs: float = 0.0
+    sum_sq: float = 0.0
+    max_abs: float = 0.0
+
+    @property
+    def mean_abs(self) -> float:
+        return self.sum_abs / self.both if self.both else 0.0
+
+    @property
+    def rmse(self) -> float:
+        return math.sqrt(self.sum_sq / self.both) if self.both else 0.0
+
+    @property
+    def inlier_ratio(self) -> float:
+        return self.inliers / self.both if self.both else 0.0
+
+
+class _DepthAgreementRecord(ctypes.Structure):
+    _fields_ = [("both", ctypes.c_int64), ("model_only", ctypes.c_int64), ("frame_only", ctypes.c_int64), ("inliers", ctypes.c_int64),
+                ("sum_abs", ctypes.c_double), ("sum_sq", ctypes.c_double), ("max_abs", ctypes.c_float), ("reserved", ctypes.c_int32)]
+
+
+def compare_depth_to_raster(pixel_face_indices, pixel_depths, depth, depth_scale=1000.0, depth_max=3.0, inlier_threshold=0.01):
+    """Rasterized model depth (slot 0; valid where the face is >= 0) against a depth frame [H, W], uint16 in sensor units or
+    float32 (valid iff 0 < raw / depth_scale < depth_max): (DepthAgreement, difference image [H, W] float32 on the device,
+    model - frame in metres, NaN where either side is invalid). The sums are reproducible (csrc/shading.hip)."""
+    dev = _dev()
+    pf = to_device(pixel_face_indices, torch.int64, dev)
+    pd = to_device(pixel_depths, torch.float32, dev)
+    if pf.dim() != 3 or pd.shape != pf.shape:
+        raise ValueError(f"pixel_face_indices and pixel_depths must both be [H, W, K], got {tuple(pf.shape)} and {tuple(pd.shape)}")
+    H, W, K = pf.shape
+    if image_proc._is_depth_u16(depth):
+        d, code = image_proc._depth_on_device(depth, torch.int16), image_proc.DTYPE_UINT16
+    elif (isinstance(depth, np.ndarray) and depth.dtype == np.float32) or (isinstance(depth, torch.Tensor) and depth.dtype == torch.float32):
+        d, code = image_proc._depth_on_device(depth, torch.float32), image_proc.DTYPE_FLOAT32
+    else:
+        raise ValueError("depth must be a uint16 or float32 image (numpy or torch)")
+    if tuple(d.shape) != (H, W):
+        raise ValueError(f"depth must be [{H}, {W}] like the fragments, got {tuple(d.shape)}")
+    difference = torch.empty((H, W), dtype=torch.float32, device=dev)
+    record = _DepthAgreementRecord()
+    N.check(N.lib().nnrt_compare_depth_to_raster(N.ptr(pf), N.ptr(pd), H, W, K, N.ptr(d), code, float(depth_scale), float(depth_max),
+                                                 float(inlier_threshold), N.ptr(difference), ctypes.byref(record), N.stream_ptr()))
+    return DepthAgreement(int(record.both), int(record.model_only), int(record.frame_only), int(record.inliers), float(record.sum_abs),
+                          float(record.sum_sq), float(record.max_abs)), difference

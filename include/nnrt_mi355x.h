@@ -322,6 +322,16 @@ nnrt_status nnrt_get_meshes_ndc_face_vertices_and_clip_mask(const float* const* 
                                                             const int64_t* h_face_counts, int32_t mesh_count, const double* h_K,
                                                             int32_t height, int32_t width, float near_clip, float far_clip,
                                                             float* d_face_ndc, uint8_t* d_clip_mask, void* stream);
+/* The same with the image -> NDC mapping chosen: NNRT_NDC_REFERENCE is the function above; NNRT_NDC_CONSISTENT puts pixel
+ * (u, v) of K on the centre of raster pixel (u, v) with the image as the clip window (nnrt_fitter_params.ndc_convention),
+ * which a render that is compared with a depth frame needs. That mapping does not mirror y, so it turns every face's
+ * winding in NDC: a caller that culls back faces swaps two vertices of each face first, as the fitter does. Any other
+ * ndc_convention is NNRT_ERROR_ARGUMENT. */
+nnrt_status nnrt_get_meshes_ndc_face_vertices_and_clip_mask_in_convention(const float* const* h_vertex_sets, const int64_t* const* h_face_sets,
+                                                                          const int64_t* h_face_counts, int32_t mesh_count, const double* h_K,
+                                                                          int32_t height, int32_t width, float near_clip, float far_clip,
+                                                                          int32_t ndc_convention, float* d_face_ndc, uint8_t* d_clip_mask,
+                                                                          void* stream);
 /* nnrt.rendering.functional.get_mesh_ndc_face_vertices_and_clip_mask (cpp/rendering/functional/ExtractFaceVertices.cpp:56-85).
  * d_face_ndc [F,3,3], d_clip_mask [F] uint8 (1 = keep). */
 nnrt_status nnrt_get_mesh_ndc_face_vertices_and_clip_mask(const float* d_vertices, const int64_t* d_faces, int64_t face_count,
@@ -384,6 +394,58 @@ nnrt_status nnrt_filter_depth(const uint16_t* d_in, int32_t height, int32_t widt
 nnrt_status nnrt_bilateral_filter_depth(const void* d_in, int32_t in_dtype, int32_t height, int32_t width, int32_t radius,
                                         const float* h_spatial_weights, const float* h_range_weights, int32_t range_weight_count,
                                         float range_index_scale, float depth_scale, float* d_out, void* stream);
+/* Shaders: the front fragment (slot 0 of the faces_per_pixel slots) of every pixel of a rasterization -> d_out_pixels
+ * [H,W,3] uint8 RGB. Every pixel is written; a pixel whose slot-0 face is negative is (0,0,0). Fragments as
+ * nnrt_rasterize_ndc_triangles writes them: d_pixel_face_indices [H,W,K] int64, d_pixel_barycentric_coordinates
+ * [H,W,K,3], d_pixel_face_distances [H,W,K]. Mesh data: d_triangle_indices [face_count,3] int64 over the joined meshes
+ * (faces numbered as nnrt_get_meshes_ndc_face_vertices_and_clip_mask numbers them), d_vertex_colors and
+ * d_vertex_normals [vertex_count,3] float32; the reference's gathered [F,3,3] face attributes are never formed. A face
+ * index >= face_count or a vertex index outside [0, vertex_count) is drawn as background. byte(x) truncates the float32
+ * product toward zero, with x <= 0 and NaN -> 0 and x >= 255 -> 255 (the reference's cast is undefined there). float32
+ * arithmetic, unfused, in this order:
+ *   NNRT_SHADE_VERTEX_COLOR  VertexColorShader::ShadeMeshes (cpp/rendering/VertexColorShader.cpp:29-61 over
+ *     InterpolateFaceAttributesImpl.h:60-66): per channel a = 0; a += b0 c0; a += b1 c1; a += b2 c2; byte(a * 255).
+ *   NNRT_SHADE_FLAT_EDGE     FlatEdgeShader (cpp/rendering/kernel/FlatEdgeShaderImpl.h:66-98, FlatEdgeShader.cpp:56-58,
+ *     CoordinateSystemConversions.h:98-101): w = pixel_line_width / (min(H, W) / 2), w2 = w w, d = |distance|; if
+ *     d < w2 every channel is byte(255 * color_c * ((w2 - d) / w2)), else 0. h_color [3] is the line colour.
+ *   NNRT_SHADE_HEADLIGHT     (not in the reference) n = (b0 n0 + b1 n1) + b2 n2 of camera-space vertex normals,
+ *     s = max(0, -n_z / |n|), 0 if |n| is 0 or not finite; byte(255 * color_c * (ambient + (1 - ambient) s)).
+ * Refused on the host with NNRT_ERROR_ARGUMENT before any device work, naming the argument: an unknown mode, a negative
+ * height, width, face_count or vertex_count, faces_per_pixel < 1, pixel_line_width <= 0 (FLAT_EDGE; the reference raises
+ * there), ambient outside [0, 1] (HEADLIGHT), a null h_color (FLAT_EDGE, HEADLIGHT), null d_vertex_colors (VERTEX_COLOR)
+ * or d_vertex_normals (HEADLIGHT) with vertex_count > 0, null d_triangle_indices with face_count > 0 (VERTEX_COLOR,
+ * HEADLIGHT), and, for a non-empty image, a null fragment array the mode reads, a null d_out_pixels, or d_out_pixels
+ * overlapping an input. height == 0 or width == 0 is no error and launches nothing. */
+#define NNRT_SHADE_VERTEX_COLOR 0
+#define NNRT_SHADE_FLAT_EDGE 1
+#define NNRT_SHADE_HEADLIGHT 2
+nnrt_status nnrt_shade_pixels(int32_t mode, const int64_t* d_pixel_face_indices, const float* d_pixel_barycentric_coordinates,
+                              const float* d_pixel_face_distances, int32_t height, int32_t width, int32_t faces_per_pixel,
+                              const int64_t* d_triangle_indices, int64_t face_count, const float* d_vertex_colors,
+                              const float* d_vertex_normals, int64_t vertex_count, const float* h_color, float pixel_line_width,
+                              float ambient, uint8_t* d_out_pixels, void* stream);
+/* The rasterized model depth (slot 0 of d_pixel_depths [H,W,K], valid where d_pixel_face_indices [H,W,K] >= 0) against a
+ * depth frame d_depth [H,W], uint16 (NNRT_DTYPE_UINT16) or float32 (NNRT_DTYPE_FLOAT32). A frame pixel is valid iff
+ * z = raw / depth_scale (float32) satisfies 0 < z < depth_max, which NaN fails: the rule of nnrt_unproject_depth_image
+ * (PerspectiveProjectionImpl.h:60-146). d_out_difference [H,W] float32 receives model - frame in metres, NaN where
+ * either side is invalid. *h_out_statistics receives the counts of pixels valid on both sides, on the model's only and
+ * on the frame's only, and over the pixels valid on both sides, with d the float32 difference: the count of
+ * |d| <= inlier_threshold, the float64 sums of |d| and of |d|^2 and the largest |d|. The sums are reproducible (fixed
+ * order, no atomics: DESIGN.md section 22). Synchronizes `stream`. Refused on the host with NNRT_ERROR_ARGUMENT before
+ * any device work, naming the argument: a null h_out_statistics, a negative height or width, faces_per_pixel < 1, an
+ * unknown depth_dtype, a depth_scale that is not finite and positive, a NaN depth_max, a negative or NaN
+ * inlier_threshold, and, for a non-empty image, a null array or d_out_difference overlapping an input. height == 0 or
+ * width == 0 is no error and launches nothing; the statistics are then all zero. */
+typedef struct nnrt_depth_agreement {
+	int64_t both, model_only, frame_only, inliers;
+	double sum_abs, sum_sq;
+	float max_abs;
+	int32_t reserved;   /* 0 */
+} nnrt_depth_agreement;
+nnrt_status nnrt_compare_depth_to_raster(const int64_t* d_pixel_face_indices, const float* d_pixel_depths, int32_t height, int32_t width,
+                                         int32_t faces_per_pixel, const void* d_depth, int32_t depth_dtype, float depth_scale,
+                                         float depth_max, float inlier_threshold, float* d_out_difference,
+                                         nnrt_depth_agreement* h_out_statistics, void* stream);
 /* nnrt.geometry.functional.compute_triangle_normals(mesh, normalized=True) (cpp/geometry/functional/NormalsOperations.cpp:36-46,
  * kernel NormalsOperationsImpl.h:39-68): d_out [F,3] = (v1 - v0) x (v2 - v0), optionally normalized (zero stays zero,
  * NaN -> (0,0,1)) */
