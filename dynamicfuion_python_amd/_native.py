@@ -78,6 +78,7 @@ _SIGNATURES = {
     "nnrt_fitter_graph_count": (c_int32, [c_void_p]),
     "nnrt_fitter_corner_info": (c_int32, [c_void_p, c_void_p]),
     "nnrt_fitter_corner_work": (c_int32, [c_void_p, c_void_p]),
+    "nnrt_fitter_launch_plan": (c_int32, [c_void_p, c_void_p, c_int64]),
     "nnrt_fitter_get_arrowhead_system": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_void_p]),
     "nnrt_fitter_get_warped_mesh": (c_int32, [c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
     "nnrt_release_arrowhead_plans": (None, []),

@@ -409,11 +409,6 @@ __global__ __launch_bounds__(256) void k_warp_mesh_vertex(const float* __restric
 	out_n[v] = make_float4(wn.x, wn.y, wn.z, 0.f);
 }
 
-static bool warp_vertex_path(int64_t V) {
-	if (const char* e = std::getenv("NNRT_WARP_VERTEX")) return *e == '1';   // development switch: 0 / 1 force a path
-	return V >= (int64_t{1} << 16);
-}
-
 // [V, 4] int32 anchors (every index < 65535, -1 for none) -> 4 x 16 bits per vertex (0xFFFF: none), for the
 // lane-per-vertex warp's anchor loads (C3: 36 of its ~200 MB per launch as int32)
 __global__ void k_pack_anchors16(const int4* __restrict__ anchors, int64_t V, uint2* __restrict__ out) {
@@ -432,9 +427,9 @@ nnrt_status launch_pack_anchors16(const int32_t* anchors, int64_t V, uint2* out,
 
 nnrt_status launch_warp_mesh(const float* points, const float* normals, int64_t V, const float* node_state, const int32_t* anchors,
                              const float* weights, int K, const WarpExtrinsics& E, float4* out_p, float4* out_n, float2* jrows,
-                             hipStream_t stream, bool from_identity, const uint2* anchors16) {
+                             bool vertex_path, hipStream_t stream, bool from_identity, const uint2* anchors16) {
 	if (V == 0) return NNRT_OK;
-	if (K <= 4 && !jrows && warp_vertex_path(V)) {
+	if (K <= 4 && !jrows && vertex_path) {
 		const unsigned grid = static_cast<unsigned>(ceil_div(V, 256));
 		const bool vec4 = K == 4 && (reinterpret_cast<uintptr_t>(anchors) & 15) == 0 && (reinterpret_cast<uintptr_t>(weights) & 15) == 0;
 		if (from_identity) {

@@ -98,9 +98,10 @@ nnrt_status launch_rigid_align(const float* points, const float* normals, int64_
                                int W, float fx, float fy, float cx, float cy, const double* h_T_init, int iterations, float distance_threshold,
                                float normal_agreement_cos, int cull_back_faces, int minimum_correspondence_count, double* h_T_out, double* h_log,
                                int32_t* h_status, hipStream_t stream);
+// vertex_path: the lane-per-vertex kernels where K <= 4 and no rows are gathered (launch_plan.hpp choose_warp_vertex)
 nnrt_status launch_warp_mesh(const float* points, const float* normals, int64_t V, const float* node_state, const int32_t* anchors,
                              const float* weights, int K, const WarpExtrinsics& E, float4* out_p, float4* out_n, float2* jrows,
-                             hipStream_t stream, bool from_identity = false, const uint2* anchors16 = nullptr);
+                             bool vertex_path, hipStream_t stream, bool from_identity = false, const uint2* anchors16 = nullptr);
 // K = 4 anchors with every index below 65535 as 4 x 16 bits per vertex (the lane-per-vertex warp's anchors16)
 nnrt_status launch_pack_anchors16(const int32_t* anchors, int64_t V, uint2* out, hipStream_t stream);
 nnrt_status launch_pack_nodes(const float* nodes, const float* R, const float* t, int N, float* state, hipStream_t stream);
@@ -186,11 +187,11 @@ nnrt_status launch_raster_scatter_ndc(const float* face_ndc, const uint8_t* mask
 nnrt_status launch_raster_resolve(const float* face_ndc, int64_t F, const RasterOptions& o, uint64_t* keys, int64_t* out_face,
                                   float* out_depth, float* out_bary, float* out_dist, hipStream_t stream);
 nnrt_status launch_raster_scatter_mesh(const float4* wpos, const int4* faces4, int64_t F, const NdcSetup& s, float near_clip, float far_clip,
-                                       const RasterOptions& o, uint64_t* keys, hipStream_t stream);
+                                       const RasterOptions& o, uint64_t* keys, bool dense, hipStream_t stream);
 nnrt_status launch_raster_multi(const float* face_ndc, const uint8_t* mask, int64_t F, const RasterOptions& o, int faces_per_pixel,
                                 int64_t* out_face, float* out_depth, float* out_bary, float* out_dist, hipStream_t stream);
 
-// read-only device view of a warp field (capi.hip owns the handle; the TSDF kernels warp voxels with it)
+// read-only device view of a warp field (handles.hpp defines the handle, capi.hip exports it; the TSDF kernels warp voxels with it)
 struct WarpFieldView {
 	int N, anchor_count, minimum_valid, fixed_coverage;
 	float coverage;                 // node coverage (fixed-coverage weights use coverage^2)

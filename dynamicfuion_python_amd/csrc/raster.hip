@@ -481,16 +481,11 @@ __global__ __launch_bounds__(SCATTER_BLOCK) void k_raster_scatter_mesh_dense(con
 	scatter_wave(fn, ok, static_cast<int32_t>(face0), o, keys, s_wave[threadIdx.x >> 6]);
 }
 
-bool raster_mesh_dense(int64_t F, const RasterOptions& o) {
-	if (const char* v = std::getenv("NNRT_RASTER_DENSE")) return *v == '1';   // development switch: 0 / 1 force a path
-	return F >= static_cast<int64_t>(o.H) * o.W;
-}
-
 nnrt_status launch_raster_scatter_mesh(const float4* wpos, const int4* faces4, int64_t F, const NdcSetup& s, float near_clip, float far_clip,
-                                       const RasterOptions& o, uint64_t* keys, hipStream_t stream) {
+                                       const RasterOptions& o, uint64_t* keys, bool dense, hipStream_t stream) {
 	if (F == 0) return NNRT_OK;
 	NNRT_CHECK_ARG(o.W < 65536 && F < (int64_t(1) << 31), "image wider than 65535 pixels or more than 2^31 faces");
-	if (raster_mesh_dense(F, o)) {
+	if (dense) {
 		k_raster_scatter_mesh_dense<<<static_cast<unsigned>(ceil_div(F, SCATTER_WAVES * DENSE_FPW)), SCATTER_BLOCK, 0, stream>>>(wpos, faces4, F, s, near_clip,
 		                                                                                                                   far_clip, o, keys);
 		NNRT_LAUNCH_CHECK();

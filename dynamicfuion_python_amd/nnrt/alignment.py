@@ -264,6 +264,14 @@ class DeformableMeshToImageFitter:
         keys = ("corner_nodes", "tile_columns", "factor_launches", "back_launches", "stored_tiles", "dense_lower_tiles")
         return {k: int(v) for k, v in zip(keys, out)}
 
+    def launch_plan(self) -> dict:
+        """Launch choices of the last prepared frame (csrc/launch_plan.hpp), 0 / 1 each: which pixel-launch order table and
+        build, anchor format, warp kernel and raster kernel its iterations use."""
+        out = np.zeros(6, np.int32)
+        N.check(N.lib().nnrt_fitter_launch_plan(self._h, N.ptr(out), out.size))
+        keys = ("tile_order", "quad_order", "pix_low_occupancy", "anchors16", "warp_vertex", "raster_dense")
+        return {k: int(v) for k, v in zip(keys, out)}
+
     def arrowhead_system(self, node_count: int, edge_count: int, stream=None):
         """The last ARAP iteration's float arrowhead system as the fitter solved it (virtual order): diagonal blocks
         [N,6,6] with LM, wing blocks [E,6,6] (block (i, j) of edge (i, j)), right-hand side [6N]."""

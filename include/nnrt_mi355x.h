@@ -170,6 +170,9 @@ int32_t nnrt_fitter_graph_count(const nnrt_fitter* fitter);
  * 64-unknown tile columns, factorization launches (elimination-tree levels), back-substitution launches, stored
  * (structurally non-zero) tiles, lower tiles of the dense corner. */
 nnrt_status nnrt_fitter_corner_info(const nnrt_fitter* fitter, int64_t* h_out);
+/* h_out[0..count): tile_order, quad_order, pix_low_occupancy, anchors16, warp_vertex, raster_dense (0/1) of the
+   last prepared frame; count must be >= 6 (NNRT_ERROR_ARGUMENT otherwise, and before prepare). */
+nnrt_status nnrt_fitter_launch_plan(const nnrt_fitter* fitter, int32_t* h_out, int64_t count);
 /* Work of that plan's factorization as executed (diagnostic; zeros without ARAP): h_out[3] = MFMA flops per
  * factorization (every update term's 64 x 64 x 64 tile product + the rank-32 products of the split eliminations),
  * update terms, tile-column eliminations (real columns summed). The reference's dense count is (6 n1)^3 / 3 + ... */

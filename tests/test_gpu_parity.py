@@ -98,6 +98,8 @@ def test_fitter_warp_bit_exact(nn, S, oracle_mod, name, from_identity, vertex_pa
     sc = _scene(S, oracle_mod, name)
     depth = scene_target(oracle_mod, sc)
     wf, ft = _new_fit(nn, sc, depth, 1)
+    plan = ft.launch_plan()   # the forced paths are the ones the frame runs (4 anchors, fewer than 65535 nodes)
+    assert plan["warp_vertex"] == int(vertex_path[0]) and plan["anchors16"] == (0 if vertex_path.endswith("int32") else 1)
     V, Nn = len(sc.points), len(sc.nodes)
     if from_identity:
         ft.iterate_from_identity(wf, 0, 1)
@@ -989,6 +991,77 @@ def test_graph_policy_and_cache_invalidation(nn, S, oracle_mod):
     ft.fit_to_image(wf, mesh, None, depth, None, K2, None, 1.0)
     assert lib.nnrt_fitter_graph_count(ft._h) == 0
     assert rel_err(wf.get_node_translations(), t2) < 1e-6
+    # the two launcher switches are part of what a graph bakes in: changing one between frames drops the graphs, the
+    # next frame runs the newly chosen kernel and the one after it captures again (same inputs throughout)
+    import os
+    switches = ("NNRT_RASTER_DENSE", "NNRT_WARP_VERTEX")
+    old = {k: os.environ.get(k) for k in switches}
+    try:
+        for k in switches:
+            os.environ.pop(k, None)
+        wf.reset_motion()
+        ft.fit_to_image(wf, mesh, None, depth, None, K2, None, 1.0)
+        assert lib.nnrt_fitter_graph_count(ft._h) == 1
+        assert ft.launch_plan()["raster_dense"] == 0 and ft.launch_plan()["warp_vertex"] == 0   # S1's defaults
+        for k, choice in zip(switches, ("raster_dense", "warp_vertex")):
+            os.environ[k] = "1"
+            wf.reset_motion()
+            ft.fit_to_image(wf, mesh, None, depth, None, K2, None, 1.0)
+            assert lib.nnrt_fitter_graph_count(ft._h) == 0, k
+            assert ft.launch_plan()[choice] == 1, k
+            wf.reset_motion()
+            ft.fit_to_image(wf, mesh, None, depth, None, K2, None, 1.0)
+            assert lib.nnrt_fitter_graph_count(ft._h) == 1, k
+            assert np.array_equal(ft.diagnostics()["pixel_faces"], d2["pixel_faces"]), k
+            assert rel_err(wf.get_node_translations(), t2) < 1e-6, k
+    finally:
+        for k, v in old.items():
+            if v is None:
+                os.environ.pop(k, None)
+            else:
+                os.environ[k] = v
+
+
+def test_buffer_move_alone_drops_graphs(nn, S, oracle_mod):
+    """A captured graph bakes every buffer's address in. A mesh with a few more (unused) vertices at the same image,
+    node and anchor counts makes the per-vertex buffers grow and move: the graphs are dropped, and the reused fitter
+    equals a fresh one. This does not isolate the moved-buffer check from the frame key: the vertex count is in the key
+    too, and since the fitter's buffers only grow, and every size follows from what the key holds, no sequence of
+    prepare() calls moves a buffer without also changing the key. The check per allocation guards the sizes a later
+    change might add outside the key; what this test holds is the outcome, that no graph survives a frame whose
+    buffers moved."""
+    A, G = nn.alignment, nn.geometry
+    from dynamicfuion_python_amd import _native as NV
+    lib = NV.lib()
+    sc = _scene(S, oracle_mod, "S1")
+    depth = scene_target(oracle_mod, sc)
+    mesh = G.TriangleMesh(sc.points, sc.normals, sc.faces)
+    pad = 5   # vertices no face uses
+    points = np.concatenate([sc.points, np.repeat(sc.points[:1], pad, 0)])
+    normals = np.concatenate([sc.normals, np.repeat(sc.normals[:1], pad, 0)])
+    padded = G.TriangleMesh(points, normals, sc.faces)
+
+    def new_wf():
+        return G.HierarchicalGraphWarpField(sc.nodes, sc.coverage, False, 4, 0, G.WarpNodeCoverageComputationMethod.FIXED_NODE_COVERAGE,
+                                            sc.layer_count)
+
+    ft = A.DeformableMeshToImageFitter(2, [A.IterationMode.ALL], preconditioning_dampening_factor=0.001, use_hip_graph=1)
+    wf = new_wf()
+    for _ in range(2):   # the second request captures
+        wf.reset_motion()
+        ft.fit_to_image(wf, mesh, None, depth, None, sc.K, None, 1.0)
+    assert lib.nnrt_fitter_graph_count(ft._h) == 1
+    wf.reset_motion()
+    ft.fit_to_image(wf, padded, None, depth, None, sc.K, None, 1.0)
+    assert lib.nnrt_fitter_graph_count(ft._h) == 0
+    wf_new = new_wf()
+    ft_new = A.DeformableMeshToImageFitter(2, [A.IterationMode.ALL], preconditioning_dampening_factor=0.001, use_hip_graph=0)
+    ft_new.fit_to_image(wf_new, padded, None, depth, None, sc.K, None, 1.0)
+    dg, dg_new = ft.diagnostics(), ft_new.diagnostics()
+    for k in ("pixel_faces", "residual_mask"):
+        assert np.array_equal(dg[k], dg_new[k]), k
+    # (the second iteration starts from the first one's update, whose fp64 atomics' order differs run to run)
+    assert rel_err(wf.get_node_translations(), wf_new.get_node_translations()) < 1e-6
 
 
 @pytest.mark.parametrize("name", ["S1", "S1_ARAP"])
@@ -1307,7 +1380,8 @@ def test_pixel_tile_order_same_iteration(nn, S, oracle_mod, name):
     try:
         for v in ("2", "0"):
             os.environ["NNRT_TILE_ORDER"] = v
-            _, _, dg = _gpu_fit(nn, sc, depth, 1)
+            _, ft, dg = _gpu_fit(nn, sc, depth, 1)
+            assert ft.launch_plan()["tile_order"] == (1 if v == "2" else 0), "the forced path is not the one that ran"
             out[v] = dg
     finally:
         if old is None:
@@ -1337,7 +1411,8 @@ def test_raster_dense_path_same_iteration(nn, S, oracle_mod, name):
     try:
         for v in ("1", "0"):
             os.environ["NNRT_RASTER_DENSE"] = v
-            _, _, dg = _gpu_fit(nn, sc, depth, 1)
+            _, ft, dg = _gpu_fit(nn, sc, depth, 1)
+            assert ft.launch_plan()["raster_dense"] == (int(v)), "the forced path is not the one that ran"
             out[v] = dg
     finally:
         if old is None:
@@ -1369,7 +1444,8 @@ def test_pixel_launch_builds_same_iteration(nn, S, oracle_mod, name):
     try:
         for v in ("1", "0"):
             os.environ["NNRT_PIX_WPE4"] = v
-            _, _, dg = _gpu_fit(nn, sc, depth, 1)
+            _, ft, dg = _gpu_fit(nn, sc, depth, 1)
+            assert ft.launch_plan()["pix_low_occupancy"] == (int(v)), "the forced path is not the one that ran"
             out[v] = dg
     finally:
         if old is None:

@@ -198,6 +198,9 @@ def iterations(nn, sc, depth, mode, quad, wpe4, count=1, graph=0):
         wf = G.HierarchicalGraphWarpField(sc.nodes, sc.coverage, False, 4, 0, G.WarpNodeCoverageComputationMethod.FIXED_NODE_COVERAGE, 1)
         ft = A.DeformableMeshToImageFitter(1, [A.IterationMode[mode]], preconditioning_dampening_factor=0.001, use_hip_graph=graph)
         ft.prepare(wf, G.TriangleMesh(sc.points, sc.normals, sc.faces), np.array(depth), None, sc.K)
+        plan = ft.launch_plan()   # the forced choices are the ones the frame runs with
+        assert plan["quad_order"] == int(quad) and plan["tile_order"] == 0
+        assert wpe4 is None or plan["pix_low_occupancy"] == int(wpe4)
         for _ in range(count):
             ft.iterate(wf, 0, 1)
             dg = ft.diagnostics()

@@ -119,6 +119,23 @@ def test_diagnostic_exports_refuse_bad_arguments(native):
     assert native.jacobian_fma() is False   # the product: the reference CPU path's unfused arithmetic
 
 
+def test_launch_plan_refuses_bad_arguments(native):
+    """nnrt_fitter_launch_plan takes the caller's buffer length and checks it, and its pointers, before it reads the
+    fitter (a caller-sized host buffer is never written past). Argument checks only: nothing is launched, and the
+    stand-in handle is never dereferenced."""
+    lib = native.lib()
+    out = np.full(8, -1, np.int32)
+    handle = np.zeros(64, np.uint8)   # any non-null address: both refusals below come before the fitter is read
+    assert lib.nnrt_fitter_launch_plan(None, native.ptr(out), 6) == 1
+    assert b"null" in lib.nnrt_last_error()
+    assert lib.nnrt_fitter_launch_plan(native.ptr(handle), None, 6) == 1
+    assert b"null" in lib.nnrt_last_error()
+    for count in (5, 0, -1):
+        assert lib.nnrt_fitter_launch_plan(native.ptr(handle), native.ptr(out), count) == 1
+        assert b"count" in lib.nnrt_last_error()
+    assert (out == -1).all()
+
+
 def test_overlapping_outputs_are_rejected(native):
     """outputs that overlap an input the kernel still reads are refused before any device work (pointer
     arithmetic only, so this runs without a GPU): InvertTriangularBlocks into its own blocks, BlockSparseAndVectorProduct
