@@ -92,6 +92,10 @@ _SIGNATURES = {
     "nnrt_fitter_set_refine_ratio": (c_int32, [c_void_p, c_float]),
     "nnrt_fitter_set_robust_options": (c_int32, [c_void_p, c_int32, c_int32]),
     "nnrt_fitter_get_robust_options": (c_int32, [c_void_p, ctypes.POINTER(c_int32), ctypes.POINTER(c_int32)]),
+    "nnrt_fitter_set_data_coupling": (c_int32, [c_void_p, c_int32]),
+    "nnrt_fitter_get_data_coupling": (c_int32, [c_void_p, ctypes.POINTER(c_int32)]),
+    "nnrt_fitter_coupled_pair_count": (c_int64, [c_void_p]),
+    "nnrt_fitter_get_coupled_system": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_void_p]),
     "nnrt_fitter_set_anchor_graph": (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_void_p]),
     "nnrt_fitter_check": (c_int32, [c_void_p, c_void_p]),
     "nnrt_fitter_get_diagnostics": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),

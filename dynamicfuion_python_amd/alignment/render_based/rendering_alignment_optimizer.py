@@ -47,6 +47,9 @@ class RenderingAlignmentParameters:
     # PenaltyForm.IRLS and guard_zero_rotation=True.
     penalty_form: A.PenaltyForm = A.PenaltyForm.REFERENCE
     guard_zero_rotation: bool = False
+    # The data term's coupling across nodes (DeformableMeshToImageFitter.set_data_coupling): the reference's
+    # block-diagonal Hessian by default; real sequences want DataCoupling.COUPLED (IterationMode.ALL only).
+    data_coupling: A.DataCoupling = A.DataCoupling.BLOCK_DIAGONAL
 
 
 def as_triangle_mesh(mesh) -> G.TriangleMesh:
@@ -79,6 +82,7 @@ class RenderingAlignmentOptimizer:
             use_huber_penalty_for_arap_term=p.regularization_term_penalty_function == PenaltyFunction.HUBER,
             huber_penalty_constant=p.regularization_term_penalty_constant, device=dev, ndc_convention=p.ndc_convention,
             penalty_form=p.penalty_form, guard_zero_rotation=p.guard_zero_rotation)
+        self.fitter.set_data_coupling(A.DataCoupling(p.data_coupling))
 
     def set_anchor_graph(self, edges):
         """Anchor the canonical mesh along these edge rows ([N, D] int32, the graph's virtual node order, -1 = empty) in

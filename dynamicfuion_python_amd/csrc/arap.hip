@@ -12,6 +12,7 @@
 
 
 #include "arrow_device.hpp"
+#include "coupled.hpp"
 
 namespace nnrt {
 
@@ -564,6 +565,15 @@ nnrt_status launch_arrowhead_iteration(const ArrowheadWorkspace& ws, const doubl
 	    ws.N, lm, const_cast<double*>(acc), ws.inc_off, edge_jr, ws.diag, ws.rhs, gradient_out, hessian_out);
 	NNRT_LAUNCH_CHECK();
 	return arrowhead_solve_core(ws, edges, wing, error_flag, stream, true, node_state, updates_out, state_in);
+}
+
+// the prepare launch alone (coupled.hpp): the coupled data term assembles its pair blocks before the solve
+nnrt_status launch_arrow_prepare(int N, float lm, double* acc, const int* inc_off, const float* edge_terms, float* diag, float* rhs,
+                                 float* gradient_out, float* hessian_out, hipStream_t stream) {
+	k_arrow_prepare<<<static_cast<unsigned>(ceil_div(static_cast<int64_t>(N) * 32, 256)), 256, 0, stream>>>(N, lm, acc, inc_off, edge_terms, diag, rhs,
+	                                                                                                     gradient_out, hessian_out);
+	NNRT_LAUNCH_CHECK();
+	return NNRT_OK;
 }
 
 } // namespace nnrt

@@ -11,6 +11,7 @@
 #include <type_traits>
 #include <vector>
 
+#include "coupled.hpp"
 #include "handles.hpp"
 
 using namespace nnrt;
@@ -27,16 +28,18 @@ struct FrameKey {
 	const nnrt_warp_field* wf;
 	uint64_t wf_id;               // id of the warp field whose buffers the cached graphs captured
 	uint64_t corner_generation;   // CornerSolver::generation: the corner's plan and buffers
+	uint64_t pair_generation;     // the coupled data term's solver plan (0: block-diagonal data term)
 	int H, W, N, K;
 	int E, n0;                    // the warp field's edges and first-layer nodes (the ARAP terms' launch arguments)
 	int quad_slots;              // the pixel launch's wave slots at four waves per SIMD (launch_quad_order's overflow bound)
+	int coupled, M;              // nnrt_fitter_set_data_coupling at prepare(), and the frame's node pairs (coupled only)
 	NdcSetup ndc;
 	Camera pix;
 	WarpExtrinsics extr;
 	LaunchChoices launch;
 };
 static_assert(std::is_trivially_copyable<FrameKey>::value &&
-                  sizeof(FrameKey) == 2 * sizeof(int64_t) + sizeof(void*) + 2 * sizeof(uint64_t) + 7 * sizeof(int) + sizeof(NdcSetup) +
+                  sizeof(FrameKey) == 2 * sizeof(int64_t) + sizeof(void*) + 3 * sizeof(uint64_t) + 9 * sizeof(int) + sizeof(NdcSetup) +
                                           sizeof(Camera) + sizeof(WarpExtrinsics) + sizeof(LaunchChoices),
               "FrameKey is compared with memcmp: no padding");
 
@@ -81,6 +84,17 @@ struct nnrt_fitter {
 	// whether a node update of rotation angle exactly 0 keeps the rotation (launch arguments of every iteration)
 	int32_t penalty_form = NNRT_PENALTY_REFERENCE;
 	int32_t guard_zero_rotation = 0;
+	// nnrt_fitter_set_data_coupling: NNRT_DATA_COUPLED adds the data term's off-diagonal blocks. The
+	// pair structure, the solver plan over it (arrow base 0: every node in the corner) and the workspace are per frame.
+	int32_t data_coupling = NNRT_DATA_BLOCK_DIAGONAL;
+	PairStructure ps;
+	CornerSolver pair_corner;
+	DeviceBuffer<double> pair_acc;      // [M, 36] fp64 sums of J_a^T J_b (zeroed on the stream before every pair launch)
+	DeviceBuffer<float> pair_blocks;    // [M, 36] the system's pair blocks (data + ARAP wing blocks on the pair)
+	DeviceBuffer<int> zero_inc;         // [N + 1] zeros: the prepare launch's incidence offsets without a hierarchy
+	DeviceBuffer<int> c_edge_off;       // [1] the empty stem's edge CSR
+	DeviceBuffer<float> c_dinv;         // [1] (no stem blocks)
+	ArrowheadWorkspace cw;
 	int last_mode = 0;
 	DeviceBuffer<float> snapshot;   // [N,16] node state stored by nnrt_fitter_snapshot_motion (restore-before-iteration runs)
 	// nnrt_fitter_set_anchor_graph: edge rows [graph_nodes, graph_degree] in the warp field's virtual node order (checked
@@ -328,9 +342,28 @@ nnrt_status enqueue_iteration(nnrt_fitter* ft, const nnrt_warp_field* wf, int mo
 		fa.arap_blocks = fit_pixels_arap_blocks(ft->key.E);
 	}
 	if ((stages & STAGE_PIXEL) && (st = launch_fit_pixels(mode, fa, s, marks ? marks[3] : nullptr))) return st;
+	const bool coupled = ft->key.coupled != 0;
+	if (coupled && (stages & STAGE_PIXEL) && ft->ps.M > 0) {   // the off-diagonal data blocks: a second launch on the same stream
+		NNRT_HIP(hipMemsetAsync(ft->pair_acc.ptr, 0, sizeof(double) * 36 * static_cast<size_t>(ft->ps.M), s));
+		if ((st = launch_fit_pairs(fa, FitPairArgs{ft->ps.row_off.ptr, ft->ps.pairs.ptr, ft->pair_acc.ptr, 0}, ft->ps.M, s))) return st;
+	}
 	if ((st = mark(4))) return st;
 	if (!(stages & STAGE_SOLVE)) return mark(6);
-	if (ft->key.E > 0) {
+	if (coupled) {
+		// diagonal blocks (data + ARAP + LM) and right-hand side as on the arrowhead path, the pair blocks, then the
+		// tile-sparse solve with arrow base 0 and the node updates
+		if ((st = mark(5))) return st;
+		if ((st = launch_arrow_prepare(ft->key.N, ft->p.preconditioning_dampening_factor, ft->acc.ptr,
+		                               ft->key.E > 0 ? ft->a_inc_off.ptr : ft->zero_inc.ptr, ft->edge_jr.ptr, ft->a_diag.ptr, ft->a_rhs.ptr,
+		                               ft->gradient.ptr, ft->hessian.ptr, s)) ||
+		    (st = launch_coupled_assemble(ft->pair_acc.ptr, ft->ps.M, ft->ps.edge_off.ptr, ft->ps.edge_list.ptr, ft->wing.ptr, ft->pair_blocks.ptr, s)))
+			return st;
+		ArrowheadWorkspace cw = ft->cw;
+		cw.refine_ratio = ft->refine_ratio;
+		cw.guard_zero_rotation = ft->guard_zero_rotation;
+		if ((st = arrowhead_solve_core(cw, ft->ps.pairs.ptr, ft->pair_blocks.ptr, ft->error_flag.ptr, s, false, wf->state.ptr, ft->updates.ptr, state_in)))
+			return st;
+	} else if (ft->key.E > 0) {
 		if ((st = mark(5))) return st;
 		const float lm = ft->p.preconditioning_dampening_factor;
 		if ((st = launch_arrowhead_iteration(ft->aw, ft->acc.ptr, lm, wf->edges.ptr, ft->wing.ptr, wf->state.ptr, ft->edge_jr.ptr,
@@ -466,6 +499,10 @@ nnrt_status prepare_frame(nnrt_fitter* ft, nnrt_warp_field* wf, const float* d_v
 	key.ndc = make_ndc_setup(h_K, H, W, ft->p.ndc_convention == NNRT_NDC_CONSISTENT);
 	key.pix = pixel_camera(h_K);
 	key.extr = make_extrinsics(h_E);
+	key.coupled = ft->data_coupling == NNRT_DATA_COUPLED;
+	// the pair structure is known only after the device has built it (below): until then the last frame's
+	key.pair_generation = key.coupled ? ft->key.pair_generation : 0;
+	key.M = key.coupled ? ft->key.M : 0;
 	key.launch = choose_launches(read_launch_switches(), V, F, H, W, N, K, cus, fit_pixels_tile_order_supported());
 	// (re)allocate. Captured graphs bake every buffer's address into their kernel arguments, so every allocation of the
 	// frame goes through these two, and a buffer that moved (or was lost to a failed allocation) drops the graphs.
@@ -574,6 +611,17 @@ nnrt_status prepare_frame(nnrt_fitter* ft, nnrt_warp_field* wf, const float* d_v
 		ft->aw.edge_offsets = ft->a_offsets.ptr;
 		ft->aw.edge_list = ft->a_list.ptr;
 	}
+	if (key.coupled && E == 0) {   // the coupled solve's vectors (with a hierarchy the arrowhead path's, above)
+		if ((st = ensure(ft->a_diag, static_cast<size_t>(N) * 36)) || (st = ensure(ft->a_rhs, 6 * static_cast<size_t>(N))) ||
+		    (st = ensure(ft->a_x, 6 * static_cast<size_t>(N))) || (st = ensure(ft->a_res, 6 * static_cast<size_t>(N))) ||
+		    (st = ensure(ft->a_dx, 6 * static_cast<size_t>(N))) || (st = ensure(ft->edge_jr, 1)))
+			return st;
+	}
+	if (key.coupled) {
+		if ((st = ensure(ft->zero_inc, static_cast<size_t>(N) + 1)) || (st = ensure(ft->c_edge_off, 1)) || (st = ensure(ft->c_dinv, 36))) return st;
+		NNRT_HIP(hipMemset(ft->zero_inc.ptr, 0, sizeof(int) * (static_cast<size_t>(N) + 1)));
+		NNRT_HIP(hipMemset(ft->c_edge_off.ptr, 0, sizeof(int)));
+	}
 	key.corner_generation = ft->corner.generation;
 	// any other change of what the graphs bake in drops them too
 	if (std::memcmp(&key, &ft->key, sizeof(key)) != 0) ft->drop_graphs();
@@ -603,6 +651,48 @@ nnrt_status prepare_frame(nnrt_fitter* ft, nnrt_warp_field* wf, const float* d_v
 	// the faces' distinct anchor nodes (AssociateFacesWithAnchors, :105), consumed by the node pass of every iteration
 	if ((st = launch_face_node_table(ft->faces4.ptr, F, ft->anchors.ptr, K, ft->face_nodes.ptr, s))) return st;
 	if (ft->key.launch.anchors16 && (st = launch_pack_anchors16(ft->anchors.ptr, V, ft->anchors16.ptr, s))) return st;
+	if (ft->key.coupled) {
+		// the frame's node pairs from the face table (+ the hierarchy's edges), then the solver plan over them: the one
+		// host round trip of the coupled mode (the plan needs the coordinates); iterate() plans nothing
+		bool moved = false;
+		if ((st = build_pair_structure(ft->ps, ft->face_nodes.ptr, F, K, wf->edges.ptr, wf->h.edges.data(), E, N, s, &moved))) {
+			ft->drop_graphs();
+			return st;
+		}
+		const int M = ft->ps.M;
+		std::vector<float> cpos(3 * static_cast<size_t>(N));   // node positions (virtual order) for the nested-dissection bisection
+		for (int a = 0; a < N; a++) {
+			const int64_t o = wf->h.virtual_indices.empty() ? a : wf->h.virtual_indices[static_cast<size_t>(a)];
+			for (int c = 0; c < 3; c++) cpos[3 * static_cast<size_t>(a) + c] = wf->nodes_original[3 * static_cast<size_t>(o) + c];
+		}
+		if ((st = ft->pair_corner.prepare(ft->ps.h_pairs.data(), M, 0, N, cpos.data()))) {
+			ft->drop_graphs();
+			return st;
+		}
+		if ((st = ensure(ft->pair_acc, 36 * static_cast<size_t>(M))) || (st = ensure(ft->pair_blocks, 36 * static_cast<size_t>(M)))) return st;
+		if (moved || ft->pair_corner.generation != ft->key.pair_generation || M != ft->key.M) ft->drop_graphs();
+		ft->key.pair_generation = ft->pair_corner.generation;
+		ft->key.M = M;
+		ArrowheadWorkspace& cw = ft->cw;
+		cw = ArrowheadWorkspace();
+		cw.N = N;
+		cw.n0 = 0;
+		cw.E = M;
+		cw.m = 6 * N;
+		cw.corner = &ft->pair_corner;
+		cw.diag = ft->a_diag.ptr;
+		cw.dinv = ft->c_dinv.ptr;
+		cw.dinv_b = ft->c_dinv.ptr;
+		cw.rhs = ft->a_rhs.ptr;
+		cw.x = ft->a_x.ptr;
+		cw.refine = NNRT_ARAP_REFINE != 0;
+		cw.res = ft->a_res.ptr;
+		cw.dx = ft->a_dx.ptr;
+		cw.edge_offsets = ft->c_edge_off.ptr;
+		cw.edge_list = ft->c_edge_off.ptr;
+		cw.inc_off = ft->ps.inc_off.ptr;
+		cw.inc_list = ft->ps.inc_list.ptr;
+	}
 	// reference point cloud (:289-306): depth / scale with 0 < d < max_depth, AND the user mask; stored as depth (0 = masked)
 	if (ref.depth)
 		k_prepare_reference_depth<<<static_cast<unsigned>(ceil_div(P, 256)), 256, 0, s>>>(ref.depth, ref.mask, H, W, ref.depth_scale,
@@ -680,7 +770,7 @@ enum { RESET_NONE = 0, RESET_IDENTITY = 1, RESET_SNAPSHOT = 2, RESET_SNAPSHOT_FI
 // A restart folded into the iteration's kernels where they support it: from the identity (block-diagonal path, <= 4
 // anchors: the identity-specialised warp / update), or from the snapshot (every path: the warp, the ARAP edge terms and
 // the update read the snapshot as the starting state). Otherwise a separate kernel restarts.
-bool fold_reset(const nnrt_fitter* ft) { return ft->key.E == 0 && ft->key.K <= 4; }
+bool fold_reset(const nnrt_fitter* ft) { return ft->key.E == 0 && ft->key.K <= 4 && !ft->key.coupled; }
 bool fold_snapshot(const nnrt_fitter*) { return true; }
 
 nnrt_status check_frame(const nnrt_fitter* ft, const nnrt_warp_field* wf, const char* who) {
@@ -906,6 +996,52 @@ nnrt_status nnrt_fitter_set_robust_options(nnrt_fitter* ft, int32_t penalty_form
 	ft->guard_zero_rotation = guard_zero_rotation;
 	ft->aw.guard_zero_rotation = guard_zero_rotation;
 	ft->drop_graphs();   // both are launch arguments of the captured sequences; the prepared frame stays
+	return NNRT_OK;
+}
+
+nnrt_status nnrt_fitter_set_data_coupling(nnrt_fitter* ft, int32_t data_coupling) {
+	NNRT_CHECK_ARG(ft, "null pointer");
+	NNRT_CHECK_ARG(data_coupling == NNRT_DATA_BLOCK_DIAGONAL || data_coupling == NNRT_DATA_COUPLED,
+	               "data_coupling must be NNRT_DATA_BLOCK_DIAGONAL (0) or NNRT_DATA_COUPLED (1)");
+	if (data_coupling == NNRT_DATA_COUPLED)
+		for (int i = 0; i < ft->p.iteration_mode_count; i++)
+			NNRT_CHECK_ARG(ft->p.iteration_modes[i] == NNRT_ITERATION_ALL,
+			               "data_coupling: NNRT_DATA_COUPLED supports IterationMode ALL only (6x6 blocks), and the fitter's mode list holds another");
+	if (data_coupling == ft->data_coupling) return NNRT_OK;
+	DeviceGuard guard(ft->device);
+	NNRT_HIP(hipStreamSynchronize(ft->work));
+	ft->data_coupling = data_coupling;
+	ft->drop_graphs();      // the captured sequences hold the launches of the other mode
+	ft->prepared = false;   // the pair structure and the solver plan over it are built in prepare()
+	return NNRT_OK;
+}
+
+nnrt_status nnrt_fitter_get_data_coupling(const nnrt_fitter* ft, int32_t* data_coupling) {
+	NNRT_CHECK_ARG(ft && data_coupling, "null pointer");
+	*data_coupling = ft->data_coupling;
+	return NNRT_OK;
+}
+
+int64_t nnrt_fitter_coupled_pair_count(const nnrt_fitter* ft) {
+	if (!ft) return -1;
+	return ft->prepared && ft->key.coupled ? ft->ps.M : 0;
+}
+
+nnrt_status nnrt_fitter_get_coupled_system(nnrt_fitter* ft, float* h_diag, int32_t* h_pairs, float* h_blocks, float* h_rhs, int64_t node_count,
+                                           int64_t pair_count, void* stream) {
+	NNRT_CHECK_ARG(ft && h_diag && h_pairs && h_blocks && h_rhs, "null pointer");
+	NNRT_CHECK_ARG(ft->prepared && ft->key.coupled && ft->a_diag.ptr && ft->a_rhs.ptr, "no prepared frame in NNRT_DATA_COUPLED mode");
+	NNRT_CHECK_ARG(node_count == ft->key.N && pair_count == ft->ps.M, "node_count / pair_count differ from the prepared frame's");
+	DeviceGuard guard(ft->device);
+	NNRT_HIP(hipStreamSynchronize(static_cast<hipStream_t>(stream)));
+	NNRT_HIP(hipStreamSynchronize(ft->work));
+	const size_t M = static_cast<size_t>(ft->ps.M);
+	NNRT_HIP(hipMemcpy(h_diag, ft->a_diag.ptr, sizeof(float) * 36 * static_cast<size_t>(ft->key.N), hipMemcpyDeviceToHost));
+	NNRT_HIP(hipMemcpy(h_rhs, ft->a_rhs.ptr, sizeof(float) * 6 * static_cast<size_t>(ft->key.N), hipMemcpyDeviceToHost));
+	if (M > 0) {
+		std::memcpy(h_pairs, ft->ps.h_pairs.data(), sizeof(int32_t) * 2 * M);
+		NNRT_HIP(hipMemcpy(h_blocks, ft->pair_blocks.ptr, sizeof(float) * 36 * M, hipMemcpyDeviceToHost));
+	}
 	return NNRT_OK;
 }
 

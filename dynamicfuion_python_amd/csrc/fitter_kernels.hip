@@ -12,8 +12,8 @@
 //    into fp64 accumulator rows.
 // Products are rounded to float exactly as the reference forms them and summed in double, so the data term equals the
 // exactly-summed reference data term (see DESIGN.md "Numerics"); no node-list cap.
+#include "coupled.hpp"
 #include "fitter_kernels.hpp"
-
 
 
 namespace nnrt {
@@ -1204,6 +1204,280 @@ nnrt_status launch_fit_pixels(int mode, const FitPixelArgs& args, hipStream_t st
 		default: set_error("unknown iteration mode"); return NNRT_ERROR_ARGUMENT;
 	}
 	NNRT_LAUNCH_CHECK();
+	return NNRT_OK;
+}
+
+// =====================================================================================================================
+// Coupled data term (NNRT_DATA_COUPLED, mode ALL): the off-diagonal blocks J_a^T J_b of every pair
+// a < b of a contributing pixel's face nodes, a second launch after the fused one. Pass 1 reset the raster keys, so each
+// lane puts its pixel's face (the fused launch's pixel_face output) back into its key and runs pixel_body again: the
+// same re-resolve from the warped mesh, the same record (kept in registers), the key reset once more. The pixel-node
+// Jacobian rows restate pass 2's (2b) arithmetic, build switches included.
+//
+// One wave per 8 x 8 pixels (the fused launch's arithmetic tile mapping). Per lane: the face's table row and the J row of
+// every entry, parked in LDS (lane-private columns). The lane's pairs (a < b over its ascending row) are ascending in the
+// frame's pair list, so the wave takes the minimum of the lanes' next pair slots (as pass 2 takes its next node), the
+// lanes holding it file their two rows at consecutive LDS positions, and lane e < 36 sums entry (e / 6, e % 6) over them:
+// exact products double(J_a[r]) * double(J_b[c]) added in double, then ONE atomic per entry per (wave, pair). No
+// workgroup waits on another.
+// =====================================================================================================================
+// slot of pair (i, j), i < j, in the frame's pair list: binary search in row i of the CSR (-1: not a pair)
+__device__ __forceinline__ int pair_slot(const int* __restrict__ row_off, const int32_t* __restrict__ pairs, int i, int j) {
+	int lo = row_off[i], hi = row_off[i + 1];
+	while (lo < hi) {
+		const int mid = lo + ((hi - lo) >> 1);
+		const int v = pairs[2 * mid + 1];
+		if (v == j) return mid;
+		if (v < j) lo = mid + 1;
+		else hi = mid;
+	}
+	return -1;
+}
+
+// the pixel-node Jacobian row (mode ALL: rotation 3, translation 3) of face-table entry `code` for the pixel whose face
+// has vertices vid and whose record is rk: node_body's (2a) loads and (2b) expressions
+__device__ __forceinline__ void pair_node_jacobian(const FitPixelArgs& a, uint32_t code, const int (&vid)[3], const float (&rk)[16], float (&J)[6]) {
+	const int KA = a.anchor_count;
+	const int node = static_cast<int>(code >> FACE_NODE_SHIFT);
+	int rows[3];
+#pragma unroll
+	for (int fv = 0; fv < 3; fv++) {
+		const int k = static_cast<int>((code >> (4 * fv)) & 0xFu);
+		rows[fv] = k != 0xF ? vid[fv] * KA + k : -1;
+	}
+	float4 jv[3];
+	[[maybe_unused]] float4 jn[3];
+#if NNRT_GATHER_ROWS
+#pragma unroll
+	for (int fv = 0; fv < 3; fv++) {
+		const int r = rows[fv] >= 0 ? rows[fv] : 0;
+		const float w = a.weights[r];
+		const float2* row = a.jrows + 3 * static_cast<int64_t>(r);
+		const float2 j0 = row[0], j1 = row[1], j2 = row[2];
+		jv[fv] = make_float4(j0.x, j0.y, j1.x, w);
+		jn[fv] = make_float4(j1.y, j2.x, j2.y, 0.f);
+	}
+#else
+	float4 ns4[4], cp4[3], cn4[3];
+#pragma unroll
+	for (int fv = 0; fv < 3; fv++) {
+		const int r = rows[fv] >= 0 ? rows[fv] : 0;
+		jv[fv].w = a.weights[r];
+		cp4[fv] = a.cmesh_p[vid[fv]];
+		cn4[fv] = a.cmesh_n[vid[fv]];
+	}
+	{
+		const float4* ns = a.state_in + 4 * static_cast<int64_t>(node);
+		ns4[0] = ns[0];
+		if (!a.state_identity) {
+			ns4[1] = ns[1];
+			ns4[2] = ns[2];
+			ns4[3] = ns[3];
+		}
+	}
+	const f3 g = make3(ns4[0].x, ns4[0].y, ns4[0].z);
+	float R[9];
+	if (a.state_identity) {
+#pragma unroll
+		for (int i = 0; i < 9; i++) R[i] = (i % 4 == 0) ? 1.f : 0.f;
+	} else {
+		const float Rl[9] = {ns4[1].z, ns4[1].w, ns4[2].x, ns4[2].y, ns4[2].z, ns4[2].w, ns4[3].x, ns4[3].y, ns4[3].z};
+#pragma unroll
+		for (int i = 0; i < 9; i++) R[i] = Rl[i];
+	}
+#endif
+	const float dr_dV[9] = {rk[0], rk[1], rk[2], rk[3], rk[4], rk[5], rk[6], rk[7], rk[8]};
+	const float rn[3] = {rk[9], rk[10], rk[11]};
+	const float rho[3] = {rk[12], rk[13], rk[14]};
+	float jr[3] = {0.f, 0.f, 0.f}, jt[3] = {0.f, 0.f, 0.f};
+#if NNRT_JAC_FMA && !NNRT_GATHER_ROWS
+#pragma unroll
+	for (int fv = 0; fv < 3; fv++) {
+		const float ws = rows[fv] >= 0 ? jv[fv].w : 0.f;
+		const f3 dv = make3(dr_dV[3 * fv], dr_dV[3 * fv + 1], dr_dV[3 * fv + 2]);
+		jt[0] = fmaf(dv.x, ws, jt[0]);
+		jt[1] = fmaf(dv.y, ws, jt[1]);
+		jt[2] = fmaf(dv.z, ws, jt[2]);
+		const f3 d3 = sub3(make3(cp4[fv].x, cp4[fv].y, cp4[fv].z), g);
+		const f3 n3 = make3(cn4[fv].x, cn4[fv].y, cn4[fv].z);
+		const f3 p = make3(fmaf(R[0], d3.x, fmaf(R[1], d3.y, R[2] * d3.z)), fmaf(R[3], d3.x, fmaf(R[4], d3.y, R[5] * d3.z)),
+		                   fmaf(R[6], d3.x, fmaf(R[7], d3.y, R[8] * d3.z)));
+		const f3 q = make3(fmaf(R[0], n3.x, fmaf(R[1], n3.y, R[2] * n3.z)), fmaf(R[3], n3.x, fmaf(R[4], n3.y, R[5] * n3.z)),
+		                   fmaf(R[6], n3.x, fmaf(R[7], n3.y, R[8] * n3.z)));
+		const f3 dn = make3(rn[0] * rho[fv], rn[1] * rho[fv], rn[2] * rho[fv]);
+		const float cx = fmaf(dv.y, p.z, fmaf(-dv.z, p.y, fmaf(dn.y, q.z, -dn.z * q.y)));
+		const float cy = fmaf(dv.z, p.x, fmaf(-dv.x, p.z, fmaf(dn.z, q.x, -dn.x * q.z)));
+		const float cz = fmaf(dv.x, p.y, fmaf(-dv.y, p.x, fmaf(dn.x, q.y, -dn.y * q.x)));
+		jr[0] = fmaf(-ws, cx, jr[0]);
+		jr[1] = fmaf(-ws, cy, jr[1]);
+		jr[2] = fmaf(-ws, cz, jr[2]);
+	}
+#else
+#if !NNRT_GATHER_ROWS
+#pragma unroll
+	for (int fv = 0; fv < 3; fv++) {
+		const float w = jv[fv].w;
+		const f3 Rj = matvec3(R, sub3(make3(cp4[fv].x, cp4[fv].y, cp4[fv].z), g));
+		const f3 Rnj = matvec3(R, make3(cn4[fv].x, cn4[fv].y, cn4[fv].z));
+		jv[fv] = make_float4(-w * Rj.x, -w * Rj.y, -w * Rj.z, w);
+		jn[fv] = make_float4(-w * Rnj.x, -w * Rnj.y, -w * Rnj.z, 0.f);
+	}
+#endif
+#pragma unroll
+	for (int fv = 0; fv < 3; fv++) {
+		const bool on = rows[fv] >= 0;
+		const f3 dv = make3(dr_dV[3 * fv], dr_dV[3 * fv + 1], dr_dV[3 * fv + 2]);
+		jt[0] += on ? dv.x * jv[fv].w : 0.f;
+		jt[1] += on ? dv.y * jv[fv].w : 0.f;
+		jt[2] += on ? dv.z * jv[fv].w : 0.f;
+		const f3 dn = make3(rn[0] * rho[fv], rn[1] * rho[fv], rn[2] * rho[fv]);
+		const f3 t1 = row_times_skew(dv, make3(jv[fv].x, jv[fv].y, jv[fv].z));
+		const f3 t2 = row_times_skew(dn, make3(jn[fv].x, jn[fv].y, jn[fv].z));
+		jr[0] += on ? t1.x + t2.x : 0.f;
+		jr[1] += on ? t1.y + t2.y : 0.f;
+		jr[2] += on ? t1.z + t2.z : 0.f;
+	}
+#endif
+	J[0] = jr[0];
+	J[1] = jr[1];
+	J[2] = jr[2];
+	J[3] = jt[0];
+	J[4] = jt[1];
+	J[5] = jt[2];
+}
+
+constexpr int PAIR_ROW = 13;   // LDS stride of a filed (J_a, J_b) row (12 floats; odd: the lanes' stores spread over the banks)
+
+// LW: the waves of each workgroup one launch runs (their LDS regions are what limits it: 3 MAXK (6 + 1) 64 + 64 PAIR_ROW
+// words each); the waves [pa.wave_base, pa.wave_base + LW) work, the others leave at once
+template <int MAXK, int LW>
+__global__ __launch_bounds__(PIX_BLOCK) void k_fit_pairs(FitPixelArgs a, FitPairArgs pa) {
+	constexpr int NSLOT = 3 * MAXK;
+	constexpr int WORDS = NSLOT * 6 * 64 + NSLOT * 64 + 64 * PAIR_ROW;
+	static_assert(NSLOT * 6 >= 27, "pass 1's parked terms alias the Jacobian rows");
+	__shared__ float s_u[LW][WORDS];
+	const int wave = static_cast<int>(threadIdx.x >> 6), lane = static_cast<int>(threadIdx.x & 63);
+	if (wave < pa.wave_base || wave >= pa.wave_base + LW) return;   // wave-uniform
+	float* w = s_u[wave - pa.wave_base];
+	float* jst = w;                                                       // [(entry * 6 + c) * 64 + lane]
+	uint32_t* ent = reinterpret_cast<uint32_t*>(w + NSLOT * 6 * 64);      // [entry * 64 + lane]
+	float* filed = w + NSLOT * 6 * 64 + NSLOT * 64;                       // [rank * PAIR_ROW + 0..11]
+	// this lane's pixel (pixel_body's mapping): its key takes the fused launch's face back
+	{
+		const int tiles = a.tiles_x * a.tiles_y;
+		const int qd = pix_quadrant(a), tile = qd >> 2, quad = qd & 3;
+		const int tu = tile % a.tiles_x, tv = a.tile_row0 + tile / a.tiles_x;
+		const int u = tu * PIX_TILE + (quad & 1) * 8 + (lane & 7), v = tv * PIX_TILE + (quad >> 1) * 8 + (lane >> 3);
+		if (tile < tiles && u < a.W && v < a.H) {
+			const int64_t p = static_cast<int64_t>(v) * a.W + u;
+			const int32_t f = a.pixel_face[p];
+			a.keys[p] = f >= 0 ? static_cast<uint64_t>(static_cast<uint32_t>(f)) : EMPTY_KEY;
+		}
+	}
+	int face = -1, vid[3] = {0, 0, 0}, n = 0;
+	float rk[16];
+#pragma unroll
+	for (int i = 0; i < 16; i++) rk[i] = 0.f;
+	pixel_body<NNRT_ITERATION_ALL, true>(a, w + lane, 64, face, vid, rk, n);
+	__builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+	__builtin_amdgcn_wave_barrier();
+	__builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+	// the face's table row and every entry's J row into this lane's LDS columns
+	if (face < 0) n = 0;
+	n = n < NSLOT ? n : NSLOT;
+	for (int i = 0; i < n; i++) {
+		const uint32_t code = a.face_nodes[static_cast<int64_t>(face) * NSLOT + i];
+		if (code == FACE_NODE_NONE) {   // (the row's count says otherwise: never)
+			n = i;
+			break;
+		}
+		ent[i * 64 + lane] = code;
+		float J[6];
+		pair_node_jacobian(a, code, vid, rk, J);
+#pragma unroll
+		for (int c = 0; c < 6; c++) jst[(i * 6 + c) * 64 + lane] = J[c];
+	}
+	// the lane's next pair (ia < ib over its row) and its slot; INT_MAX: none left
+	constexpr int NONE = 0x7fffffff;
+	int ia = 0, ib = 1, head = NONE;
+	auto seek = [&]() {   // the slot of (ia, ib), stepping over anything that is not a pair of the frame (never, by construction)
+		head = NONE;
+		while (ia + 1 < n) {
+			const int s = pair_slot(pa.row_off, pa.pairs, static_cast<int>(ent[ia * 64 + lane] >> FACE_NODE_SHIFT),
+			                        static_cast<int>(ent[ib * 64 + lane] >> FACE_NODE_SHIFT));
+			if (s >= 0) {
+				head = s;
+				return;
+			}
+			if (++ib >= n) {
+				ia++;
+				ib = ia + 1;
+			}
+		}
+	};
+	seek();
+	const uint64_t lanes_below = (1ull << lane) - 1ull;
+	const int er = lane < 36 ? lane / 6 : 0, ec = lane < 36 ? lane % 6 : 0;
+	auto wave_sync = [&]() {
+		__builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+		__builtin_amdgcn_wave_barrier();
+		__builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+	};
+	while (true) {
+		const int X = wave_min_i32(head);
+		if (X == NONE) break;
+		const uint64_t Mk = __ballot(head == X);
+		if (Mk == 0) break;   // unreachable (X is some lane's head); guarantees progress
+		const int cnt = __popcll(Mk);
+		if (head == X) {
+			float* row = filed + __popcll(Mk & lanes_below) * PAIR_ROW;
+#pragma unroll
+			for (int c = 0; c < 6; c++) {
+				row[c] = jst[(ia * 6 + c) * 64 + lane];
+				row[6 + c] = jst[(ib * 6 + c) * 64 + lane];
+			}
+			if (++ib >= n) {
+				ia++;
+				ib = ia + 1;
+			}
+			seek();
+		}
+		wave_sync();
+		if (lane < 36) {
+			double s0 = 0.0, s1 = 0.0;
+			int q = 0;
+			for (; q + 1 < cnt; q += 2) {
+				s0 += static_cast<double>(filed[q * PAIR_ROW + er]) * static_cast<double>(filed[q * PAIR_ROW + 6 + ec]);
+				s1 += static_cast<double>(filed[(q + 1) * PAIR_ROW + er]) * static_cast<double>(filed[(q + 1) * PAIR_ROW + 6 + ec]);
+			}
+			if (q < cnt) s0 += static_cast<double>(filed[q * PAIR_ROW + er]) * static_cast<double>(filed[q * PAIR_ROW + 6 + ec]);
+			atomicAdd(pa.pair_acc + static_cast<int64_t>(X) * 36 + lane, s0 + s1);
+		}
+		wave_sync();
+	}
+}
+
+nnrt_status launch_fit_pairs(const FitPixelArgs& args, FitPairArgs pa, int M, hipStream_t stream) {
+	if (M == 0) return NNRT_OK;
+	FitPixelArgs a = args;
+	a.quad_order = nullptr;   // the arithmetic mapping: every quadrant once, whatever order table the fused launch used
+	a.tile_order = nullptr;
+	a.order_blocks = 0;
+	a.arap_blocks = 0;
+	const unsigned grid = static_cast<unsigned>(((4 * a.tiles_x * a.tiles_y + PIX_WAVES - 1) / PIX_WAVES + 7) / 8 * 8);
+	if (a.anchor_count <= 4) {
+		pa.wave_base = 0;
+		k_fit_pairs<4, PIX_WAVES><<<grid, PIX_BLOCK, 0, stream>>>(a, pa);
+		NNRT_LAUNCH_CHECK();
+	} else {
+		// rows of up to 24 nodes: the LDS holds two waves' regions, so each half of the workgroups' waves gets a launch
+		constexpr int LW = PIX_WAVES >= 2 ? 2 : 1;
+		for (int base = 0; base < PIX_WAVES; base += LW) {
+			pa.wave_base = base;
+			k_fit_pairs<MAX_ANCHORS, LW><<<grid, PIX_BLOCK, 0, stream>>>(a, pa);
+			NNRT_LAUNCH_CHECK();
+		}
+	}
 	return NNRT_OK;
 }
 

@@ -42,12 +42,14 @@ cutoff c contributes iff |r| <= c, and its residual and Jacobian row are scaled 
 (1 - (r / c)^2)^2 on the squared residual), so depth discontinuities, occlusion edges and sensor outliers carry no
 weight; an ARAP edge's residual 3-vector r and its Jacobian terms are scaled by s = 1 if |r| <= delta else
 sqrt(delta / |r|) (Huber's weight min(1, delta / |r|)). Hand-held sequences (DeepDeform's are) also want
-`rigid_alignment=True`. `guard_zero_rotation=True` keeps the rotation of a node whose
+`rigid_alignment=True`, and every real sequence wants `coupled_data_term=True`: the reference's block-diagonal data
+Hessian overshoots from the second iteration on, the coupled step converges. `guard_zero_rotation=True` keeps the rotation of a node whose
 rotation update is exactly zero (every node without pixels), where the reference's Rodrigues formula gives NaN (A7).
 The defaults (`_default_alignment`) keep their values.
 """
 from __future__ import annotations
 
+import dataclasses
 import enum
 import time
 from dataclasses import dataclass, field
@@ -63,7 +65,7 @@ from ..data.frame import FrameSequenceDataset
 from ..nnrt import geometry as G
 from ..nnrt import image_proc
 from ..nnrt import rendering
-from ..nnrt.alignment import NDC_CONSISTENT, align_rigid_point_to_plane
+from ..nnrt.alignment import NDC_CONSISTENT, DataCoupling, align_rigid_point_to_plane
 from ..warp_field.graph_warp_field import build_graph_nodes_from_depth_image, extend_warp_field, sample_graph_nodes_from_mesh
 
 
@@ -162,6 +164,15 @@ class FusionParameters:
     model_agreement: bool = False
     model_agreement_inlier_threshold: float = 0.01   # metres
     alignment: RenderingAlignmentParameters = field(default_factory=_default_alignment)
+    # the full Gauss-Newton step (DataCoupling.COUPLED) in place of the reference's block-diagonal data
+    # Hessian; real sequences should turn it on. Overrides alignment.data_coupling when set.
+    coupled_data_term: bool = False
+
+
+def alignment_parameters(p: FusionParameters) -> RenderingAlignmentParameters:
+    """The optimizer's parameters for these fusion parameters: p.alignment, in DataCoupling.COUPLED mode when
+    coupled_data_term is set."""
+    return dataclasses.replace(p.alignment, data_coupling=DataCoupling.COUPLED) if p.coupled_data_term else p.alignment
 
 
 @dataclass
@@ -258,7 +269,8 @@ class FusionPipeline:
         self.node_order = None
         # SHORTEST_PATH: the graph's edge rows in the warp field's virtual node order, as handed to the optimizer
         self.anchor_graph_edges = None
-        self.optimizer = RenderingAlignmentOptimizer((self.intrinsics.height, self.intrinsics.width), self.device, self.K, p.alignment)
+        self.optimizer = RenderingAlignmentOptimizer((self.intrinsics.height, self.intrinsics.width), self.device, self.K,
+                                                     alignment_parameters(p))
         self.canonical_mesh = None
         self.warped_mesh = None
         # the point image the last tracked frame was aligned and fitted to, and whose normals gated its integration

@@ -33,6 +33,14 @@ class PenaltyForm(enum.IntEnum):
     IRLS = 1
 
 
+class DataCoupling(enum.IntEnum):
+    """How the data term couples the nodes (include/nnrt_mi355x.h NNRT_DATA_*): the reference's block-diagonal Hessian
+    (SURVEY A17), or the full Gauss-Newton system with an off-diagonal block for every pair of nodes that share a face
+    (DESIGN section 23). Real sequences should use COUPLED: the block-diagonal step diverges after its first iteration."""
+    BLOCK_DIAGONAL = 0
+    COUPLED = 1
+
+
 NDC_REFERENCE = 0     # the reference's image -> NDC mapping (SURVEY A11)
 NDC_CONSISTENT = 1    # raster pixel (u, v) == pixel (u, v) of the intrinsics
 
@@ -187,6 +195,35 @@ class DeformableMeshToImageFitter:
         form, guard = ctypes.c_int32(), ctypes.c_int32()
         N.check(N.lib().nnrt_fitter_get_robust_options(self._h, ctypes.byref(form), ctypes.byref(guard)))
         return PenaltyForm(form.value), bool(guard.value)
+
+    def set_data_coupling(self, data_coupling):
+        """DataCoupling.BLOCK_DIAGONAL (default: the reference's arithmetic) or DataCoupling.COUPLED (the data term's
+        off-diagonal blocks and one sparse solve of the whole system; IterationMode.ALL only). A change drops the cached
+        graphs and invalidates the prepared frame: call prepare() again. Other values, or COUPLED on a fitter whose mode
+        list holds another mode, raise."""
+        N.check(N.lib().nnrt_fitter_set_data_coupling(self._h, int(data_coupling)))
+
+    @property
+    def data_coupling(self) -> DataCoupling:
+        v = ctypes.c_int32()
+        N.check(N.lib().nnrt_fitter_get_data_coupling(self._h, ctypes.byref(v)))
+        return DataCoupling(v.value)
+
+    @property
+    def coupled_pair_count(self) -> int:
+        """Node pairs of the prepared frame's coupled system (0 in block-diagonal mode)."""
+        return int(N.lib().nnrt_fitter_coupled_pair_count(self._h))
+
+    def coupled_system(self, stream=None):
+        """The last coupled iteration's float system as the fitter solved it (virtual order): diagonal blocks [N,6,6]
+        with LM, pairs [M,2] (i < j, ascending), block (i, j) of each pair [M,6,6], right-hand side [6N]."""
+        n, m = self._node_count, self.coupled_pair_count
+        d = np.empty((n, 6, 6), np.float32)
+        pairs = np.empty((m, 2), np.int32)
+        blocks = np.empty((m, 6, 6), np.float32)
+        b = np.empty(6 * n, np.float32)
+        N.check(N.lib().nnrt_fitter_get_coupled_system(self._h, N.ptr(d), N.ptr(pairs), N.ptr(blocks), N.ptr(b), n, m, N.stream_ptr(stream)))
+        return d, pairs, blocks, b
 
     @property
     def graph_count(self) -> int:

@@ -213,6 +213,29 @@ nnrt_status nnrt_fitter_set_refine_ratio(nnrt_fitter* fitter, float ratio);
 #define NNRT_PENALTY_IRLS 1
 nnrt_status nnrt_fitter_set_robust_options(nnrt_fitter* fitter, int32_t penalty_form, int32_t guard_zero_rotation);
 nnrt_status nnrt_fitter_get_robust_options(const nnrt_fitter* fitter, int32_t* penalty_form, int32_t* guard_zero_rotation);
+/* Coupling of the data term across nodes. NNRT_DATA_BLOCK_DIAGONAL (default): the reference's
+ * data Hessian, one 6x6 block per node, bit for bit. NNRT_DATA_COUPLED: the full Gauss-Newton step -- every
+ * pair (a, b), a < b, of nodes that anchor vertices of one face gets the off-diagonal block sum over the face's
+ * contributing pixels of J_a^T J_b (with the IRLS scale where it is on), united with the ARAP wing blocks, and the whole
+ * system is factored by the tile-sparse solver (arrow base 0). Real sequences should use it: the block-diagonal step
+ * overshoots from its second iteration on. IterationMode ALL only: a fitter whose mode list holds
+ * another mode refuses NNRT_DATA_COUPLED with NNRT_ERROR_ARGUMENT; any other value is NNRT_ERROR_ARGUMENT too,
+ * nnrt_last_error() naming the argument. A change drops the fitter's cached graphs AND invalidates the prepared frame
+ * (the pair structure and the solver plan over it are built in prepare(), with one host round trip): prepare() must be
+ * called again before the next iterate(). A singular system (lambda = 0 and a node without pixels or edges) is reported by
+ * nnrt_fitter_check as NNRT_ERROR_NOT_POSITIVE_DEFINITE. */
+#define NNRT_DATA_BLOCK_DIAGONAL 0
+#define NNRT_DATA_COUPLED 1
+nnrt_status nnrt_fitter_set_data_coupling(nnrt_fitter* fitter, int32_t data_coupling);
+nnrt_status nnrt_fitter_get_data_coupling(const nnrt_fitter* fitter, int32_t* data_coupling);
+/* Node pairs of the prepared frame's coupled system (0 in block-diagonal mode or without a prepared frame; -1: null). */
+int64_t nnrt_fitter_coupled_pair_count(const nnrt_fitter* fitter);
+/* The last coupled iteration's float system exactly as the fitter factored it (diagnostic; synchronizes `stream`; virtual
+ * node order), the counterpart of nnrt_fitter_get_arrowhead_system: h_diag [N,36] diagonal blocks (data + ARAP + LM),
+ * h_pairs [M,2] the pairs (i, j), i < j, ascending, h_blocks [M,36] block (i, j) of each pair (its transpose at (j, i)),
+ * h_rhs [6N] right-hand side (negative gradient). node_count / pair_count must equal the prepared frame's. */
+nnrt_status nnrt_fitter_get_coupled_system(nnrt_fitter* fitter, float* h_diag, int32_t* h_pairs, float* h_blocks, float* h_rhs,
+                                           int64_t node_count, int64_t pair_count, void* stream);
 /* Anchor the canonical mesh along a motion graph's edges instead of by Euclidean distance (the reference's
  * AnchorComputationMethod::SHORTEST_PATH, PlanarGraphWarpField::PrecomputeAnchorsAndWeights; apps/fusion/pipeline.py:577-582):
  * d_edges [node_count, graph_degree] int32 rows in the warp field's virtual node order (entry < 0 = empty) are copied
