@@ -30,6 +30,18 @@ class FitterParams(ctypes.Structure):
                 ("ndc_convention", c_int32)]
 
 
+class StepControlSettings(ctypes.Structure):   # nnrt_step_control
+    _fields_ = [("initial_lambda", c_float), ("increase", c_float), ("decrease", c_float), ("lambda_min", c_float),
+                ("lambda_max", c_float), ("relative_cost_tolerance", c_float), ("poll_interval", c_int32)]
+
+
+class StepRecord(ctypes.Structure):   # nnrt_step_record
+    _fields_ = [("cost", ctypes.c_double), ("lambda_", c_float), ("max_update", c_float), ("decision", c_int32), ("iteration", c_int32)]
+
+
+STEP_HISTORY_CAPACITY = 256   # NNRT_STEP_HISTORY_CAPACITY
+
+
 def build(force: bool = False) -> str:
     """Compile the HIP sources for gfx950 in-tree (hipcc; no GPU needed)."""
     if force:
@@ -95,6 +107,9 @@ _SIGNATURES = {
     "nnrt_fitter_set_data_coupling": (c_int32, [c_void_p, c_int32]),
     "nnrt_fitter_get_data_coupling": (c_int32, [c_void_p, ctypes.POINTER(c_int32)]),
     "nnrt_fitter_coupled_pair_count": (c_int64, [c_void_p]),
+    "nnrt_fitter_set_step_control": (c_int32, [c_void_p, ctypes.POINTER(StepControlSettings)]),
+    "nnrt_fitter_get_step_control": (c_int32, [c_void_p, ctypes.POINTER(c_int32), ctypes.POINTER(StepControlSettings)]),
+    "nnrt_fitter_get_step_history": (c_int32, [c_void_p, ctypes.POINTER(StepRecord), c_int64, ctypes.POINTER(c_int64), c_void_p]),
     "nnrt_fitter_get_coupled_system": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_void_p]),
     "nnrt_fitter_set_anchor_graph": (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_void_p]),
     "nnrt_fitter_check": (c_int32, [c_void_p, c_void_p]),

@@ -10,7 +10,7 @@ from __future__ import annotations
 
 import enum
 from dataclasses import dataclass
-from typing import Tuple
+from typing import Optional, Tuple
 
 import numpy as np
 import torch
@@ -50,6 +50,10 @@ class RenderingAlignmentParameters:
     # The data term's coupling across nodes (DeformableMeshToImageFitter.set_data_coupling): the reference's
     # block-diagonal Hessian by default; real sequences want DataCoupling.COUPLED (IterationMode.ALL only).
     data_coupling: A.DataCoupling = A.DataCoupling.BLOCK_DIAGONAL
+    # On-device step control (DeformableMeshToImageFitter.set_step_control): None (default) runs every
+    # iteration with the fixed damping, as the reference does; an A.StepControl keeps a step only if the cost fell.
+    # SQUARE penalties (or PenaltyForm.REFERENCE) and IterationMode.ALL only.
+    step_control: Optional[A.StepControl] = None
 
 
 def as_triangle_mesh(mesh) -> G.TriangleMesh:
@@ -83,6 +87,9 @@ class RenderingAlignmentOptimizer:
             huber_penalty_constant=p.regularization_term_penalty_constant, device=dev, ndc_convention=p.ndc_convention,
             penalty_form=p.penalty_form, guard_zero_rotation=p.guard_zero_rotation)
         self.fitter.set_data_coupling(A.DataCoupling(p.data_coupling))
+        self.last_step_summary = None   # DeformableMeshToImageFitter.step_summary() of the last optimize_graph (step control on)
+        if p.step_control is not None:
+            self.fitter.set_step_control(p.step_control)
 
     def set_anchor_graph(self, edges):
         """Anchor the canonical mesh along these edge rows ([N, D] int32, the graph's virtual node order, -1 = empty) in
@@ -101,4 +108,6 @@ class RenderingAlignmentOptimizer:
         valid = torch.isfinite(pts).all(dim=1) & (pts[:, 2] > 0)
         pts = torch.where(valid[:, None], pts, torch.zeros_like(pts))
         self.fitter.fit_to_image(graph, mesh, target_rgb, pts, valid.to(torch.uint8), self.intrinsic_matrix, extrinsics, (H, W))
+        # what step control made of the fit (None while it is off)
+        self.last_step_summary = self.fitter.step_summary() if self.parameters.step_control is not None else None
         return graph

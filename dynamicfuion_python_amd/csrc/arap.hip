@@ -73,7 +73,9 @@ __device__ __forceinline__ bool prepare_node(int n, int q, float lm, double* __r
 }
 
 // ---- data acc + ARAP edge terms -> full diagonal blocks (+LM) and rhs = negative gradient (every node) ----
-__global__ __launch_bounds__(256) void k_arrow_prepare(int N, float lm, double* __restrict__ acc, const int* __restrict__ inc_off,
+// Lm: float (a launch argument) or const float* (a device word: lm_value, fitter_kernels.hpp)
+template <class Lm>
+__global__ __launch_bounds__(256) void k_arrow_prepare(int N, Lm lm, double* __restrict__ acc, const int* __restrict__ inc_off,
                                                        const float* __restrict__ edge_terms, float* __restrict__ diag, float* __restrict__ rhs,
                                                        float* __restrict__ gradient_out, float* __restrict__ hessian_out) {
 	const int n = static_cast<int>((static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x) >> 5);
@@ -81,7 +83,7 @@ __global__ __launch_bounds__(256) void k_arrow_prepare(int N, float lm, double* 
 	if (n >= N) return;   // uniform per 32-lane node group
 	int r0, c0;
 	float dv;
-	prepare_node(n, q, lm, acc, inc_off, edge_terms, diag, rhs, gradient_out, hessian_out, r0, c0, dv);
+	prepare_node(n, q, lm_value(lm), acc, inc_off, edge_terms, diag, rhs, gradient_out, hessian_out, r0, c0, dv);
 }
 
 // ---- stem: D^-1 and D^-1 B per stem node, four lanes per node (each forms D^-1 with the same arithmetic and the products
@@ -558,20 +560,25 @@ nnrt_status arrowhead_solve_core(const ArrowheadWorkspace& ws, const int32_t* ed
 
 nnrt_status launch_arrowhead_iteration(const ArrowheadWorkspace& ws, const double* acc, float lm, const int32_t* edges, const float* wing,
                                        float* node_state, const float* edge_jr, float* updates_out, float* gradient_out, float* hessian_out,
-                                       int* error_flag, hipStream_t stream, const float* state_in) {
+                                       int* error_flag, hipStream_t stream, const float* state_in, const float* lm_device) {
 	// (one launch of prepare + stem + corner init, every node's block kept in its workgroup, measured 22.4 µs at C5 against
 	// 11.6 + 9.1 µs as two launches: the stem phase then ran on 4 of every 32 lanes; round 4, not kept)
-	k_arrow_prepare<<<static_cast<unsigned>(ceil_div(static_cast<int64_t>(ws.N) * 32, 256)), 256, 0, stream>>>(
-	    ws.N, lm, const_cast<double*>(acc), ws.inc_off, edge_jr, ws.diag, ws.rhs, gradient_out, hessian_out);
+	if (lm_device)
+		k_arrow_prepare<const float*><<<static_cast<unsigned>(ceil_div(static_cast<int64_t>(ws.N) * 32, 256)), 256, 0, stream>>>(
+		    ws.N, lm_device, const_cast<double*>(acc), ws.inc_off, edge_jr, ws.diag, ws.rhs, gradient_out, hessian_out);
+	else
+		k_arrow_prepare<float><<<static_cast<unsigned>(ceil_div(static_cast<int64_t>(ws.N) * 32, 256)), 256, 0, stream>>>(
+		    ws.N, lm, const_cast<double*>(acc), ws.inc_off, edge_jr, ws.diag, ws.rhs, gradient_out, hessian_out);
 	NNRT_LAUNCH_CHECK();
 	return arrowhead_solve_core(ws, edges, wing, error_flag, stream, true, node_state, updates_out, state_in);
 }
 
 // the prepare launch alone (coupled.hpp): the coupled data term assembles its pair blocks before the solve
 nnrt_status launch_arrow_prepare(int N, float lm, double* acc, const int* inc_off, const float* edge_terms, float* diag, float* rhs,
-                                 float* gradient_out, float* hessian_out, hipStream_t stream) {
-	k_arrow_prepare<<<static_cast<unsigned>(ceil_div(static_cast<int64_t>(N) * 32, 256)), 256, 0, stream>>>(N, lm, acc, inc_off, edge_terms, diag, rhs,
-	                                                                                                     gradient_out, hessian_out);
+                                 float* gradient_out, float* hessian_out, hipStream_t stream, const float* lm_device) {
+	const unsigned grid = static_cast<unsigned>(ceil_div(static_cast<int64_t>(N) * 32, 256));
+	if (lm_device) k_arrow_prepare<const float*><<<grid, 256, 0, stream>>>(N, lm_device, acc, inc_off, edge_terms, diag, rhs, gradient_out, hessian_out);
+	else k_arrow_prepare<float><<<grid, 256, 0, stream>>>(N, lm, acc, inc_off, edge_terms, diag, rhs, gradient_out, hessian_out);
 	NNRT_LAUNCH_CHECK();
 	return NNRT_OK;
 }

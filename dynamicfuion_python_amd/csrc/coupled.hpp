@@ -40,8 +40,9 @@ nnrt_status launch_fit_pairs(const FitPixelArgs& args, FitPairArgs pa, int M, hi
 nnrt_status launch_coupled_assemble(const double* pair_acc, int M, const int* edge_off, const int* edge_list, const float* wing,
                                     float* pair_blocks, hipStream_t stream);
 
-// arap.hip: data accumulator + ARAP edge terms -> diagonal blocks (+ LM) and right-hand side (k_arrow_prepare alone)
+// arap.hip: data accumulator + ARAP edge terms -> diagonal blocks (+ LM) and right-hand side (k_arrow_prepare alone);
+// lm_device (nullable): the damping is read from this device word instead of `lm` (step control)
 nnrt_status launch_arrow_prepare(int N, float lm, double* acc, const int* inc_off, const float* edge_terms, float* diag, float* rhs,
-                                 float* gradient_out, float* hessian_out, hipStream_t stream);
+                                 float* gradient_out, float* hessian_out, hipStream_t stream, const float* lm_device = nullptr);
 
 } // namespace nnrt

@@ -13,6 +13,7 @@
 
 #include "coupled.hpp"
 #include "handles.hpp"
+#include "step_control.hpp"
 
 using namespace nnrt;
 
@@ -95,6 +96,14 @@ struct nnrt_fitter {
 	DeviceBuffer<int> c_edge_off;       // [1] the empty stem's edge CSR
 	DeviceBuffer<float> c_dinv;         // [1] (no stem blocks)
 	ArrowheadWorkspace cw;
+	// nnrt_fitter_set_step_control: the settings, and the state machine's device state (allocated by
+	// prepare() while the mode is on)
+	bool step_on = false;
+	nnrt_step_control step{};
+	DeviceBuffer<StepState> step_state;
+	DeviceBuffer<nnrt_step_record> step_history;   // [NNRT_STEP_HISTORY_CAPACITY]
+	DeviceBuffer<float> step_best;                 // [N, STEP_BEST_STRIDE] best motion (t, R)
+	DeviceBuffer<double> step_partials;            // [step_cost_blocks] k_step_cost's partial sums
 	int last_mode = 0;
 	DeviceBuffer<float> snapshot;   // [N,16] node state stored by nnrt_fitter_snapshot_motion (restore-before-iteration runs)
 	// nnrt_fitter_set_anchor_graph: edge rows [graph_nodes, graph_degree] in the warp field's virtual node order (checked
@@ -163,6 +172,13 @@ private:
 	hipStream_t us_;
 	bool entered_ = false;
 };
+
+// the damping step control starts a fit with: initial_lambda, or preconditioning_dampening_factor when that is 0, clamped
+// into [lambda_min, lambda_max]
+float step_initial_lambda(const nnrt_fitter* ft) {
+	const float l = ft->step.initial_lambda > 0.f ? ft->step.initial_lambda : ft->p.preconditioning_dampening_factor;
+	return fminf(fmaxf(l, ft->step.lambda_min), ft->step.lambda_max);
+}
 
 // timing events, destroyed on every return
 struct Events {
@@ -349,13 +365,39 @@ nnrt_status enqueue_iteration(nnrt_fitter* ft, const nnrt_warp_field* wf, int mo
 	}
 	if ((st = mark(4))) return st;
 	if (!(stages & STAGE_SOLVE)) return mark(6);
+	if ((st = mark(5))) return st;
+	// step control: the cost of the state this iteration started from and the decision, before the solve; the solve
+	// launches then read the damping the decision left on the device
+	const bool step = ft->step_on;
+	const float* lm_device = step ? &ft->step_state.ptr->lambda : nullptr;
+	if (step) {
+		StepCostArgs ca{};
+		ca.P = static_cast<int64_t>(ft->key.H) * ft->key.W;
+		ca.E3 = 3 * static_cast<int64_t>(ft->key.E);
+		ca.N = ft->key.N;
+		ca.blocks = step_cost_blocks(ca.P + ca.E3);
+		ca.chunk = step_cost_chunk(ca.P + ca.E3, ca.blocks);
+		ca.residuals = ft->residuals.ptr;
+		ca.residual_mask = ft->residual_mask.ptr;
+		ca.edge_residuals = ft->edge_residuals.ptr;
+		ca.state_in = state_in;
+		ca.best = ft->step_best.ptr;
+		ca.partials = ft->step_partials.ptr;
+		ca.st = ft->step_state.ptr;
+		ca.error_flag = ft->error_flag.ptr;
+		ca.increase = ft->step.increase;
+		ca.decrease = ft->step.decrease;
+		ca.lambda_min = ft->step.lambda_min;
+		ca.lambda_max = ft->step.lambda_max;
+		ca.relative_cost_tolerance = ft->step.relative_cost_tolerance;
+		if ((st = launch_step_cost(ca, s))) return st;
+	}
 	if (coupled) {
 		// diagonal blocks (data + ARAP + LM) and right-hand side as on the arrowhead path, the pair blocks, then the
 		// tile-sparse solve with arrow base 0 and the node updates
-		if ((st = mark(5))) return st;
 		if ((st = launch_arrow_prepare(ft->key.N, ft->p.preconditioning_dampening_factor, ft->acc.ptr,
 		                               ft->key.E > 0 ? ft->a_inc_off.ptr : ft->zero_inc.ptr, ft->edge_jr.ptr, ft->a_diag.ptr, ft->a_rhs.ptr,
-		                               ft->gradient.ptr, ft->hessian.ptr, s)) ||
+		                               ft->gradient.ptr, ft->hessian.ptr, s, lm_device)) ||
 		    (st = launch_coupled_assemble(ft->pair_acc.ptr, ft->ps.M, ft->ps.edge_off.ptr, ft->ps.edge_list.ptr, ft->wing.ptr, ft->pair_blocks.ptr, s)))
 			return st;
 		ArrowheadWorkspace cw = ft->cw;
@@ -364,13 +406,24 @@ nnrt_status enqueue_iteration(nnrt_fitter* ft, const nnrt_warp_field* wf, int mo
 		if ((st = arrowhead_solve_core(cw, ft->ps.pairs.ptr, ft->pair_blocks.ptr, ft->error_flag.ptr, s, false, wf->state.ptr, ft->updates.ptr, state_in)))
 			return st;
 	} else if (ft->key.E > 0) {
-		if ((st = mark(5))) return st;
 		const float lm = ft->p.preconditioning_dampening_factor;
 		if ((st = launch_arrowhead_iteration(ft->aw, ft->acc.ptr, lm, wf->edges.ptr, ft->wing.ptr, wf->state.ptr, ft->edge_jr.ptr,
-		                                     ft->updates.ptr, ft->gradient.ptr, ft->hessian.ptr, ft->error_flag.ptr, s, state_in)))
+		                                     ft->updates.ptr, ft->gradient.ptr, ft->hessian.ptr, ft->error_flag.ptr, s, state_in, lm_device)))
 			return st;
+	} else if (step) {
+		SolveArgsDeviceLm sa{};
+		sa.N = ft->key.N;
+		sa.lm = lm_device;
+		sa.acc = ft->acc.ptr;
+		sa.state_in = state_in;
+		sa.node_state = wf->state.ptr;
+		sa.updates_out = ft->updates.ptr;
+		sa.gradient_out = ft->gradient.ptr;
+		sa.hessian_out = ft->hessian.ptr;
+		sa.error_flag = ft->error_flag.ptr;
+		sa.guard_zero_rotation = ft->guard_zero_rotation;
+		if ((st = launch_solve_update_device_lm(sa, s))) return st;
 	} else {
-		if ((st = mark(5))) return st;
 		SolveArgs sa{};
 		sa.N = ft->key.N;
 		sa.lm = ft->p.preconditioning_dampening_factor;
@@ -383,6 +436,18 @@ nnrt_status enqueue_iteration(nnrt_fitter* ft, const nnrt_warp_field* wf, int mo
 		sa.error_flag = ft->error_flag.ptr;
 		sa.guard_zero_rotation = ft->guard_zero_rotation;
 		if ((st = launch_solve_update(mode, sa, s, from_identity))) return st;
+	}
+	if (step) {   // keep the step, or put the best motion back; the history record
+		StepSelectArgs sa{};
+		sa.N = ft->key.N;
+		sa.updates = ft->updates.ptr;
+		sa.node_state = wf->state.ptr;
+		sa.best = ft->step_best.ptr;
+		sa.st = ft->step_state.ptr;
+		sa.history = ft->step_history.ptr;
+		sa.error_flag = ft->error_flag.ptr;
+		sa.minimal_update_threshold = ft->p.minimal_update_threshold;
+		if ((st = launch_step_select(sa, s))) return st;
 	}
 	return mark(6);
 }
@@ -622,6 +687,12 @@ nnrt_status prepare_frame(nnrt_fitter* ft, nnrt_warp_field* wf, const float* d_v
 		NNRT_HIP(hipMemset(ft->zero_inc.ptr, 0, sizeof(int) * (static_cast<size_t>(N) + 1)));
 		NNRT_HIP(hipMemset(ft->c_edge_off.ptr, 0, sizeof(int)));
 	}
+	if (ft->step_on) {   // step control's device state (a moved buffer drops the graphs, as above)
+		if ((st = ensure(ft->step_state, 1)) || (st = ensure(ft->step_history, NNRT_STEP_HISTORY_CAPACITY)) ||
+		    (st = ensure(ft->step_best, static_cast<size_t>(N) * STEP_BEST_STRIDE)) ||
+		    (st = ensure(ft->step_partials, static_cast<size_t>(step_cost_blocks(P + 3 * static_cast<int64_t>(E))))))
+			return st;
+	}
 	key.corner_generation = ft->corner.generation;
 	// any other change of what the graphs bake in drops them too
 	if (std::memcmp(&key, &ft->key, sizeof(key)) != 0) ft->drop_graphs();
@@ -711,6 +782,11 @@ nnrt_status prepare_frame(nnrt_fitter* ft, nnrt_warp_field* wf, const float* d_v
 		return st;
 	NNRT_HIP(hipMemsetAsync(ft->keys.ptr, 0xff, sizeof(uint64_t) * P, s));
 	NNRT_HIP(hipMemsetAsync(ft->acc.ptr, 0, sizeof(double) * N * ACC_STRIDE, s));
+	if (ft->step_on) {
+		if ((st = launch_step_reset(ft->step_state.ptr, step_initial_lambda(ft), s))) return st;
+		// an edge the ARAP launch refuses (A3, error bit 2) writes no residual: the cost then sums zeros there, not stale values
+		if (E > 0) NNRT_HIP(hipMemsetAsync(ft->edge_residuals.ptr, 0, sizeof(float) * 3 * static_cast<size_t>(E), s));
+	}
 	if ((st = scope.leave())) return st;
 	ft->prepared = true;
 	return NNRT_OK;
@@ -825,6 +901,14 @@ int restart_of(int reset, bool first_of_call) {
 nnrt_status iterate_impl(nnrt_fitter* ft, nnrt_warp_field* wf, int32_t first_iteration, int32_t count, int reset, hipStream_t us) {
 	ft->refine_ratio_used = ft->refine_ratio;
 	nnrt_status st;
+	if (ft->step_on) {
+		if (reset == RESET_IDENTITY || reset == RESET_SNAPSHOT) {
+			set_error("invalid argument: step control is on: iterations that restart every time (nnrt_fitter_iterate_from_identity / _from_snapshot) are refused");
+			return NNRT_ERROR_ARGUMENT;
+		}
+		// a fit starts: the state machine restarts (outside the captured sequences, which stay the same launches)
+		if (first_iteration == 0 && count > 0 && (st = launch_step_reset(ft->step_state.ptr, step_initial_lambda(ft), us))) return st;
+	}
 	for (int it0 = first_iteration; it0 < first_iteration + count; it0 += MAX_GRAPH_ITERATIONS) {
 		const int n = std::min(MAX_GRAPH_ITERATIONS, first_iteration + count - it0);
 		std::vector<int> modes(static_cast<size_t>(n));
@@ -989,6 +1073,8 @@ nnrt_status nnrt_fitter_set_robust_options(nnrt_fitter* ft, int32_t penalty_form
 	NNRT_CHECK_ARG(penalty_form == NNRT_PENALTY_REFERENCE || penalty_form == NNRT_PENALTY_IRLS,
 	               "penalty_form must be NNRT_PENALTY_REFERENCE (0) or NNRT_PENALTY_IRLS (1)");
 	NNRT_CHECK_ARG(guard_zero_rotation == 0 || guard_zero_rotation == 1, "guard_zero_rotation must be 0 or 1");
+	NNRT_CHECK_ARG(!(ft->step_on && penalty_form == NNRT_PENALTY_IRLS),
+	               "penalty_form: NNRT_PENALTY_IRLS is refused while step control is on (its cost is the square objective)");
 	if (penalty_form == ft->penalty_form && guard_zero_rotation == ft->guard_zero_rotation) return NNRT_OK;
 	DeviceGuard guard(ft->device);
 	NNRT_HIP(hipStreamSynchronize(ft->work));
@@ -1019,6 +1105,81 @@ nnrt_status nnrt_fitter_set_data_coupling(nnrt_fitter* ft, int32_t data_coupling
 nnrt_status nnrt_fitter_get_data_coupling(const nnrt_fitter* ft, int32_t* data_coupling) {
 	NNRT_CHECK_ARG(ft && data_coupling, "null pointer");
 	*data_coupling = ft->data_coupling;
+	return NNRT_OK;
+}
+
+nnrt_status nnrt_fitter_set_step_control(nnrt_fitter* ft, const nnrt_step_control* settings) {
+	nnrt_step_control v{};
+	if (settings) {   // the ranges first: they need no fitter
+		v = *settings;
+		// (every comparison is false for a NaN, which is refused with the rest)
+		NNRT_CHECK_ARG(v.initial_lambda >= 0.f && std::isfinite(v.initial_lambda), "step control: initial_lambda must be finite and >= 0 (0: preconditioning_dampening_factor)");
+		NNRT_CHECK_ARG(v.increase > 1.f && std::isfinite(v.increase), "step control: increase must be finite and > 1");
+		NNRT_CHECK_ARG(v.decrease > 0.f && v.decrease <= 1.f, "step control: decrease must lie in (0, 1]");
+		NNRT_CHECK_ARG(v.lambda_min >= 0.f && v.lambda_max >= v.lambda_min && v.lambda_max > 0.f && std::isfinite(v.lambda_max),
+		               "step control: lambda_min / lambda_max must satisfy 0 <= lambda_min <= lambda_max, 0 < lambda_max < inf");
+		NNRT_CHECK_ARG(v.relative_cost_tolerance >= 0.f && std::isfinite(v.relative_cost_tolerance),
+		               "step control: relative_cost_tolerance must be finite and >= 0");
+		NNRT_CHECK_ARG(v.poll_interval >= 0, "step control: poll_interval must be >= 0");
+	}
+	NNRT_CHECK_ARG(ft, "null pointer");
+	if (settings) {
+		NNRT_CHECK_ARG(ft->penalty_form != NNRT_PENALTY_IRLS,
+		               "step control is refused while NNRT_PENALTY_IRLS is set (SQUARE penalties only: the residual buffer holds the scaled residual)");
+		for (int i = 0; i < ft->p.iteration_mode_count; i++)
+			NNRT_CHECK_ARG(ft->p.iteration_modes[i] == NNRT_ITERATION_ALL,
+			               "step control supports IterationMode ALL only, and the fitter's mode list holds another");
+	}
+	const bool on = settings != nullptr;
+	if (on == ft->step_on && std::memcmp(&v, &ft->step, sizeof(v)) == 0) return NNRT_OK;
+	DeviceGuard guard(ft->device);
+	NNRT_HIP(hipStreamSynchronize(ft->work));
+	ft->step_on = on;
+	ft->step = v;
+	ft->drop_graphs();      // the captured sequences hold the launches of the other mode
+	ft->prepared = false;   // the state machine's buffers are prepare()'s
+	if (!on) {              // nothing of the mode stays allocated
+		ft->step_state.release();
+		ft->step_history.release();
+		ft->step_best.release();
+		ft->step_partials.release();
+	}
+	return NNRT_OK;
+}
+
+nnrt_status nnrt_fitter_get_step_control(const nnrt_fitter* ft, int32_t* enabled, nnrt_step_control* settings) {
+	NNRT_CHECK_ARG(ft && enabled, "null pointer");
+	*enabled = ft->step_on ? 1 : 0;
+	if (settings) *settings = ft->step;
+	return NNRT_OK;
+}
+
+namespace {
+// the device's state word, after everything enqueued on the caller's stream (and the work stream) has run
+nnrt_status read_step_state(nnrt_fitter* ft, hipStream_t us, StepState* out) {
+	NNRT_HIP(hipStreamSynchronize(us));
+	NNRT_HIP(hipStreamSynchronize(ft->work));
+	NNRT_HIP(hipMemcpy(out, ft->step_state.ptr, sizeof(StepState), hipMemcpyDeviceToHost));
+	return NNRT_OK;
+}
+} // namespace
+
+nnrt_status nnrt_fitter_get_step_history(nnrt_fitter* ft, nnrt_step_record* records, int64_t capacity, int64_t* out_count, void* stream) {
+	NNRT_CHECK_ARG(ft && out_count, "null pointer");
+	*out_count = 0;
+	if (!ft->step_on || !ft->prepared || !ft->step_state.ptr) return NNRT_OK;
+	DeviceGuard guard(ft->device);
+	StepState ss;
+	nnrt_status st = read_step_state(ft, static_cast<hipStream_t>(stream), &ss);
+	if (st) return st;
+	const int64_t total = ss.iteration, n = std::min<int64_t>(total, NNRT_STEP_HISTORY_CAPACITY);
+	*out_count = n;
+	// the host buffer holds `capacity` records: fewer than there are is refused, not written past
+	NNRT_CHECK_ARG(capacity >= n && (records || n == 0), "capacity is smaller than the number of step records");
+	if (n == 0) return NNRT_OK;
+	std::vector<nnrt_step_record> ring(NNRT_STEP_HISTORY_CAPACITY);
+	NNRT_HIP(hipMemcpy(ring.data(), ft->step_history.ptr, sizeof(nnrt_step_record) * ring.size(), hipMemcpyDeviceToHost));
+	for (int64_t k = 0; k < n; k++) records[k] = ring[static_cast<size_t>((total - n + k) % NNRT_STEP_HISTORY_CAPACITY)];
 	return NNRT_OK;
 }
 
@@ -1237,6 +1398,10 @@ nnrt_status nnrt_fitter_time_kernels(nnrt_fitter* ft, nnrt_warp_field* wf, int32
 		NNRT_HIP(hipMemsetAsync(ft->acc.ptr, 0, sizeof(double) * static_cast<size_t>(ft->key.N) * ACC_STRIDE, s));
 		NNRT_HIP(hipStreamSynchronize(s));
 		NNRT_HIP(hipMemcpy(ft->error_flag.ptr, &pending_flag, sizeof(int), hipMemcpyHostToDevice));
+		// the replays drove step control's state machine: it restarts (a fit in progress does not survive the timing)
+		if (ft->step_on) {
+			if (nnrt_status rs = launch_step_reset(ft->step_state.ptr, step_initial_lambda(ft), s)) return rs;
+		}
 	}
 	return st ? st : scope.leave();
 }
@@ -1269,13 +1434,29 @@ nnrt_status nnrt_fitter_check(nnrt_fitter* ft, void* stream) {
 	return NNRT_OK;
 }
 
+// a whole frame's iterations: all of them in one call; with step control's poll_interval = k > 0, k at a time, the host
+// reading the device's `done` between the calls and stopping there
+static nnrt_status fit_iterations(nnrt_fitter* ft, nnrt_warp_field* wf, void* stream) {
+	const int total = ft->p.max_iteration_count, k = ft->step_on ? ft->step.poll_interval : 0;
+	if (k <= 0) return nnrt_fitter_iterate(ft, wf, 0, total, stream);
+	for (int it0 = 0; it0 < total; it0 += k) {
+		nnrt_status st = nnrt_fitter_iterate(ft, wf, it0, std::min(k, total - it0), stream);
+		if (st) return st;
+		DeviceGuard guard(ft->device);
+		StepState ss;
+		if ((st = read_step_state(ft, static_cast<hipStream_t>(stream), &ss))) return st;
+		if (ss.done) break;
+	}
+	return NNRT_OK;
+}
+
 nnrt_status nnrt_fitter_fit_to_image(nnrt_fitter* ft, nnrt_warp_field* wf, const float* d_vertices, const float* d_normals, int64_t V,
                                      const int64_t* d_faces, int64_t F, const float* d_depth, const uint8_t* d_mask, int32_t H, int32_t W,
                                      const double* h_K, const double* h_E, float depth_scale, void* stream) {
 	nnrt_status st = nnrt_fitter_prepare(ft, wf, d_vertices, d_normals, V, d_faces, F, d_depth, d_mask, H, W, h_K, h_E, depth_scale, stream);
 	if (st) return st;
 	// A14: the reference never updates `maximum_update`, so the loop always runs max_iteration_count iterations
-	if ((st = nnrt_fitter_iterate(ft, wf, 0, ft->p.max_iteration_count, stream))) return st;
+	if ((st = fit_iterations(ft, wf, stream))) return st;
 	return nnrt_fitter_check(ft, stream);
 }
 
@@ -1284,7 +1465,7 @@ nnrt_status nnrt_fitter_fit_to_point_cloud(nnrt_fitter* ft, nnrt_warp_field* wf,
                                            int32_t W, const double* h_K, const double* h_E, void* stream) {
 	nnrt_status st = nnrt_fitter_prepare_point_cloud(ft, wf, d_vertices, d_normals, V, d_faces, F, d_points, d_point_mask, H, W, h_K, h_E, stream);
 	if (st) return st;
-	if ((st = nnrt_fitter_iterate(ft, wf, 0, ft->p.max_iteration_count, stream))) return st;
+	if ((st = fit_iterations(ft, wf, stream))) return st;
 	return nnrt_fitter_check(ft, stream);
 }
 

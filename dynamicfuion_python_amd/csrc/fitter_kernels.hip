@@ -1522,8 +1522,9 @@ __device__ inline void apply_update(float* ns, const float* old, const float* x,
 
 // IDENTITY: the node's motion before the update is R = I, t = 0 (iterate-from-identity) and is not read. Otherwise the
 // (t, R) row is loaded up front so its latency overlaps the accumulator loads.
-template <int MODE, bool IDENTITY>
-__global__ __launch_bounds__(64) void k_solve_update(SolveArgs a) {
+// Args: SolveArgs (the damping a launch argument) or SolveArgsDeviceLm (a device word, step control)
+template <int MODE, bool IDENTITY, class Args = SolveArgs>
+__global__ __launch_bounds__(64) void k_solve_update(Args a) {
 	using T = ModeTraits<MODE>;
 	constexpr int S = T::S;
 	const int n = blockIdx.x * blockDim.x + threadIdx.x;
@@ -1586,9 +1587,10 @@ __global__ __launch_bounds__(64) void k_solve_update(SolveArgs a) {
 	}
 #pragma unroll
 	for (int c = 0; c < S; c++) a.gradient_out[static_cast<int64_t>(n) * S + c] = g[c];
-	if (a.lm > 0.f) {
+	const float lm = lm_value(a.lm);
+	if (lm > 0.f) {
 #pragma unroll
-		for (int i = 0; i < S; i++) H[i][i] += a.lm;
+		for (int i = 0; i < S; i++) H[i][i] += lm;
 	}
 	float x[S];
 	if (!cholesky_small<S>(H)) {
@@ -1634,8 +1636,8 @@ __device__ __forceinline__ float group_bcast(float v, int j) {
 	return __builtin_bit_cast(float, in_quad ? same : other);
 }
 
-template <int MODE, bool IDENTITY>
-__global__ __launch_bounds__(64) void k_solve_update_lanes(SolveArgs a) {
+template <int MODE, bool IDENTITY, class Args = SolveArgs>
+__global__ __launch_bounds__(64) void k_solve_update_lanes(Args a) {
 	using T = ModeTraits<MODE>;
 	constexpr int S = T::S;
 	constexpr int NPW = 64 / SOLVE_GL;   // nodes per wave
@@ -1686,10 +1688,11 @@ __global__ __launch_bounds__(64) void k_solve_update_lanes(SolveArgs a) {
 		}
 		a.gradient_out[static_cast<int64_t>(n) * S + r] = gr;
 	}
-	if (a.lm > 0.f) {
+	const float lm = lm_value(a.lm);
+	if (lm > 0.f) {
 #pragma unroll
 		for (int c = 0; c < S; c++)
-			if (c == r) h[c] += a.lm;
+			if (c == r) h[c] += lm;
 	}
 	// factor: lane r holds L_r0 .. L_rr in h[0 .. r]
 	bool bad = false;
@@ -1770,6 +1773,16 @@ static nnrt_status solve_update_mode(int mode, const SolveArgs& args, hipStream_
 nnrt_status launch_solve_update(int mode, const SolveArgs& args, hipStream_t stream, bool from_identity) {
 	const nnrt_status st = from_identity ? solve_update_mode<true>(mode, args, stream) : solve_update_mode<false>(mode, args, stream);
 	if (st) return st;
+	NNRT_LAUNCH_CHECK();
+	return NNRT_OK;
+}
+
+nnrt_status launch_solve_update_device_lm(const SolveArgsDeviceLm& args, hipStream_t stream) {
+#if NNRT_SOLVE_LANES
+	k_solve_update_lanes<NNRT_ITERATION_ALL, false, SolveArgsDeviceLm><<<static_cast<unsigned>(ceil_div(args.N, 64 / SOLVE_GL)), 64, 0, stream>>>(args);
+#else
+	k_solve_update<NNRT_ITERATION_ALL, false, SolveArgsDeviceLm><<<static_cast<unsigned>(ceil_div(args.N, 64)), 64, 0, stream>>>(args);
+#endif
 	NNRT_LAUNCH_CHECK();
 	return NNRT_OK;
 }

@@ -203,9 +203,12 @@ struct FitPixelArgs {
 	const int* quad_order;  // [4 * order_blocks] wave -> 8 x 8 quadrant (launch_quad_order; nullable; takes precedence)
 };
 
-struct SolveArgs {
+// Lm: how the launch receives the Levenberg-Marquardt damping -- `float`, a launch argument (the default), or
+// `const float*`, a device word read when the kernel runs (step control: the previous launch of the iteration chose it)
+template <class Lm>
+struct SolveArgsT {
 	int N;
-	float lm;
+	Lm lm;
 	double* acc;
 	const float* state_in;  // [N,16] the motion the iteration started from (read)
 	float* node_state;      // [N,16] updated motion (written; may equal state_in)
@@ -215,6 +218,10 @@ struct SolveArgs {
 	int* error_flag;
 	int guard_zero_rotation;   // 1: a node whose rotation update has angle exactly 0 keeps its R (0: Rodrigues' NaN, A7)
 };
+using SolveArgs = SolveArgsT<float>;
+using SolveArgsDeviceLm = SolveArgsT<const float*>;
+__device__ inline float lm_value(float lm) { return lm; }
+__device__ inline float lm_value(const float* lm) { return *lm; }
 
 // Per face (once per frame, after the anchors): the face's distinct anchor nodes in ascending order, each with, per face
 // vertex, the LAST anchor slot holding it (AssociateFacesWithAnchorsImpl.h:34-107): entry = node << 12 | k2 << 8 | k1 << 4 | k0
@@ -243,6 +250,8 @@ int quad_order_blocks(int quadrants);
 inline size_t quad_order_scratch(int quadrants) { return 2 * static_cast<size_t>(quadrants) + 1; }
 nnrt_status launch_quad_order(const float4* ref_points, int H, int W, int tiles_x, int tiles_y, int slots, int* scratch, int* order, hipStream_t stream);
 nnrt_status launch_solve_update(int mode, const SolveArgs& args, hipStream_t stream, bool from_identity = false);
+// the same launch with the damping read from the device (mode ALL, never from the identity: step control's iterations)
+nnrt_status launch_solve_update_device_lm(const SolveArgsDeviceLm& args, hipStream_t stream);
 
 
 constexpr int CORNER_NB = 64;   // Schur-corner tile size (tile columns are padded to a multiple with identity)
@@ -514,7 +523,8 @@ StemSchurLists build_stem_schur_lists(const int32_t* edges, int E, int n0, int N
 // acc -> diagonal blocks (+lm) + rhs ; arrowhead solve ; update node state
 nnrt_status launch_arrowhead_iteration(const ArrowheadWorkspace& ws, const double* acc, float lm, const int32_t* edges, const float* wing,
                                        float* node_state, const float* edge_jr, float* updates_out, float* gradient_out, float* hessian_out,
-                                       int* error_flag, hipStream_t stream, const float* state_in = nullptr);
+                                       int* error_flag, hipStream_t stream, const float* state_in = nullptr, const float* lm_device = nullptr);
+// (lm_device, nullable: the damping is read from this device word instead of `lm`; step control)
 // arap_wings: the wing blocks have the ARAP structure dEi^T [0 | b I] (zero outside their last three columns);
 // node_state / updates_out (fitter): apply the solved increments to the node motion in the back-substitution launch;
 // state_in (default: node_state): the motion the iteration started from (a snapshot the iteration restarts from)

@@ -65,7 +65,7 @@ from ..data.frame import FrameSequenceDataset
 from ..nnrt import geometry as G
 from ..nnrt import image_proc
 from ..nnrt import rendering
-from ..nnrt.alignment import NDC_CONSISTENT, DataCoupling, align_rigid_point_to_plane
+from ..nnrt.alignment import NDC_CONSISTENT, DataCoupling, StepControl, align_rigid_point_to_plane
 from ..warp_field.graph_warp_field import build_graph_nodes_from_depth_image, extend_warp_field, sample_graph_nodes_from_mesh
 
 
@@ -167,12 +167,17 @@ class FusionParameters:
     # the full Gauss-Newton step (DataCoupling.COUPLED) in place of the reference's block-diagonal data
     # Hessian; real sequences should turn it on. Overrides alignment.data_coupling when set.
     coupled_data_term: bool = False
+    # on-device step control of the non-rigid fit (StepControl): a step is kept only if the cost fell, so a
+    # frame's fit cannot end worse than it began. SQUARE penalties only (this loop's default). Overrides
+    # alignment.step_control when set.
+    step_control: Optional[StepControl] = None
 
 
 def alignment_parameters(p: FusionParameters) -> RenderingAlignmentParameters:
     """The optimizer's parameters for these fusion parameters: p.alignment, in DataCoupling.COUPLED mode when
-    coupled_data_term is set."""
-    return dataclasses.replace(p.alignment, data_coupling=DataCoupling.COUPLED) if p.coupled_data_term else p.alignment
+    coupled_data_term is set and with step_control where that is set."""
+    a = dataclasses.replace(p.alignment, data_coupling=DataCoupling.COUPLED) if p.coupled_data_term else p.alignment
+    return dataclasses.replace(a, step_control=p.step_control) if p.step_control is not None else a
 
 
 @dataclass
@@ -199,6 +204,11 @@ class FrameResult:
     model_depth_mean_abs: float = 0.0
     model_depth_rmse: float = 0.0
     model_inlier_ratio: float = 0.0
+    # FusionParameters.step_control (0 while it is off): iterations up to and including the one that stopped the fit, the
+    # cost of the state the fit ended on, and the steps it rejected
+    iterations_used: int = 0
+    final_cost: float = 0.0
+    rejected_step_count: int = 0
 
 
 def remap_edges_to_node_order(edges, order) -> np.ndarray:
@@ -478,6 +488,10 @@ class FusionPipeline:
             if res.canonical_triangle_count > 0:
                 self.optimizer.optimize_graph(self.active_graph, canonical, points, extrinsics=self.extrinsics)
                 res.tracked = True
+                summary = self.optimizer.last_step_summary
+                if summary is not None:
+                    res.iterations_used, res.final_cost = summary["iterations_used"], summary["final_cost"]
+                    res.rejected_step_count = summary["rejected_step_count"]
                 if p.model_agreement:
                     agreement, _ = self.measure_model_agreement(depth)
                     res.model_overlap_count, res.model_only_count, res.frame_only_count = agreement.both, agreement.model_only, agreement.frame_only

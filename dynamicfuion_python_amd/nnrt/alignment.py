@@ -3,6 +3,7 @@
 from __future__ import annotations
 
 import ctypes
+import dataclasses
 import enum
 
 import numpy as np
@@ -39,6 +40,59 @@ class DataCoupling(enum.IntEnum):
     (DESIGN section 23). Real sequences should use COUPLED: the block-diagonal step diverges after its first iteration."""
     BLOCK_DIAGONAL = 0
     COUPLED = 1
+
+
+class StepDecision(enum.IntEnum):
+    """What one iteration under step control decided (include/nnrt_mi355x.h NNRT_STEP_*)."""
+    HOLD = 0            # the fit was done already: the frozen state is re-evaluated
+    START = 1           # first iteration, or the one after a reject: the state becomes the best state, then a step
+    ACCEPT = 2          # the cost fell: new best state, lambda shrinks, step
+    CONVERGED = 3       # the cost fell by no more than the relative tolerance: new best state, done
+    REJECT = 4          # the cost rose (or is not finite): best state put back, lambda grows
+    REJECT_FINAL = 5    # a reject with lambda already at lambda_max: done
+    SMALL_UPDATE = 6    # a step whose max |update| is below minimal_update_threshold: best state put back, done
+
+
+STEP_DONE_DECISIONS = (StepDecision.CONVERGED, StepDecision.REJECT_FINAL, StepDecision.SMALL_UPDATE)
+
+
+@dataclasses.dataclass(frozen=True)
+class StepControl:
+    """Settings of the fitter's on-device step control (nnrt_step_control): keep a Gauss-Newton step
+    only if the cost fell, damp harder if not, stop when nothing moves. IterationMode.ALL and SQUARE penalties only.
+    initial_lambda 0 starts from preconditioning_dampening_factor. poll_interval k > 0: fit_to_image synchronises every k
+    iterations and returns once the device reports done; 0: never synchronises."""
+    initial_lambda: float = 0.0
+    increase: float = 10.0
+    decrease: float = 0.5
+    lambda_min: float = 1e-6
+    lambda_max: float = 1.0
+    relative_cost_tolerance: float = 1e-4
+    poll_interval: int = 0
+
+
+@dataclasses.dataclass(frozen=True)
+class StepRecord:
+    """One iteration of a fit under step control: the cost of the state it started from, the damping its solve used, its
+    decision and (stepping iterations) the largest absolute update."""
+    iteration: int
+    cost: float
+    lambda_used: float
+    decision: StepDecision
+    max_update: float
+
+
+def summarize_step_history(history) -> dict:
+    """iterations_used, final_cost, rejected_step_count and done of a list of StepRecords (zeros for an empty one)."""
+    used, done, final_cost, rejected = len(history), False, 0.0, 0
+    for i, r in enumerate(history):
+        if r.decision in (StepDecision.START, StepDecision.ACCEPT, StepDecision.CONVERGED):
+            final_cost = r.cost   # the best state's cost
+        if r.decision in (StepDecision.REJECT, StepDecision.REJECT_FINAL):
+            rejected += 1
+        if not done and (r.decision in STEP_DONE_DECISIONS or r.decision == StepDecision.HOLD):
+            used, done = (i + 1 if r.decision != StepDecision.HOLD else i), True
+    return dict(iterations_used=used, final_cost=float(final_cost), rejected_step_count=rejected, done=done)
 
 
 NDC_REFERENCE = 0     # the reference's image -> NDC mapping (SURVEY A11)
@@ -225,6 +279,39 @@ class DeformableMeshToImageFitter:
         N.check(N.lib().nnrt_fitter_get_coupled_system(self._h, N.ptr(d), N.ptr(pairs), N.ptr(blocks), N.ptr(b), n, m, N.stream_ptr(stream)))
         return d, pairs, blocks, b
 
+    def set_step_control(self, step_control: StepControl | None):
+        """Turn the on-device step control on with these settings, or off with None (the default: every output as
+        without it). A change drops the cached graphs and invalidates the prepared frame: call prepare() again.
+        Out-of-range settings, PenaltyForm.IRLS, or a mode list holding another mode than ALL raise."""
+        if step_control is None:
+            N.check(N.lib().nnrt_fitter_set_step_control(self._h, None))
+            return
+        c = step_control
+        s = N.StepControlSettings(float(c.initial_lambda), float(c.increase), float(c.decrease), float(c.lambda_min), float(c.lambda_max),
+                                  float(c.relative_cost_tolerance), int(c.poll_interval))
+        N.check(N.lib().nnrt_fitter_set_step_control(self._h, ctypes.byref(s)))
+
+    @property
+    def step_control(self) -> StepControl | None:
+        on, s = ctypes.c_int32(), N.StepControlSettings()
+        N.check(N.lib().nnrt_fitter_get_step_control(self._h, ctypes.byref(on), ctypes.byref(s)))
+        if not on.value:
+            return None
+        return StepControl(s.initial_lambda, s.increase, s.decrease, s.lambda_min, s.lambda_max, s.relative_cost_tolerance, s.poll_interval)
+
+    def step_history(self, stream=None) -> list:
+        """The StepRecords of the iterations since the fit started (iterate() from iteration 0), oldest first: at most
+        the last 256. Empty with step control off. Synchronizes."""
+        buf = (N.StepRecord * N.STEP_HISTORY_CAPACITY)()
+        n = ctypes.c_int64()
+        N.check(N.lib().nnrt_fitter_get_step_history(self._h, buf, N.STEP_HISTORY_CAPACITY, ctypes.byref(n), N.stream_ptr(stream)))
+        return [StepRecord(r.iteration, r.cost, r.lambda_, StepDecision(r.decision), r.max_update) for r in buf[: n.value]]
+
+    def step_summary(self, stream=None) -> dict:
+        """From step_history(): iterations_used (up to and including the one that set done; all of them otherwise),
+        final_cost (the best state's, which the fit ends on), rejected_step_count and done. Zeros with step control off."""
+        return summarize_step_history(self.step_history(stream))
+
     @property
     def graph_count(self) -> int:
         """Instantiated iteration-sequence graphs the fitter holds."""
@@ -275,7 +362,16 @@ class DeformableMeshToImageFitter:
             self.prepare(warp_field, canonical_mesh, depth, mask, K, E, scale)
         else:
             raise TypeError("fit_to_image: no overload matches the arguments (see DeformableMeshToImageFitter.h:58-90)")
-        self.iterate(warp_field, 0, self.params.max_iteration_count)
+        total = self.params.max_iteration_count
+        control = self.step_control
+        k = control.poll_interval if control is not None else 0
+        if k <= 0:
+            self.iterate(warp_field, 0, total)
+        else:   # step control's host early exit: k iterations at a time until the device reports done
+            for first in range(0, total, k):
+                self.iterate(warp_field, first, min(k, total - first))
+                if self.step_summary()["done"]:
+                    break
         self.check()
 
     def diagnostics(self, stream=None) -> dict:

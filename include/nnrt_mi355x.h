@@ -93,7 +93,7 @@ typedef struct nnrt_fitter_params {
 	int32_t max_iteration_count;            /* 100 */
 	int32_t iteration_mode_count;           /* 1 */
 	int32_t iteration_modes[16];            /* {NNRT_ITERATION_ALL} */
-	float minimal_update_threshold;         /* 1e-6 (never effective in the reference: A14) */
+	float minimal_update_threshold;         /* 1e-6 (never effective in the reference: A14; step control gives it effect) */
 	int32_t use_perspective_correction;     /* 1 */
 	float max_depth;                        /* 10 */
 	int32_t use_tukey_penalty_for_data_term;/* 0 */
@@ -236,6 +236,71 @@ int64_t nnrt_fitter_coupled_pair_count(const nnrt_fitter* fitter);
  * h_rhs [6N] right-hand side (negative gradient). node_count / pair_count must equal the prepared frame's. */
 nnrt_status nnrt_fitter_get_coupled_system(nnrt_fitter* fitter, float* h_diag, int32_t* h_pairs, float* h_blocks, float* h_rhs,
                                            int64_t node_count, int64_t pair_count, void* stream);
+/* Step control, off by default: with it off every launch, the launch plan, the graph count and
+ * every output are what they were. With it on, every iteration forms the total cost c of the state it starts from (the
+ * fp64 sum over the residual mask of the squared float residuals, plus the squared ARAP edge residuals with a hierarchy;
+ * per-workgroup partial sums in a fixed order, then one lane sums the partials in index order: no atomics on the sum, a
+ * graph replay equals the eager run) and decides ON THE DEVICE, so an iteration stays one fixed sequence of launches:
+ *   done already                         NNRT_STEP_HOLD
+ *   first iteration, or after a reject   NNRT_STEP_START   c_best = c, best motion = current, lambda unchanged, step
+ *   c <= c_best                          best motion = current, then: (c_best - c) <= relative_cost_tolerance * c_best:
+ *                                        NNRT_STEP_CONVERGED (done, hold); else NNRT_STEP_ACCEPT, lambda =
+ *                                        max(lambda * decrease, lambda_min), step; c_best = c in both
+ *   anything else (a non-finite c too)   NNRT_STEP_REJECT  lambda = min(lambda * increase, lambda_max), hold; the next
+ *                                        iteration re-linearises the restored best state under the larger lambda (a
+ *                                        rejection costs two iterations). lambda already at lambda_max:
+ *                                        NNRT_STEP_REJECT_FINAL, done
+ * The solve launches read lambda from the device. At the end of the iteration a held iteration puts the best motion back
+ * (the solve's update is discarded, and so are the error bits it raised: the error word is saved at the decision and
+ * restored); a stepping iteration whose max |update| is below minimal_update_threshold puts the best motion back and is
+ * done (NNRT_STEP_SMALL_UPDATE): the one mode in which that parameter has an effect (A14). Every iteration appends one
+ * nnrt_step_record to a ring of NNRT_STEP_HISTORY_CAPACITY records. nnrt_fitter_iterate with first_iteration == 0
+ * restarts the state machine (lambda = initial_lambda, empty history).
+ * Limits: IterationMode ALL only, and SQUARE penalties only -- under NNRT_PENALTY_IRLS the residual buffer holds the
+ * scaled residual s r, from which the robust objective cannot be evaluated. Enabling step control while
+ * NNRT_PENALTY_IRLS is set, or setting NNRT_PENALTY_IRLS while step control is on, returns NNRT_ERROR_ARGUMENT; so does
+ * a mode list holding another mode than ALL, and nnrt_fitter_iterate_from_identity / _from_snapshot (every iteration a
+ * restart) while it is on. An ARAP edge the fixed-coverage weight lookup refuses (quirk A3, error bit 2 of
+ * nnrt_fitter_check) contributes 0 to the cost; that fit is reported as failed anyway.
+ *  initial_lambda: 0 = preconditioning_dampening_factor; either is clamped into [lambda_min, lambda_max] (a lambda of 0
+ *   never grows: give lambda_min > 0). increase > 1; 0 < decrease <= 1; 0 <= lambda_min <= lambda_max, lambda_max > 0;
+ *   relative_cost_tolerance >= 0; poll_interval >= 0: k > 0 makes nnrt_fitter_fit_to_image / _to_point_cloud synchronise
+ *   after every k iterations and return once the device reports done; 0 (default) never synchronises, the held
+ *   iterations then re-evaluate the frozen state. Values outside these ranges (NaN included) are NNRT_ERROR_ARGUMENT,
+ *   nnrt_last_error() naming the field. settings == NULL turns the mode off. A change drops the fitter's cached graphs (as
+ *   nnrt_fitter_set_data_coupling does) and invalidates the prepared frame: prepare() again before iterating. */
+typedef struct nnrt_step_control {
+	float initial_lambda;
+	float increase;
+	float decrease;
+	float lambda_min;
+	float lambda_max;
+	float relative_cost_tolerance;
+	int32_t poll_interval;
+} nnrt_step_control;
+typedef struct nnrt_step_record {
+	double cost;        /* c of the state the iteration started from */
+	float lambda;       /* the damping the iteration's solve used (after the decision) */
+	float max_update;   /* max |update| of a stepping iteration (+inf if an update is not finite); 0 on a held one */
+	int32_t decision;   /* NNRT_STEP_* */
+	int32_t iteration;  /* index since the restart */
+} nnrt_step_record;
+#define NNRT_STEP_HOLD 0
+#define NNRT_STEP_START 1
+#define NNRT_STEP_ACCEPT 2
+#define NNRT_STEP_CONVERGED 3
+#define NNRT_STEP_REJECT 4
+#define NNRT_STEP_REJECT_FINAL 5
+#define NNRT_STEP_SMALL_UPDATE 6
+#define NNRT_STEP_HISTORY_CAPACITY 256
+nnrt_status nnrt_fitter_set_step_control(nnrt_fitter* fitter, const nnrt_step_control* settings);
+/* *enabled = 0 / 1; *settings (nullable) receives the settings as held (zeros when off). */
+nnrt_status nnrt_fitter_get_step_control(const nnrt_fitter* fitter, int32_t* enabled, nnrt_step_control* settings);
+/* The records of the iterations since the restart, oldest first (synchronizes `stream`): *out_count of them, at most
+ * NNRT_STEP_HISTORY_CAPACITY (the most recent ones of a longer run). A `capacity` below that count is refused with
+ * NNRT_ERROR_ARGUMENT, nothing written, as nnrt_fitter_get_warped_mesh refuses a wrong vertex count; *out_count is still
+ * set, so records == NULL with capacity 0 asks for the count. 0 records with step control off. */
+nnrt_status nnrt_fitter_get_step_history(nnrt_fitter* fitter, nnrt_step_record* records, int64_t capacity, int64_t* out_count, void* stream);
 /* Anchor the canonical mesh along a motion graph's edges instead of by Euclidean distance (the reference's
  * AnchorComputationMethod::SHORTEST_PATH, PlanarGraphWarpField::PrecomputeAnchorsAndWeights; apps/fusion/pipeline.py:577-582):
  * d_edges [node_count, graph_degree] int32 rows in the warp field's virtual node order (entry < 0 = empty) are copied
@@ -273,7 +338,10 @@ nnrt_status nnrt_fitter_iterate_timed(nnrt_fitter* fitter, nnrt_warp_field* warp
  * h_kernel_ms[NNRT_KERNEL_TIMES] = 0 warp (k_warp_mesh_quad), 1 raster (k_raster_scatter_mesh), 2 fused pixel launch
  * (k_fit_pixels_fused), 3 solve + update (k_solve_update; ARAP: the whole arrowhead chain), 4 whole iteration, by
  * differences. Leaves raster keys empty, the accumulators zero and the node motion at the snapshot's one-iteration
- * result. Requires nnrt_fitter_snapshot_motion after the last prepare(). Synchronizes `stream`. */
+ * result. Requires nnrt_fitter_snapshot_motion after the last prepare(). Synchronizes `stream`. With step control on the
+ * solve time includes its two launches; every replayed iteration restarts from the snapshot, so from the third on they
+ * are held iterations (the node motion ends at the snapshot), and the state machine is restarted afterwards (empty
+ * history, initial lambda): a fit in progress does not survive the timing. */
 #define NNRT_KERNEL_TIMES 5
 nnrt_status nnrt_fitter_time_kernels(nnrt_fitter* fitter, nnrt_warp_field* warp_field, int32_t reps, int32_t trials, float* h_kernel_ms,
                                      void* stream);
