@@ -110,6 +110,9 @@ _SIGNATURES = {
     "nnrt_fitter_set_step_control": (c_int32, [c_void_p, ctypes.POINTER(StepControlSettings)]),
     "nnrt_fitter_get_step_control": (c_int32, [c_void_p, ctypes.POINTER(c_int32), ctypes.POINTER(StepControlSettings)]),
     "nnrt_fitter_get_step_history": (c_int32, [c_void_p, ctypes.POINTER(StepRecord), c_int64, ctypes.POINTER(c_int64), c_void_p]),
+    "nnrt_fitter_set_step_objective": (c_int32, [c_void_p, c_int32]),
+    "nnrt_fitter_get_step_objective": (c_int32, [c_void_p, ctypes.POINTER(c_int32)]),
+    "nnrt_fitter_get_raw_residuals": (c_int32, [c_void_p, c_void_p, c_int64, c_void_p]),
     "nnrt_fitter_get_coupled_system": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_void_p]),
     "nnrt_fitter_set_anchor_graph": (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_void_p]),
     "nnrt_fitter_check": (c_int32, [c_void_p, c_void_p]),

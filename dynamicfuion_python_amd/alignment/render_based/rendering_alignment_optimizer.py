@@ -52,8 +52,11 @@ class RenderingAlignmentParameters:
     data_coupling: A.DataCoupling = A.DataCoupling.BLOCK_DIAGONAL
     # On-device step control (DeformableMeshToImageFitter.set_step_control): None (default) runs every
     # iteration with the fixed damping, as the reference does; an A.StepControl keeps a step only if the cost fell.
-    # SQUARE penalties (or PenaltyForm.REFERENCE) and IterationMode.ALL only.
+    # IterationMode.ALL only. Under step_objective = StepObjective.SQUARE (default) SQUARE penalties (or
+    # PenaltyForm.REFERENCE) only; StepObjective.ROBUST compares the robust cost, so PenaltyForm.IRLS
+    # and step control run together: what real sequences want.
     step_control: Optional[A.StepControl] = None
+    step_objective: A.StepObjective = A.StepObjective.SQUARE
 
 
 def as_triangle_mesh(mesh) -> G.TriangleMesh:
@@ -85,7 +88,7 @@ class RenderingAlignmentOptimizer:
             arap_term_weight=p.arap_term_weight,
             use_huber_penalty_for_arap_term=p.regularization_term_penalty_function == PenaltyFunction.HUBER,
             huber_penalty_constant=p.regularization_term_penalty_constant, device=dev, ndc_convention=p.ndc_convention,
-            penalty_form=p.penalty_form, guard_zero_rotation=p.guard_zero_rotation)
+            penalty_form=p.penalty_form, guard_zero_rotation=p.guard_zero_rotation, step_objective=A.StepObjective(p.step_objective))
         self.fitter.set_data_coupling(A.DataCoupling(p.data_coupling))
         self.last_step_summary = None   # DeformableMeshToImageFitter.step_summary() of the last optimize_graph (step control on)
         if p.step_control is not None:

@@ -104,6 +104,10 @@ struct nnrt_fitter {
 	DeviceBuffer<nnrt_step_record> step_history;   // [NNRT_STEP_HISTORY_CAPACITY]
 	DeviceBuffer<float> step_best;                 // [N, STEP_BEST_STRIDE] best motion (t, R)
 	DeviceBuffer<double> step_partials;            // [step_cost_blocks] k_step_cost's partial sums
+	// nnrt_fitter_set_step_objective: the cost step control compares. ROBUST: k_step_cost_robust takes
+	// k_step_cost's place and leaves the raw residuals it resolved in step_raw (allocated by prepare() in that mode)
+	int32_t step_objective = NNRT_STEP_OBJECTIVE_SQUARE;
+	DeviceBuffer<float> step_raw;                  // [P]
 	int last_mode = 0;
 	DeviceBuffer<float> snapshot;   // [N,16] node state stored by nnrt_fitter_snapshot_motion (restore-before-iteration runs)
 	// nnrt_fitter_set_anchor_graph: edge rows [graph_nodes, graph_degree] in the warp field's virtual node order (checked
@@ -179,6 +183,9 @@ float step_initial_lambda(const nnrt_fitter* ft) {
 	const float l = ft->step.initial_lambda > 0.f ? ft->step.initial_lambda : ft->p.preconditioning_dampening_factor;
 	return fminf(fmaxf(l, ft->step.lambda_min), ft->step.lambda_max);
 }
+
+// a Tukey or Huber penalty is enabled in the fitter's parameters (its form is nnrt_fitter_set_robust_options')
+bool penalties_enabled(const nnrt_fitter* ft) { return ft->p.use_tukey_penalty_for_data_term || ft->p.use_huber_penalty_for_arap_term; }
 
 // timing events, destroyed on every return
 struct Events {
@@ -390,7 +397,37 @@ nnrt_status enqueue_iteration(nnrt_fitter* ft, const nnrt_warp_field* wf, int mo
 		ca.lambda_min = ft->step.lambda_min;
 		ca.lambda_max = ft->step.lambda_max;
 		ca.relative_cost_tolerance = ft->step.relative_cost_tolerance;
-		if ((st = launch_step_cost(ca, s))) return st;
+		if (ft->step_objective == NNRT_STEP_OBJECTIVE_ROBUST) {
+			// the robust cost of the raw residuals: the kernel resolves each masked pixel again from the buffers the warp, the
+			// scatter and the fused launch left (nothing between that launch and this one writes them: the pair launch
+			// above only reads), one item per pixel and per edge
+			StepCostRobustArgs ra{};
+			ca.blocks = step_cost_blocks(ca.P + ft->key.E);
+			ca.chunk = step_cost_chunk(ca.P + ft->key.E, ca.blocks);
+			ra.base = ca;
+			ra.F = ft->key.F;
+			ra.E = ft->key.E;
+			ra.W = ft->key.W;
+			ra.perspective = fa.perspective;
+			ra.use_tukey = fa.use_tukey == PENALTY_IRLS;
+			ra.use_huber = ft->key.E > 0 && fa.arap.use_huber == PENALTY_IRLS;
+			ra.tukey_c = fa.tukey_c;
+			ra.huber_delta = ft->p.huber_penalty_constant;
+			ra.blur = fa.blur;
+			ra.ax = fa.ax;
+			ra.ay = fa.ay;
+			ra.ndc = fa.ndc;
+			ra.pix = fa.pix;
+			ra.pixel_face = fa.pixel_face;
+			ra.faces4 = fa.faces4;
+			ra.wpos = fa.wpos;
+			ra.wnrm = fa.wnrm;
+			ra.ref_points = fa.ref_points;
+			ra.raw = ft->step_raw.ptr;
+			if ((st = launch_step_cost_robust(ra, s))) return st;
+		} else if ((st = launch_step_cost(ca, s))) {
+			return st;
+		}
 	}
 	if (coupled) {
 		// diagonal blocks (data + ARAP + LM) and right-hand side as on the arrowhead path, the pair blocks, then the
@@ -692,6 +729,7 @@ nnrt_status prepare_frame(nnrt_fitter* ft, nnrt_warp_field* wf, const float* d_v
 		    (st = ensure(ft->step_best, static_cast<size_t>(N) * STEP_BEST_STRIDE)) ||
 		    (st = ensure(ft->step_partials, static_cast<size_t>(step_cost_blocks(P + 3 * static_cast<int64_t>(E))))))
 			return st;
+		if (ft->step_objective == NNRT_STEP_OBJECTIVE_ROBUST && (st = ensure(ft->step_raw, P))) return st;
 	}
 	key.corner_generation = ft->corner.generation;
 	// any other change of what the graphs bake in drops them too
@@ -786,6 +824,8 @@ nnrt_status prepare_frame(nnrt_fitter* ft, nnrt_warp_field* wf, const float* d_v
 		if ((st = launch_step_reset(ft->step_state.ptr, step_initial_lambda(ft), s))) return st;
 		// an edge the ARAP launch refuses (A3, error bit 2) writes no residual: the cost then sums zeros there, not stale values
 		if (E > 0) NNRT_HIP(hipMemsetAsync(ft->edge_residuals.ptr, 0, sizeof(float) * 3 * static_cast<size_t>(E), s));
+		// nnrt_fitter_get_raw_residuals before the first iteration reads zeros
+		if (ft->step_objective == NNRT_STEP_OBJECTIVE_ROBUST) NNRT_HIP(hipMemsetAsync(ft->step_raw.ptr, 0, sizeof(float) * static_cast<size_t>(P), s));
 	}
 	if ((st = scope.leave())) return st;
 	ft->prepared = true;
@@ -1073,8 +1113,11 @@ nnrt_status nnrt_fitter_set_robust_options(nnrt_fitter* ft, int32_t penalty_form
 	NNRT_CHECK_ARG(penalty_form == NNRT_PENALTY_REFERENCE || penalty_form == NNRT_PENALTY_IRLS,
 	               "penalty_form must be NNRT_PENALTY_REFERENCE (0) or NNRT_PENALTY_IRLS (1)");
 	NNRT_CHECK_ARG(guard_zero_rotation == 0 || guard_zero_rotation == 1, "guard_zero_rotation must be 0 or 1");
-	NNRT_CHECK_ARG(!(ft->step_on && penalty_form == NNRT_PENALTY_IRLS),
+	NNRT_CHECK_ARG(!(ft->step_on && penalty_form == NNRT_PENALTY_IRLS && ft->step_objective == NNRT_STEP_OBJECTIVE_SQUARE),
 	               "penalty_form: NNRT_PENALTY_IRLS is refused while step control is on (its cost is the square objective)");
+	NNRT_CHECK_ARG(!(ft->step_objective == NNRT_STEP_OBJECTIVE_ROBUST && penalty_form == NNRT_PENALTY_REFERENCE && penalties_enabled(ft)),
+	               "penalty_form: NNRT_PENALTY_REFERENCE with a penalty enabled is refused under NNRT_STEP_OBJECTIVE_ROBUST (the "
+	               "reference's branches have no objective)");
 	if (penalty_form == ft->penalty_form && guard_zero_rotation == ft->guard_zero_rotation) return NNRT_OK;
 	DeviceGuard guard(ft->device);
 	NNRT_HIP(hipStreamSynchronize(ft->work));
@@ -1124,7 +1167,7 @@ nnrt_status nnrt_fitter_set_step_control(nnrt_fitter* ft, const nnrt_step_contro
 	}
 	NNRT_CHECK_ARG(ft, "null pointer");
 	if (settings) {
-		NNRT_CHECK_ARG(ft->penalty_form != NNRT_PENALTY_IRLS,
+		NNRT_CHECK_ARG(ft->penalty_form != NNRT_PENALTY_IRLS || ft->step_objective == NNRT_STEP_OBJECTIVE_ROBUST,
 		               "step control is refused while NNRT_PENALTY_IRLS is set (SQUARE penalties only: the residual buffer holds the scaled residual)");
 		for (int i = 0; i < ft->p.iteration_mode_count; i++)
 			NNRT_CHECK_ARG(ft->p.iteration_modes[i] == NNRT_ITERATION_ALL,
@@ -1143,7 +1186,48 @@ nnrt_status nnrt_fitter_set_step_control(nnrt_fitter* ft, const nnrt_step_contro
 		ft->step_history.release();
 		ft->step_best.release();
 		ft->step_partials.release();
+		ft->step_raw.release();
 	}
+	return NNRT_OK;
+}
+
+nnrt_status nnrt_fitter_set_step_objective(nnrt_fitter* ft, int32_t objective) {
+	NNRT_CHECK_ARG(objective == NNRT_STEP_OBJECTIVE_SQUARE || objective == NNRT_STEP_OBJECTIVE_ROBUST,
+	               "objective must be NNRT_STEP_OBJECTIVE_SQUARE (0) or NNRT_STEP_OBJECTIVE_ROBUST (1)");
+	NNRT_CHECK_ARG(ft, "null pointer");
+	NNRT_CHECK_ARG(!(objective == NNRT_STEP_OBJECTIVE_ROBUST && ft->penalty_form == NNRT_PENALTY_REFERENCE && penalties_enabled(ft)),
+	               "objective: NNRT_STEP_OBJECTIVE_ROBUST is refused with NNRT_PENALTY_REFERENCE and a penalty enabled (the reference's "
+	               "branches have no objective)");
+	NNRT_CHECK_ARG(!(objective == NNRT_STEP_OBJECTIVE_SQUARE && ft->step_on && ft->penalty_form == NNRT_PENALTY_IRLS),
+	               "objective: NNRT_STEP_OBJECTIVE_SQUARE is refused while step control is on and NNRT_PENALTY_IRLS is set (SQUARE "
+	               "penalties only under that objective)");
+	if (objective == ft->step_objective) return NNRT_OK;
+	DeviceGuard guard(ft->device);
+	NNRT_HIP(hipStreamSynchronize(ft->work));
+	ft->step_objective = objective;
+	ft->drop_graphs();   // the captured sequences hold the other cost launch
+	if (objective == NNRT_STEP_OBJECTIVE_SQUARE) ft->step_raw.release();
+	// with step control on, the raw residual buffer is prepare()'s, and the state machine restarts there
+	if (ft->step_on) ft->prepared = false;
+	return NNRT_OK;
+}
+
+nnrt_status nnrt_fitter_get_step_objective(const nnrt_fitter* ft, int32_t* objective) {
+	NNRT_CHECK_ARG(ft && objective, "null pointer");
+	*objective = ft->step_objective;
+	return NNRT_OK;
+}
+
+nnrt_status nnrt_fitter_get_raw_residuals(nnrt_fitter* ft, float* h_out, int64_t count, void* stream) {
+	NNRT_CHECK_ARG(ft && h_out, "null pointer");
+	NNRT_CHECK_ARG(ft->prepared && ft->step_on && ft->step_objective == NNRT_STEP_OBJECTIVE_ROBUST && ft->step_raw.ptr,
+	               "no prepared frame with step control on under NNRT_STEP_OBJECTIVE_ROBUST");
+	// the host buffer holds `count` floats: a mismatch with the prepared image is refused, not written past
+	NNRT_CHECK_ARG(count == static_cast<int64_t>(ft->key.H) * ft->key.W, "count differs from the prepared image's pixel count");
+	DeviceGuard guard(ft->device);
+	NNRT_HIP(hipStreamSynchronize(static_cast<hipStream_t>(stream)));
+	NNRT_HIP(hipStreamSynchronize(ft->work));
+	NNRT_HIP(hipMemcpy(h_out, ft->step_raw.ptr, sizeof(float) * static_cast<size_t>(count), hipMemcpyDeviceToHost));
 	return NNRT_OK;
 }
 

@@ -24,24 +24,11 @@ __global__ void k_step_reset(StepState* st, float lambda) {
 // released with it). Phase 2, the workgroup that arrives last (its thread 0 has acquired every other partial): thread 0
 // sums the partials in index order -- the same value whichever workgroup is last -- and takes the decision; the workgroup
 // then copies the current motion into the best motion where the decision says so, one lane per float.
-__global__ __launch_bounds__(STEP_COST_THREADS) void k_step_cost(StepCostArgs a) {
+// Everything after a thread's own sum is step_cost_finish, which k_step_cost and k_step_cost_robust share.
+__device__ __forceinline__ void step_cost_finish(const StepCostArgs& a, double sum) {
 	__shared__ double s_wave[STEP_COST_THREADS / 64];
 	__shared__ int s_last, s_copy;
 	const int t = static_cast<int>(threadIdx.x);
-	const int64_t base = static_cast<int64_t>(blockIdx.x) * a.chunk, items = a.P + a.E3;
-	double sum = 0.0;
-	for (int64_t k = 0; k < a.chunk; k += STEP_COST_THREADS) {
-		const int64_t i = base + k + t;
-		if (i < a.P) {
-			if (a.residual_mask[i]) {
-				const double r = static_cast<double>(a.residuals[i]);
-				sum += r * r;
-			}
-		} else if (i < items) {
-			const double r = static_cast<double>(a.edge_residuals[i - a.P]);
-			sum += r * r;
-		}
-	}
 #pragma unroll
 	for (int off = 32; off > 0; off >>= 1) sum += __shfl_down(sum, off, 64);
 	if ((t & 63) == 0) s_wave[t >> 6] = sum;
@@ -113,6 +100,119 @@ __global__ __launch_bounds__(STEP_COST_THREADS) void k_step_cost(StepCostArgs a)
 	}
 }
 
+__global__ __launch_bounds__(STEP_COST_THREADS) void k_step_cost(StepCostArgs a) {
+	const int t = static_cast<int>(threadIdx.x);
+	const int64_t base = static_cast<int64_t>(blockIdx.x) * a.chunk, items = a.P + a.E3;
+	double sum = 0.0;
+	for (int64_t k = 0; k < a.chunk; k += STEP_COST_THREADS) {
+		const int64_t i = base + k + t;
+		if (i < a.P) {
+			if (a.residual_mask[i]) {
+				const double r = static_cast<double>(a.residuals[i]);
+				sum += r * r;
+			}
+		} else if (i < items) {
+			const double r = static_cast<double>(a.edge_residuals[i - a.P]);
+			sum += r * r;
+		}
+	}
+	step_cost_finish(a, sum);
+}
+
+// The cost under NNRT_STEP_OBJECTIVE_ROBUST. Same structure as k_step_cost, one lane per item, the
+// items being the P pixels and then the E edges. The fused pixel launch leaves the scaled residual s r behind, from which
+// r cannot be recovered, so a masked pixel is resolved again from what the iteration has left on the device: the pixel's
+// face (pixel_face), the warped mesh and the reference point, by pass 1's operations in pass 1's order (pixel_body in
+// fitter_kernels.hip, from face_test to `dist`; -ffp-contract=off: the same IEEE operations give the same bits). r goes
+// to raw[p] (0 outside the mask). Per pixel, in fp64: r^2, or with the IRLS Tukey penalty (c^2 / 3)(1 - (1 - q^2)^3),
+// q = r / c, formed as (c^2 / 3) q^2 (3 + q^2 (q^2 - 3)) (no cancellation for small q), c^2 / 3 beyond the cutoff; NaN
+// where r is not finite. Per edge: m^2 = the fp64 sum of squares of its three stored entries, or with the IRLS Huber
+// penalty m^2 if m^2 <= delta^2 else 2 m^2 - delta^2 (the stored entries are sqrt(delta / n) e, so m^2 = delta n).
+__global__ __launch_bounds__(STEP_COST_THREADS) void k_step_cost_robust(StepCostRobustArgs ra) {
+	const StepCostArgs& a = ra.base;
+	const int t = static_cast<int>(threadIdx.x);
+	const int64_t base = static_cast<int64_t>(blockIdx.x) * a.chunk, items = a.P + ra.E;
+	const double c = static_cast<double>(ra.tukey_c), c23 = c * c / 3.0;
+	const double d2 = static_cast<double>(ra.huber_delta) * static_cast<double>(ra.huber_delta);
+	double sum = 0.0;
+	if (blockIdx.x == 0) {
+		// A node motion that is not finite (Rodrigues' 0 / 0 without the zero-rotation guard) unrenders the faces it moves,
+		// so their pixels leave the mask and no residual shows it: the cost of such a state is NaN, which rejects it
+		const int64_t count = static_cast<int64_t>(a.N) * STEP_BEST_STRIDE;
+		for (int64_t i = t; i < count; i += STEP_COST_THREADS) {
+			const int64_t n = i / STEP_BEST_STRIDE;
+			if (!(fabsf(a.state_in[n * NODE_STRIDE + 3 + (i - n * STEP_BEST_STRIDE)]) <= 3.402823466e+38f)) sum = NAN;
+		}
+	}
+	for (int64_t k = 0; k < a.chunk; k += STEP_COST_THREADS) {
+		const int64_t i = base + k + t;
+		if (i < a.P) {
+			float dist = 0.0f;
+			const bool mask = a.residual_mask[i] != 0;
+			const int32_t face = mask ? ra.pixel_face[i] : -1;
+			if (face >= 0 && face < ra.F) {
+				const int u = static_cast<int>(i % ra.W), v = static_cast<int>(i / ra.W);
+				RasterHit h{0.f, 0.f, 0.f, 0.f, 0.f};
+				f3 V3[3], N3[3];
+				FaceNdc fn;
+				const float px = pixel_ndc(u, ra.ax), py = pixel_ndc(v, ra.ay);
+				const int4 fi = ra.faces4[face];
+				const int vid[3] = {fi.x, fi.y, fi.z};
+#pragma unroll
+				for (int q = 0; q < 3; q++) {
+					const float4 wp = ra.wpos[vid[q]];
+					const float4 wn = ra.wnrm[vid[q]];
+					V3[q] = make3(wp.x, wp.y, wp.z);
+					N3[q] = make3(wn.x, wn.y, wn.z);
+					ra.ndc.ndc.project(V3[q].x, V3[q].y, V3[q].z, &fn.x[q], &fn.y[q]);
+					fn.z[q] = V3[q].z;
+				}
+				if (face_test<false>(fn, px, py, ra.blur, ra.perspective, false, true, h)) {
+					const float depth = h.depth;   // (the mask says that pass 1 found it valid)
+					f3 nl = make3(0.f, 0.f, 0.f);
+					float acc;
+					acc = 0.0f;
+					acc += h.b0 * N3[0].x;
+					acc += h.b1 * N3[1].x;
+					acc += h.b2 * N3[2].x;
+					nl.x = acc;
+					acc = 0.0f;
+					acc += h.b0 * N3[0].y;
+					acc += h.b1 * N3[1].y;
+					acc += h.b2 * N3[2].y;
+					nl.y = acc;
+					acc = 0.0f;
+					acc += h.b0 * N3[0].z;
+					acc += h.b1 * N3[1].z;
+					acc += h.b2 * N3[2].z;
+					nl.z = acc;
+					const f3 prast = make3((static_cast<float>(u) - ra.pix.cx) * depth / ra.pix.fx, (static_cast<float>(v) - ra.pix.cy) * depth / ra.pix.fy, depth);
+					const float4 qr = ra.ref_points[i];
+					const f3 d = sub3(prast, make3(qr.x, qr.y, qr.z));   // point map vector w_l - o_l
+					dist = dot3(nl, d);
+				}
+			}
+			ra.raw[i] = dist;
+			if (mask) {
+				const double r = static_cast<double>(dist);
+				double term = r * r;
+				if (ra.use_tukey) {
+					const double q = r / c, q2 = q * q;
+					term = fabsf(dist) <= ra.tukey_c ? c23 * (q2 * (3.0 + q2 * (q2 - 3.0))) : c23;
+				}
+				if (!(fabsf(dist) <= 3.402823466e+38f)) term = NAN;   // not a saturated finite cost: the decision rejects it
+				sum += term;
+			}
+		} else if (i < items) {
+			const float* e = a.edge_residuals + 3 * (i - a.P);
+			const double r0 = static_cast<double>(e[0]), r1 = static_cast<double>(e[1]), r2 = static_cast<double>(e[2]);
+			const double m2 = (r0 * r0 + r1 * r1) + r2 * r2;
+			sum += (!ra.use_huber || m2 <= d2) ? m2 : 2.0 * m2 - d2;
+		}
+	}
+	step_cost_finish(a, sum);
+}
+
 // One workgroup, after the update. A held iteration: motion <- best motion, and the error word goes back to what it was
 // at the decision. A stepping iteration: max |update| (an update that is not finite counts as +inf); below the threshold
 // the best motion is put back and the fit is done. Then the iteration's history record.
@@ -176,6 +276,12 @@ nnrt_status launch_step_reset(StepState* st, float lambda, hipStream_t stream) {
 
 nnrt_status launch_step_cost(const StepCostArgs& args, hipStream_t stream) {
 	k_step_cost<<<static_cast<unsigned>(args.blocks), STEP_COST_THREADS, 0, stream>>>(args);
+	NNRT_LAUNCH_CHECK();
+	return NNRT_OK;
+}
+
+nnrt_status launch_step_cost_robust(const StepCostRobustArgs& args, hipStream_t stream) {
+	k_step_cost_robust<<<static_cast<unsigned>(args.base.blocks), STEP_COST_THREADS, 0, stream>>>(args);
 	NNRT_LAUNCH_CHECK();
 	return NNRT_OK;
 }

@@ -1,7 +1,8 @@
 // The fitter's on-device step control (nnrt_fitter_set_step_control): the state machine's device
 // state and the two launches an iteration gains -- k_step_cost between the fused pixel launch and the solve (total cost,
 // accept / reject, the damping the solve reads) and k_step_select after the update (keep the step or put the best motion
-// back, the history record).
+// back, the history record). Under NNRT_STEP_OBJECTIVE_ROBUST k_step_cost_robust takes k_step_cost's
+// place: the same tail, the robust cost of the raw residuals it resolves again.
 #pragma once
 
 #include "common.hpp"
@@ -44,6 +45,28 @@ struct StepCostArgs {
 	float increase, decrease, lambda_min, lambda_max, relative_cost_tolerance;
 };
 
+// k_step_cost_robust (NNRT_STEP_OBJECTIVE_ROBUST): base.blocks / base.chunk are those of P + E items
+// (one per pixel, one per edge); base.residuals is not read
+struct StepCostRobustArgs {
+	StepCostArgs base;
+	int64_t F;                     // faces (pixel_face is checked against it)
+	int E;                         // ARAP edges
+	int W;
+	int perspective;
+	int use_tukey, use_huber;      // 1: the IRLS form of the penalty is on
+	float tukey_c, huber_delta;
+	float blur;
+	PixelAxis ax, ay;
+	NdcSetup ndc;
+	Camera pix;
+	const int32_t* pixel_face;     // [P] the face pass 1 resolved (-1: none)
+	const int4* faces4;            // [F]
+	const float4* wpos;            // [V] the warped mesh as pass 1 read it
+	const float4* wnrm;
+	const float4* ref_points;      // [P]
+	float* raw;                    // [P] out: the raw point-to-plane distance (0 outside the mask)
+};
+
 struct StepSelectArgs {
 	int N;
 	const float* updates;          // [6N]
@@ -64,6 +87,7 @@ inline int64_t step_cost_chunk(int64_t items, int blocks) { return ceil_div(ceil
 
 nnrt_status launch_step_reset(StepState* st, float lambda, hipStream_t stream);
 nnrt_status launch_step_cost(const StepCostArgs& args, hipStream_t stream);
+nnrt_status launch_step_cost_robust(const StepCostRobustArgs& args, hipStream_t stream);
 nnrt_status launch_step_select(const StepSelectArgs& args, hipStream_t stream);
 
 } // namespace nnrt

@@ -43,7 +43,8 @@ cutoff c contributes iff |r| <= c, and its residual and Jacobian row are scaled 
 weight; an ARAP edge's residual 3-vector r and its Jacobian terms are scaled by s = 1 if |r| <= delta else
 sqrt(delta / |r|) (Huber's weight min(1, delta / |r|)). Hand-held sequences (DeepDeform's are) also want
 `rigid_alignment=True`, and every real sequence wants `coupled_data_term=True`: the reference's block-diagonal data
-Hessian overshoots from the second iteration on, the coupled step converges. `guard_zero_rotation=True` keeps the rotation of a node whose
+Hessian overshoots from the second iteration on, the coupled step converges. Add `step_control=StepControl(...)` with `step_objective=StepObjective.ROBUST`
+ so that a frame's fit cannot end at a higher robust cost than it began. `guard_zero_rotation=True` keeps the rotation of a node whose
 rotation update is exactly zero (every node without pixels), where the reference's Rodrigues formula gives NaN (A7).
 The defaults (`_default_alignment`) keep their values.
 """
@@ -65,7 +66,7 @@ from ..data.frame import FrameSequenceDataset
 from ..nnrt import geometry as G
 from ..nnrt import image_proc
 from ..nnrt import rendering
-from ..nnrt.alignment import NDC_CONSISTENT, DataCoupling, StepControl, align_rigid_point_to_plane
+from ..nnrt.alignment import NDC_CONSISTENT, DataCoupling, StepControl, StepObjective, align_rigid_point_to_plane
 from ..warp_field.graph_warp_field import build_graph_nodes_from_depth_image, extend_warp_field, sample_graph_nodes_from_mesh
 
 
@@ -168,15 +169,19 @@ class FusionParameters:
     # Hessian; real sequences should turn it on. Overrides alignment.data_coupling when set.
     coupled_data_term: bool = False
     # on-device step control of the non-rigid fit (StepControl): a step is kept only if the cost fell, so a
-    # frame's fit cannot end worse than it began. SQUARE penalties only (this loop's default). Overrides
-    # alignment.step_control when set.
+    # frame's fit cannot end worse than it began. Overrides alignment.step_control when set.
     step_control: Optional[StepControl] = None
+    # the cost step control compares (StepObjective): SQUARE allows SQUARE penalties only (this loop's
+    # default); ROBUST goes with the TUKEY / HUBER penalties in PenaltyForm.IRLS. Overrides alignment.step_objective when set.
+    step_objective: Optional[StepObjective] = None
 
 
 def alignment_parameters(p: FusionParameters) -> RenderingAlignmentParameters:
     """The optimizer's parameters for these fusion parameters: p.alignment, in DataCoupling.COUPLED mode when
-    coupled_data_term is set and with step_control where that is set."""
+    coupled_data_term is set and with step_control / step_objective where those are set."""
     a = dataclasses.replace(p.alignment, data_coupling=DataCoupling.COUPLED) if p.coupled_data_term else p.alignment
+    if p.step_objective is not None:
+        a = dataclasses.replace(a, step_objective=p.step_objective)
     return dataclasses.replace(a, step_control=p.step_control) if p.step_control is not None else a
 
 

@@ -53,13 +53,23 @@ class StepDecision(enum.IntEnum):
     SMALL_UPDATE = 6    # a step whose max |update| is below minimal_update_threshold: best state put back, done
 
 
+class StepObjective(enum.IntEnum):
+    """The cost step control compares (include/nnrt_mi355x.h NNRT_STEP_OBJECTIVE_*). SQUARE (default):
+    the sum of squared residuals, which limits step control to SQUARE penalties. ROBUST: the objective PenaltyForm.IRLS
+    minimises (Tukey's biweight over the raw pixel residuals, Huber over the edges), so that step control and IRLS run
+    together; one more pass over the pixels per iteration. Real sequences should use ROBUST with IRLS."""
+    SQUARE = 0
+    ROBUST = 1
+
+
 STEP_DONE_DECISIONS = (StepDecision.CONVERGED, StepDecision.REJECT_FINAL, StepDecision.SMALL_UPDATE)
 
 
 @dataclasses.dataclass(frozen=True)
 class StepControl:
     """Settings of the fitter's on-device step control (nnrt_step_control): keep a Gauss-Newton step
-    only if the cost fell, damp harder if not, stop when nothing moves. IterationMode.ALL and SQUARE penalties only.
+    only if the cost fell, damp harder if not, stop when nothing moves. IterationMode.ALL only; SQUARE penalties only
+    under StepObjective.SQUARE (the default), PenaltyForm.IRLS too under StepObjective.ROBUST.
     initial_lambda 0 starts from preconditioning_dampening_factor. poll_interval k > 0: fit_to_image synchronises every k
     iterations and returns once the device reports done; 0: never synchronises."""
     initial_lambda: float = 0.0
@@ -109,8 +119,8 @@ class DeformableMeshToImageFitter:
                  use_perspective_correction: bool = True, max_depth: float = 10.0, use_tukey_penalty_for_data_term: bool = False,
                  tukey_penalty_cutoff_cm: float = 0.01, preconditioning_dampening_factor: float = 0.0, arap_term_weight: float = 200.0,
                  use_huber_penalty_for_arap_term: bool = False, huber_penalty_constant: float = 1e-4, device: int | None = None,
-                 use_hip_graph: int = 1, ndc_convention: int = 0, penalty_form: PenaltyForm = PenaltyForm.REFERENCE,
-                 guard_zero_rotation: bool = False):
+                 use_hip_graph: int = 1, ndc_convention: int = 0, step_objective: StepObjective = StepObjective.SQUARE,
+                 penalty_form: PenaltyForm = PenaltyForm.REFERENCE, guard_zero_rotation: bool = False):
         device = N.current_device() if device is None else int(device)
         p = N.FitterParams()
         N.lib().nnrt_fitter_default_params(ctypes.byref(p))
@@ -138,6 +148,7 @@ class DeformableMeshToImageFitter:
         self.modes = modes
         self._frame = None
         self.set_robust_options(penalty_form, guard_zero_rotation)
+        self.set_step_objective(step_objective)
 
     def __del__(self):
         h = getattr(self, "_h", None)
@@ -282,7 +293,8 @@ class DeformableMeshToImageFitter:
     def set_step_control(self, step_control: StepControl | None):
         """Turn the on-device step control on with these settings, or off with None (the default: every output as
         without it). A change drops the cached graphs and invalidates the prepared frame: call prepare() again.
-        Out-of-range settings, PenaltyForm.IRLS, or a mode list holding another mode than ALL raise."""
+        Out-of-range settings, PenaltyForm.IRLS under StepObjective.SQUARE, or a mode list holding another mode than ALL
+        raise."""
         if step_control is None:
             N.check(N.lib().nnrt_fitter_set_step_control(self._h, None))
             return
@@ -298,6 +310,28 @@ class DeformableMeshToImageFitter:
         if not on.value:
             return None
         return StepControl(s.initial_lambda, s.increase, s.decrease, s.lambda_min, s.lambda_max, s.relative_cost_tolerance, s.poll_interval)
+
+    def set_step_objective(self, step_objective):
+        """StepObjective.SQUARE (default) or StepObjective.ROBUST: the cost step control compares. Under ROBUST,
+        PenaltyForm.IRLS and step control are accepted together, in either order. ROBUST with PenaltyForm.REFERENCE and a
+        penalty enabled raises, and so does SQUARE while step control is on with PenaltyForm.IRLS. A change drops the
+        cached graphs and, with step control on, invalidates the prepared frame: call prepare() again."""
+        N.check(N.lib().nnrt_fitter_set_step_objective(self._h, int(step_objective)))
+
+    @property
+    def step_objective(self) -> StepObjective:
+        v = ctypes.c_int32()
+        N.check(N.lib().nnrt_fitter_get_step_objective(self._h, ctypes.byref(v)))
+        return StepObjective(v.value)
+
+    def raw_residuals(self, stream=None) -> np.ndarray:
+        """[H * W] float32: the raw point-to-plane residual r of every pixel as the last iteration's cost launch resolved
+        it (0 outside the residual mask), before the IRLS scaling diagnostics()['residuals'] carries. Step control on
+        under StepObjective.ROBUST only. Synchronizes."""
+        _, _, _, _, _, _, _, H, W = self._frame
+        out = np.empty(H * W, np.float32)
+        N.check(N.lib().nnrt_fitter_get_raw_residuals(self._h, N.ptr(out), H * W, N.stream_ptr(stream)))
+        return out
 
     def step_history(self, stream=None) -> list:
         """The StepRecords of the iterations since the fit started (iterate() from iteration 0), oldest first: at most

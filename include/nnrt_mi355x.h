@@ -256,9 +256,11 @@ nnrt_status nnrt_fitter_get_coupled_system(nnrt_fitter* fitter, float* h_diag, i
  * done (NNRT_STEP_SMALL_UPDATE): the one mode in which that parameter has an effect (A14). Every iteration appends one
  * nnrt_step_record to a ring of NNRT_STEP_HISTORY_CAPACITY records. nnrt_fitter_iterate with first_iteration == 0
  * restarts the state machine (lambda = initial_lambda, empty history).
- * Limits: IterationMode ALL only, and SQUARE penalties only -- under NNRT_PENALTY_IRLS the residual buffer holds the
- * scaled residual s r, from which the robust objective cannot be evaluated. Enabling step control while
- * NNRT_PENALTY_IRLS is set, or setting NNRT_PENALTY_IRLS while step control is on, returns NNRT_ERROR_ARGUMENT; so does
+ * Limits: IterationMode ALL only, and SQUARE penalties only under NNRT_STEP_OBJECTIVE_SQUARE (the default step objective;
+ * nnrt_fitter_set_step_objective below lifts this) -- under NNRT_PENALTY_IRLS the residual buffer holds the scaled
+ * residual s r, from which the robust objective cannot be evaluated. Under NNRT_STEP_OBJECTIVE_SQUARE, enabling step
+ * control while NNRT_PENALTY_IRLS is set, or
+ * setting NNRT_PENALTY_IRLS while step control is on, returns NNRT_ERROR_ARGUMENT; so does
  * a mode list holding another mode than ALL, and nnrt_fitter_iterate_from_identity / _from_snapshot (every iteration a
  * restart) while it is on. An ARAP edge the fixed-coverage weight lookup refuses (quirk A3, error bit 2 of
  * nnrt_fitter_check) contributes 0 to the cost; that fit is reported as failed anyway.
@@ -301,6 +303,36 @@ nnrt_status nnrt_fitter_get_step_control(const nnrt_fitter* fitter, int32_t* ena
  * NNRT_ERROR_ARGUMENT, nothing written, as nnrt_fitter_get_warped_mesh refuses a wrong vertex count; *out_count is still
  * set, so records == NULL with capacity 0 asks for the count. 0 records with step control off. */
 nnrt_status nnrt_fitter_get_step_history(nnrt_fitter* fitter, nnrt_step_record* records, int64_t capacity, int64_t* out_count, void* stream);
+/* The cost step control compares. NNRT_STEP_OBJECTIVE_SQUARE (default): the sum of squares above,
+ * with every refusal above. NNRT_STEP_OBJECTIVE_ROBUST: the objective the IRLS penalties minimise, in fp64, so that step
+ * control and NNRT_PENALTY_IRLS are accepted together, set in either order:
+ *   data term   every pixel of the residual mask, r = n_l . (w_l - o_l) its raw float residual before any scaling: r^2
+ *               without the Tukey penalty; with it (c = tukey_penalty_cutoff_cm, q = r / c)
+ *               (c^2 / 3) (1 - (1 - q^2)^3) if fabsf(r) <= c, else c^2 / 3 -- twice the biweight's rho, whose IRLS weight
+ *               is the (1 - q^2)^2 of nnrt_fitter_set_robust_options; it tends to r^2 as c grows. A masked-in pixel whose
+ *               r is not finite adds NaN (a reject), not the saturated c^2 / 3.
+ *   state       a node translation or rotation entry of the evaluated state that is not finite makes the cost NaN: the
+ *               faces such a node moves are not rendered, so their pixels leave the mask and no residual would show it.
+ *   ARAP term   every edge, m^2 = the fp64 sum of squares of its three stored residual entries: m^2 without the Huber
+ *               penalty; with it (delta = huber_penalty_constant) m^2 if m^2 <= delta^2, else 2 m^2 - delta^2 (the stored
+ *               entries carry the factor sqrt(delta / n), so this is 2 delta n - delta^2, twice Huber's rho). A refused
+ *               edge (A3) adds 0.
+ * The fused pixel launch keeps only s r, so one more launch per iteration (in k_step_cost's place, same partial sums,
+ * ticket and decision) resolves every masked pixel again, bit for bit as that launch did, and leaves r in a [P] buffer:
+ * nnrt_fitter_get_raw_residuals. With both penalties off and no hierarchy the costs equal NNRT_STEP_OBJECTIVE_SQUARE's
+ * bit for bit. Refused with NNRT_ERROR_ARGUMENT: any other value; ROBUST while the penalty form is NNRT_PENALTY_REFERENCE
+ * and a penalty is enabled (the reference's branches A8 / A9 have no objective; nnrt_fitter_set_robust_options refuses the
+ * reverse order); SQUARE while step control is on and NNRT_PENALTY_IRLS is set. A change drops the fitter's cached graphs
+ * and, with step control on, invalidates the prepared frame (prepare() again: the state machine restarts). With the
+ * objective at SQUARE, or step control off, the launch plan, the graph count and every output are what they were. */
+#define NNRT_STEP_OBJECTIVE_SQUARE 0
+#define NNRT_STEP_OBJECTIVE_ROBUST 1
+nnrt_status nnrt_fitter_set_step_objective(nnrt_fitter* fitter, int32_t objective);
+nnrt_status nnrt_fitter_get_step_objective(const nnrt_fitter* fitter, int32_t* objective);
+/* The raw residuals r of the last iteration under step control with NNRT_STEP_OBJECTIVE_ROBUST (0 outside the residual
+ * mask; zeros before the first iteration), h_out [count] floats on the host. count must equal the prepared image's H * W;
+ * without such a prepared frame NNRT_ERROR_ARGUMENT. Synchronizes `stream`. */
+nnrt_status nnrt_fitter_get_raw_residuals(nnrt_fitter* fitter, float* h_out, int64_t count, void* stream);
 /* Anchor the canonical mesh along a motion graph's edges instead of by Euclidean distance (the reference's
  * AnchorComputationMethod::SHORTEST_PATH, PlanarGraphWarpField::PrecomputeAnchorsAndWeights; apps/fusion/pipeline.py:577-582):
  * d_edges [node_count, graph_degree] int32 rows in the warp field's virtual node order (entry < 0 = empty) are copied
