@@ -279,27 +279,8 @@ __global__ void k_faces_to_int4(const int64_t* __restrict__ faces, int64_t F, in
 // stages of one iteration (nnrt_fitter_time_kernels launches subsets of them)
 enum : unsigned { STAGE_WARP = 1u, STAGE_RASTER = 2u, STAGE_PIXEL = 4u, STAGE_SOLVE = 8u, STAGE_ALL = 15u };
 
-nnrt_status enqueue_iteration(nnrt_fitter* ft, const nnrt_warp_field* wf, int mode, hipStream_t s, hipEvent_t* marks = nullptr,
-                              bool from_identity = false, const float* state_in = nullptr, unsigned stages = STAGE_ALL) {
-	if (!state_in) state_in = wf->state.ptr;
-	nnrt_status st;
-	auto mark = [&](int i) -> nnrt_status {
-		if (marks) NNRT_HIP(hipEventRecord(marks[i], s));
-		return NNRT_OK;
-	};
-	if ((st = mark(0))) return st;
-	const bool with_jacobians = NNRT_GATHER_ROWS != 0;
-	if ((stages & STAGE_WARP) &&
-	    (st = launch_warp_mesh(ft->mesh_p.ptr, ft->mesh_n.ptr, ft->key.V, state_in, ft->anchors.ptr, ft->weights.ptr, ft->key.K, ft->key.extr,
-	                           ft->wpos.ptr, ft->wnrm.ptr, with_jacobians ? ft->jrows.ptr : nullptr, ft->key.launch.warp_vertex != 0, s, from_identity,
-	                           ft->key.launch.anchors16 ? ft->anchors16.ptr : nullptr)))
-		return st;
-	if ((st = mark(1))) return st;
-	const RasterOptions ro = make_raster_options(ft->key.H, ft->key.W, 0.5f / (static_cast<float>(fminf(ft->key.H, ft->key.W)) / 2.0f), ft->p.use_perspective_correction, 0, 1);
-	if ((stages & STAGE_RASTER) && (st = launch_raster_scatter_mesh(ft->wpos.ptr, ft->faces4.ptr, ft->key.F, ft->key.ndc, 0.0f, 10.0f, ro, ft->keys.ptr,
-	                                                                ft->key.launch.raster_dense != 0, s)))
-		return st;
-	if ((st = mark(2))) return st;
+// the fused pixel launch's arguments (the pair launch and the robust step cost take theirs from them)
+FitPixelArgs fit_pixel_args(const nnrt_fitter* ft, const nnrt_warp_field* wf, const RasterOptions& ro, const float* state_in, bool from_identity) {
 	FitPixelArgs fa{};
 	fa.H = ft->key.H;
 	fa.W = ft->key.W;
@@ -364,6 +345,93 @@ nnrt_status enqueue_iteration(nnrt_fitter* ft, const nnrt_warp_field* wf, int mo
 		aa.error_flag = ft->error_flag.ptr;
 		fa.arap_blocks = fit_pixels_arap_blocks(ft->key.E);
 	}
+	return fa;
+}
+
+// k_step_cost's arguments: one item per pixel and per ARAP edge residual entry
+StepCostArgs step_cost_args(const nnrt_fitter* ft, const float* state_in) {
+	StepCostArgs ca{};
+	ca.P = static_cast<int64_t>(ft->key.H) * ft->key.W;
+	ca.E3 = 3 * static_cast<int64_t>(ft->key.E);
+	ca.N = ft->key.N;
+	ca.blocks = step_cost_blocks(ca.P + ca.E3);
+	ca.chunk = step_cost_chunk(ca.P + ca.E3, ca.blocks);
+	ca.residuals = ft->residuals.ptr;
+	ca.residual_mask = ft->residual_mask.ptr;
+	ca.edge_residuals = ft->edge_residuals.ptr;
+	ca.state_in = state_in;
+	ca.best = ft->step_best.ptr;
+	ca.partials = ft->step_partials.ptr;
+	ca.st = ft->step_state.ptr;
+	ca.error_flag = ft->error_flag.ptr;
+	ca.increase = ft->step.increase;
+	ca.decrease = ft->step.decrease;
+	ca.lambda_min = ft->step.lambda_min;
+	ca.lambda_max = ft->step.lambda_max;
+	ca.relative_cost_tolerance = ft->step.relative_cost_tolerance;
+	return ca;
+}
+
+// k_step_cost_robust's, the robust cost of the raw residuals: the kernel resolves each masked pixel again from the buffers
+// the warp, the scatter and the fused launch left (nothing between that launch and this one writes them: the pair launch
+// only reads), one item per pixel and per edge
+StepCostRobustArgs step_cost_robust_args(const nnrt_fitter* ft, const FitPixelArgs& fa, StepCostArgs ca) {
+	StepCostRobustArgs ra{};
+	ca.blocks = step_cost_blocks(ca.P + ft->key.E);
+	ca.chunk = step_cost_chunk(ca.P + ft->key.E, ca.blocks);
+	ra.base = ca;
+	ra.view = pixel_resolve_view(fa);
+	ra.F = ft->key.F;
+	ra.E = ft->key.E;
+	ra.W = ft->key.W;
+	ra.use_tukey = fa.use_tukey == PENALTY_IRLS;
+	ra.use_huber = ft->key.E > 0 && fa.arap.use_huber == PENALTY_IRLS;
+	ra.tukey_c = fa.tukey_c;
+	ra.huber_delta = ft->p.huber_penalty_constant;
+	ra.pixel_face = fa.pixel_face;
+	ra.raw = ft->step_raw.ptr;
+	return ra;
+}
+
+// the block-diagonal solve + update's, with the damping as a launch argument or a device word
+template <class Lm>
+SolveArgsT<Lm> solve_args(const nnrt_fitter* ft, const nnrt_warp_field* wf, const float* state_in, Lm lm) {
+	SolveArgsT<Lm> sa{};
+	sa.N = ft->key.N;
+	sa.lm = lm;
+	sa.acc = ft->acc.ptr;
+	sa.state_in = state_in;
+	sa.node_state = wf->state.ptr;
+	sa.updates_out = ft->updates.ptr;
+	sa.gradient_out = ft->gradient.ptr;
+	sa.hessian_out = ft->hessian.ptr;
+	sa.error_flag = ft->error_flag.ptr;
+	sa.guard_zero_rotation = ft->guard_zero_rotation;
+	return sa;
+}
+
+nnrt_status enqueue_iteration(nnrt_fitter* ft, const nnrt_warp_field* wf, int mode, hipStream_t s, hipEvent_t* marks = nullptr,
+                              bool from_identity = false, const float* state_in = nullptr, unsigned stages = STAGE_ALL) {
+	if (!state_in) state_in = wf->state.ptr;
+	nnrt_status st;
+	auto mark = [&](int i) -> nnrt_status {
+		if (marks) NNRT_HIP(hipEventRecord(marks[i], s));
+		return NNRT_OK;
+	};
+	if ((st = mark(0))) return st;
+	const bool with_jacobians = NNRT_GATHER_ROWS != 0;
+	if ((stages & STAGE_WARP) &&
+	    (st = launch_warp_mesh(ft->mesh_p.ptr, ft->mesh_n.ptr, ft->key.V, state_in, ft->anchors.ptr, ft->weights.ptr, ft->key.K, ft->key.extr,
+	                           ft->wpos.ptr, ft->wnrm.ptr, with_jacobians ? ft->jrows.ptr : nullptr, ft->key.launch.warp_vertex != 0, s, from_identity,
+	                           ft->key.launch.anchors16 ? ft->anchors16.ptr : nullptr)))
+		return st;
+	if ((st = mark(1))) return st;
+	const RasterOptions ro = make_raster_options(ft->key.H, ft->key.W, 0.5f / (static_cast<float>(fminf(ft->key.H, ft->key.W)) / 2.0f), ft->p.use_perspective_correction, 0, 1);
+	if ((stages & STAGE_RASTER) && (st = launch_raster_scatter_mesh(ft->wpos.ptr, ft->faces4.ptr, ft->key.F, ft->key.ndc, 0.0f, 10.0f, ro, ft->keys.ptr,
+	                                                                ft->key.launch.raster_dense != 0, s)))
+		return st;
+	if ((st = mark(2))) return st;
+	const FitPixelArgs fa = fit_pixel_args(ft, wf, ro, state_in, from_identity);
 	if ((stages & STAGE_PIXEL) && (st = launch_fit_pixels(mode, fa, s, marks ? marks[3] : nullptr))) return st;
 	const bool coupled = ft->key.coupled != 0;
 	if (coupled && (stages & STAGE_PIXEL) && ft->ps.M > 0) {   // the off-diagonal data blocks: a second launch on the same stream
@@ -378,53 +446,9 @@ nnrt_status enqueue_iteration(nnrt_fitter* ft, const nnrt_warp_field* wf, int mo
 	const bool step = ft->step_on;
 	const float* lm_device = step ? &ft->step_state.ptr->lambda : nullptr;
 	if (step) {
-		StepCostArgs ca{};
-		ca.P = static_cast<int64_t>(ft->key.H) * ft->key.W;
-		ca.E3 = 3 * static_cast<int64_t>(ft->key.E);
-		ca.N = ft->key.N;
-		ca.blocks = step_cost_blocks(ca.P + ca.E3);
-		ca.chunk = step_cost_chunk(ca.P + ca.E3, ca.blocks);
-		ca.residuals = ft->residuals.ptr;
-		ca.residual_mask = ft->residual_mask.ptr;
-		ca.edge_residuals = ft->edge_residuals.ptr;
-		ca.state_in = state_in;
-		ca.best = ft->step_best.ptr;
-		ca.partials = ft->step_partials.ptr;
-		ca.st = ft->step_state.ptr;
-		ca.error_flag = ft->error_flag.ptr;
-		ca.increase = ft->step.increase;
-		ca.decrease = ft->step.decrease;
-		ca.lambda_min = ft->step.lambda_min;
-		ca.lambda_max = ft->step.lambda_max;
-		ca.relative_cost_tolerance = ft->step.relative_cost_tolerance;
+		const StepCostArgs ca = step_cost_args(ft, state_in);
 		if (ft->step_objective == NNRT_STEP_OBJECTIVE_ROBUST) {
-			// the robust cost of the raw residuals: the kernel resolves each masked pixel again from the buffers the warp, the
-			// scatter and the fused launch left (nothing between that launch and this one writes them: the pair launch
-			// above only reads), one item per pixel and per edge
-			StepCostRobustArgs ra{};
-			ca.blocks = step_cost_blocks(ca.P + ft->key.E);
-			ca.chunk = step_cost_chunk(ca.P + ft->key.E, ca.blocks);
-			ra.base = ca;
-			ra.F = ft->key.F;
-			ra.E = ft->key.E;
-			ra.W = ft->key.W;
-			ra.perspective = fa.perspective;
-			ra.use_tukey = fa.use_tukey == PENALTY_IRLS;
-			ra.use_huber = ft->key.E > 0 && fa.arap.use_huber == PENALTY_IRLS;
-			ra.tukey_c = fa.tukey_c;
-			ra.huber_delta = ft->p.huber_penalty_constant;
-			ra.blur = fa.blur;
-			ra.ax = fa.ax;
-			ra.ay = fa.ay;
-			ra.ndc = fa.ndc;
-			ra.pix = fa.pix;
-			ra.pixel_face = fa.pixel_face;
-			ra.faces4 = fa.faces4;
-			ra.wpos = fa.wpos;
-			ra.wnrm = fa.wnrm;
-			ra.ref_points = fa.ref_points;
-			ra.raw = ft->step_raw.ptr;
-			if ((st = launch_step_cost_robust(ra, s))) return st;
+			if ((st = launch_step_cost_robust(step_cost_robust_args(ft, fa, ca), s))) return st;
 		} else if ((st = launch_step_cost(ca, s))) {
 			return st;
 		}
@@ -448,31 +472,9 @@ nnrt_status enqueue_iteration(nnrt_fitter* ft, const nnrt_warp_field* wf, int mo
 		                                     ft->updates.ptr, ft->gradient.ptr, ft->hessian.ptr, ft->error_flag.ptr, s, state_in, lm_device)))
 			return st;
 	} else if (step) {
-		SolveArgsDeviceLm sa{};
-		sa.N = ft->key.N;
-		sa.lm = lm_device;
-		sa.acc = ft->acc.ptr;
-		sa.state_in = state_in;
-		sa.node_state = wf->state.ptr;
-		sa.updates_out = ft->updates.ptr;
-		sa.gradient_out = ft->gradient.ptr;
-		sa.hessian_out = ft->hessian.ptr;
-		sa.error_flag = ft->error_flag.ptr;
-		sa.guard_zero_rotation = ft->guard_zero_rotation;
-		if ((st = launch_solve_update_device_lm(sa, s))) return st;
+		if ((st = launch_solve_update_device_lm(solve_args(ft, wf, state_in, lm_device), s))) return st;
 	} else {
-		SolveArgs sa{};
-		sa.N = ft->key.N;
-		sa.lm = ft->p.preconditioning_dampening_factor;
-		sa.acc = ft->acc.ptr;
-		sa.state_in = state_in;
-		sa.node_state = wf->state.ptr;
-		sa.updates_out = ft->updates.ptr;
-		sa.gradient_out = ft->gradient.ptr;
-		sa.hessian_out = ft->hessian.ptr;
-		sa.error_flag = ft->error_flag.ptr;
-		sa.guard_zero_rotation = ft->guard_zero_rotation;
-		if ((st = launch_solve_update(mode, sa, s, from_identity))) return st;
+		if ((st = launch_solve_update(mode, solve_args(ft, wf, state_in, ft->p.preconditioning_dampening_factor), s, from_identity))) return st;
 	}
 	if (step) {   // keep the step, or put the best motion back; the history record
 		StepSelectArgs sa{};

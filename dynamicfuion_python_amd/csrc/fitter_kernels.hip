@@ -12,8 +12,11 @@
 //    into fp64 accumulator rows.
 // Products are rounded to float exactly as the reference forms them and summed in double, so the data term equals the
 // exactly-summed reference data term (see DESIGN.md "Numerics"); no node-list cap.
+// The per-pixel and per-association arithmetic itself (resolve, penalty, record, pixel-node row) is in pixel_terms.hpp,
+// shared with the pair launch below and the robust step cost (step_control.hip).
 #include "coupled.hpp"
 #include "fitter_kernels.hpp"
+#include "pixel_terms.hpp"
 
 
 namespace nnrt {
@@ -88,249 +91,32 @@ __device__ __forceinline__ void pixel_body(const FitPixelArgs& a, float* dn, int
 	const bool in_image = tile < tiles && u < a.W && v < a.H;
 	const int64_t p = static_cast<int64_t>(v) * a.W + u;
 
-	int vid[3] = {0, 0, 0};
-	float rn[3] = {0.f, 0.f, 0.f}, rho[3] = {0.f, 0.f, 0.f};
-
 	if (in_image) {
+		const PixelResolveView w = pixel_resolve_view(a);
 		const uint64_t key = a.keys[p];
 		int32_t face = -1;
-		RasterHit h{0.f, 0.f, 0.f, 0.f, 0.f};
-		f3 V3[3], N3[3];
-		FaceNdc fn;
-		const float px = pixel_ndc(u, a.ax), py = pixel_ndc(v, a.ay);
+		PixelResolve r = resolve_pixel(w, u, v);
 		if (key != EMPTY_KEY) {
 			face = static_cast<int32_t>(key & 0xffffffffu);
-			const int4 fi = a.faces4[face];
-			out_nodes = fi.w;   // the face's distinct anchor nodes (k_face_node_table)
-			vid[0] = fi.x;
-			vid[1] = fi.y;
-			vid[2] = fi.z;
-#pragma unroll
-			for (int i = 0; i < 3; i++) {
-				const float4 wp = a.wpos[vid[i]];
-				const float4 wn = a.wnrm[vid[i]];
-				V3[i] = make3(wp.x, wp.y, wp.z);
-				N3[i] = make3(wn.x, wn.y, wn.z);
-				a.ndc.ndc.project(V3[i].x, V3[i].y, V3[i].z, &fn.x[i], &fn.y[i]);
-				fn.z[i] = V3[i].z;
-			}
-			// the scatter accepted this face for this pixel after the full test; re-resolving needs no distance test
-			if (!face_test<false>(fn, px, py, a.blur, a.perspective, false, true, h)) face = -1;
+			if (!resolve_face(w, face, r)) face = -1;
+			out_nodes = r.nodes;
 		}
 		// ---- ComputeDepthResiduals (:331-390) ----
-		const float depth = face >= 0 ? h.depth : -1.f;
+		const float depth = face >= 0 ? r.h.depth : -1.f;
 		const bool rendered_valid = depth > 0 && depth < a.max_depth;
-		f3 nl = make3(0.f, 0.f, 0.f), prast = make3(0.f, 0.f, 0.f);
-		if (face >= 0) {
-			float acc;
-			acc = 0.0f;
-			acc += h.b0 * N3[0].x;
-			acc += h.b1 * N3[1].x;
-			acc += h.b2 * N3[2].x;
-			nl.x = acc;
-			acc = 0.0f;
-			acc += h.b0 * N3[0].y;
-			acc += h.b1 * N3[1].y;
-			acc += h.b2 * N3[2].y;
-			nl.y = acc;
-			acc = 0.0f;
-			acc += h.b0 * N3[0].z;
-			acc += h.b1 * N3[1].z;
-			acc += h.b2 * N3[2].z;
-			nl.z = acc;
-		}
-		if (rendered_valid) {
-			prast = make3((static_cast<float>(u) - a.pix.cx) * depth / a.pix.fx, (static_cast<float>(v) - a.pix.cy) * depth / a.pix.fy, depth);
-		}
-		const float4 qr = a.ref_points[p];
-		const bool ref_valid = qr.w != 0.f;
-		const f3 q = make3(qr.x, qr.y, qr.z);
-		const bool mask = ref_valid && rendered_valid;
-		const f3 d = sub3(prast, q);   // point map vector w_l - o_l
-		float dist = dot3(nl, d);
-		if (!mask) dist = 0.0f;
-		float residual = dist;
-		bool contributes = mask;
-		f3 dr_dwl = nl, dr_dnl = d;
-		if (a.use_tukey == PENALTY_IRLS) {
-			// iteratively re-weighted least squares with Tukey's biweight (1 - q^2)^2, q = r / c: residual and Jacobian
-			// row are both scaled by its square root s, so pass 2 sums s^2 J^T J and (s J)^T (s r); a pixel beyond the
-			// cutoff (or with a NaN residual) carries no weight
-			const float c = a.tukey_c;
-			contributes = mask && fabsf(dist) <= c;
-			const float qq = dist / c;
-			const float s = 1.f - qq * qq;
-			residual = contributes ? s * dist : 0.f;
-			dr_dwl = make3(s * nl.x, s * nl.y, s * nl.z);
-			dr_dnl = make3(s * d.x, s * d.y, s * d.z);
-		} else if (a.use_tukey) {
-			const float c = a.tukey_c;
-			const float c6 = (c * c / 6.f);
-			const float qq = dist / c;
-			const float left = 1.f - (qq * qq);
-			residual = c6 * (1.f - left * left * left);
-			if (dist <= c) residual = c6;   // (:384-385 as written: A8)
-		}
-		a.residuals[p] = residual;
+		resolve_distance(w, u, v, p, face >= 0, rendered_valid, r);
+		const bool mask = r.ref_valid && rendered_valid;
+		const float dist = mask ? r.dist : 0.0f;
+		const PixelPenalty pen = pixel_penalty(a.use_tukey, a.tukey_c, mask, r.nl, r.d, dist);
+		a.residuals[p] = pen.residual;
 		a.residual_mask[p] = mask ? 1 : 0;
 		a.pixel_face[p] = face;
-
-		if (contributes && a.use_tukey == PENALTY_REFERENCE) {
-			const float r = dot3(nl, d);
-			if (fabsf(r) > a.tukey_c) contributes = false;
-			const float qq = r / a.tukey_c;
-			float psi = 1 - qq * qq;
-			psi = r * psi * psi;
-			dr_dnl = make3(psi * d.x, psi * d.y, psi * d.z);
-			dr_dwl = make3(psi * nl.x, psi * nl.y, psi * nl.z);
-		}
 		a.keys[p] = EMPTY_KEY;   // ready for the next iteration's scatter (pass 2 takes the face from registers)
-		out_face = contributes ? face : -1;
-		out_vid[0] = vid[0];
-		out_vid[1] = vid[1];
-		out_vid[2] = vid[2];
-		if (contributes) {
-			// ---- rasterized surface Jacobians (RasterizedSurfaceJacobiansImpl.h:114-200) ----
-			rho[0] = h.b0;
-			rho[1] = h.b1;
-			rho[2] = h.b2;
-			float A, sa[3], drho[3] = {0.f, 0.f, 0.f};
-			A = spa_cw(fn.x[0], fn.y[0], fn.x[1], fn.y[1], fn.x[2], fn.y[2]) + K_EPSILON;
-			if (a.perspective) {
-				sa[0] = spa_cw(px, py, fn.x[1], fn.y[1], fn.x[2], fn.y[2]);
-				sa[1] = spa_cw(px, py, fn.x[2], fn.y[2], fn.x[0], fn.y[0]);
-				sa[2] = spa_cw(px, py, fn.x[0], fn.y[0], fn.x[1], fn.y[1]);
-				const float inv_A = rcp_rn_normal(A);   // consumed by div_rn only, which ignores it outside (1e-30, 1e30)
-#pragma unroll
-				for (int i = 0; i < 3; i++) drho[i] = div_rn(sa[i], A, inv_A);
-			} else {
-#pragma unroll
-				for (int i = 0; i < 3; i++) sa[i] = rho[i] * A;
-			}
-			// d rho / d ndc (BarycentricCoordinateJacobians.h:85-181)
-			const float den = A * A + K_EPSILON;
-			const float dA[3][2] = {{fn.y[1] - fn.y[2], fn.x[2] - fn.x[1]}, {fn.y[2] - fn.y[0], fn.x[0] - fn.x[2]}, {fn.y[0] - fn.y[1], fn.x[1] - fn.x[0]}};
-			// sub-area derivatives: (p, va, vb) -> d/dva = (vb.y - p.y, p.x - vb.x), d/dvb = (p.y - va.y, va.x - p.x)
-			const float s0a[2] = {fn.y[2] - py, px - fn.x[2]}, s0b[2] = {py - fn.y[1], fn.x[1] - px};   // (p, v1, v2)
-			const float s1a[2] = {fn.y[0] - py, px - fn.x[0]}, s1b[2] = {py - fn.y[2], fn.x[2] - px};   // (p, v2, v0)
-			const float s2a[2] = {fn.y[1] - py, px - fn.x[1]}, s2b[2] = {py - fn.y[0], fn.x[0] - px};   // (p, v0, v1)
-			const float inv_den = rcp_rn_normal(den);   // (div_rn only)
-			// d rho_r / d ndc of face vertex i, component c, and (below) the perspective z-terms of vertex i: parked in LDS
-			// (lane-private slots) until vertex i's columns are formed, which keeps the kernel at <= 96 VGPRs (5 waves/SIMD:
-			// one residency round at 640x480)
-#define DN(i, r, c) dn[(((i) * 3 + (r)) * 2 + (c)) * dn_stride]
-#define PZ(r, i) dn[(18 + (r) * 3 + (i)) * dn_stride]
-#pragma unroll
-			for (int c = 0; c < 2; c++) {
-				DN(0, 0, c) = div_rn(-sa[0] * dA[0][c], den, inv_den);
-				DN(1, 0, c) = div_rn(A * s0a[c] - sa[0] * dA[1][c], den, inv_den);
-				DN(2, 0, c) = div_rn(A * s0b[c] - sa[0] * dA[2][c], den, inv_den);
-				DN(0, 1, c) = div_rn(A * s1b[c] - sa[1] * dA[0][c], den, inv_den);
-				DN(1, 1, c) = div_rn(-sa[1] * dA[1][c], den, inv_den);
-				DN(2, 1, c) = div_rn(A * s1a[c] - sa[1] * dA[2][c], den, inv_den);
-				DN(0, 2, c) = div_rn(A * s2a[c] - sa[2] * dA[0][c], den, inv_den);
-				DN(1, 2, c) = div_rn(A * s2b[c] - sa[2] * dA[1][c], den, inv_den);
-				DN(2, 2, c) = div_rn(-sa[2] * dA[2][c], den, inv_den);
-			}
-			// perspective-correction factors first (RasterizedSurfaceJacobiansImpl.h:217-284), so the 3x9 Jacobian can be
-			// streamed one face vertex (3 columns) at a time: same expressions, far fewer live registers
-			float Pd[3][3];
-			if (a.perspective) {
-				const float z0 = V3[0].z, z1 = V3[1].z, z2 = V3[2].z;
-				const float v12 = z1 * z2, v02 = z0 * z2, v01 = z0 * z1;
-				const float n0 = drho[0] * v12, n1 = drho[1] * v02, n2 = drho[2] * v01;
-				const float dd = fmaxf(n0 + n1 + n2, K_EPSILON);
-				const float dd2 = dd * dd;
-				const float pd[3][3] = {{(dd - n0) * v12, -n0 * v02, -n0 * v01}, {-n1 * v12, (dd - n1) * v02, -n1 * v01},
-				                        {-n2 * v12, -n2 * v02, (dd - n2) * v01}};
-				const float pz0 = drho[1] * z2 + z1 * drho[2];
-				const float pz1 = drho[0] * z2 + z0 * drho[2];
-				const float pz2 = drho[0] * z1 + z0 * drho[1];
-				const float pz[3][3] = {{-n0 * pz0, dd * drho[0] * z2 - n0 * pz1, dd * drho[0] * z1 - n0 * pz2},
-				                        {dd * drho[1] * z2 - n1 * pz0, -n1 * pz1, dd * drho[1] * z0 - n1 * pz2},
-				                        {dd * drho[2] * z1 - n2 * pz0, dd * drho[2] * z0 - n2 * pz1, -n2 * pz2}};
-				const float inv_dd2 = rcp_rn_normal(dd2);   // (div_rn only)
-#pragma unroll
-				for (int r = 0; r < 3; r++)
-#pragma unroll
-					for (int c = 0; c < 3; c++) {
-						Pd[r][c] = div_rn(pd[r][c], dd2, inv_dd2);
-						PZ(r, c) = div_rn(pz[r][c], dd2, inv_dd2);
-					}
-			}
-			// record [dr/dV (9), dr/dn_l (3), rho (3), r]; everything but dr/dV first, so it is not held across the columns
-			float* rec_f = reinterpret_cast<float*>(a.records + 4 * p);
-			if constexpr (RK) {
-				rk[9] = dr_dnl.x;
-				rk[10] = dr_dnl.y;
-				rk[11] = dr_dnl.z;
-				rk[12] = rho[0];
-				rk[13] = rho[1];
-				rk[14] = rho[2];
-				rk[15] = residual;
-			} else {
-				rec_f[9] = dr_dnl.x;
-				rec_f[10] = dr_dnl.y;
-				rec_f[11] = dr_dnl.z;
-				reinterpret_cast<float4*>(rec_f)[3] = make_float4(rho[0], rho[1], rho[2], residual);
-			}
-			// dr/dV = dr/dwl * dwl/dV + dr/dnl * dnl/dV ; dr/dN = dr/dnl (rho (x) I)
-			const float rw[3] = {dr_dwl.x, dr_dwl.y, dr_dwl.z};
-			rn[0] = dr_dnl.x;
-			rn[1] = dr_dnl.y;
-			rn[2] = dr_dnl.z;
-#pragma unroll
-			for (int i = 0; i < 3; i++) {
-				__builtin_amdgcn_sched_barrier(0);   // one face vertex's columns at a time: bounds the live registers
-				const float z = V3[i].z;
-				const float z2 = z * z;
-				const float P0[3] = {a.ndc.ndc.fx / z, 0.f, -a.ndc.ndc.fx * V3[i].x / z2};
-				const float P1[3] = {0.f, a.ndc.ndc.fy / z, -a.ndc.ndc.fy * V3[i].y / z2};
-				float Jc[3][3];   // rows of the 3x9 Jacobian, columns 3i .. 3i+2
-#pragma unroll
-				for (int r = 0; r < 3; r++)
-#pragma unroll
-					for (int c = 0; c < 3; c++) Jc[r][c] = DN(i, r, 0) * P0[c] + DN(i, r, 1) * P1[c];
-				if (a.perspective) {
-					float J2[3][3];
-#pragma unroll
-					for (int r = 0; r < 3; r++)
-#pragma unroll
-						for (int c = 0; c < 3; c++) J2[r][c] = (Pd[r][0] * Jc[0][c] + Pd[r][1] * Jc[1][c]) + Pd[r][2] * Jc[2][c];
-#pragma unroll
-					for (int r = 0; r < 3; r++) J2[r][2] += PZ(r, i);
-#pragma unroll
-					for (int r = 0; r < 3; r++)
-#pragma unroll
-						for (int c = 0; c < 3; c++) Jc[r][c] = J2[r][c];
-				}
-#pragma unroll
-				for (int c = 0; c < 3; c++) {
-					float w_rc[3], n_rc[3];
-#pragma unroll
-					for (int r = 0; r < 3; r++) {
-						const f3 Vk[3] = {V3[0], V3[1], V3[2]};
-						const f3 Nk[3] = {N3[0], N3[1], N3[2]};
-						const float vr0 = r == 0 ? Vk[0].x : (r == 1 ? Vk[0].y : Vk[0].z);
-						const float vr1 = r == 0 ? Vk[1].x : (r == 1 ? Vk[1].y : Vk[1].z);
-						const float vr2 = r == 0 ? Vk[2].x : (r == 1 ? Vk[2].y : Vk[2].z);
-						const float nr0 = r == 0 ? Nk[0].x : (r == 1 ? Nk[0].y : Nk[0].z);
-						const float nr1 = r == 0 ? Nk[1].x : (r == 1 ? Nk[1].y : Nk[1].z);
-						const float nr2 = r == 0 ? Nk[2].x : (r == 1 ? Nk[2].y : Nk[2].z);
-						w_rc[r] = (vr0 * Jc[0][c] + vr1 * Jc[1][c]) + vr2 * Jc[2][c];
-						if (c == r) w_rc[r] += rho[i];
-						n_rc[r] = (nr0 * Jc[0][c] + nr1 * Jc[1][c]) + nr2 * Jc[2][c];
-					}
-					const float x = (rw[0] * w_rc[0] + rw[1] * w_rc[1]) + rw[2] * w_rc[2];
-					const float y = (rn[0] * n_rc[0] + rn[1] * n_rc[1]) + rn[2] * n_rc[2];
-					if constexpr (RK) rk[3 * i + c] = x + y;
-					else rec_f[3 * i + c] = x + y;   // stored as formed: no 9-float tail of live outputs
-				}
-			}
-#undef DN
-#undef PZ
-
-		}
+		out_face = pen.contributes ? face : -1;
+		out_vid[0] = r.vid[0];
+		out_vid[1] = r.vid[1];
+		out_vid[2] = r.vid[2];
+		if (pen.contributes) pixel_record<RK>(w, r, pen, dn, dn_stride, reinterpret_cast<float*>(a.records + 4 * p), rk);
 	}
 }
 
@@ -550,10 +336,8 @@ __device__ __forceinline__ void node_body(const FitPixelArgs& a, float* slots0, 
 	float4 jv[3];
 	[[maybe_unused]] float4 jn[3];   // the unfused / gathered rows only
 	float4 rq[4];
-#if !NNRT_GATHER_ROWS
-	float4 ns4[4];   // the association's node state (g, t, R), and per face vertex its canonical position / normal
-	float4 cp4[3], cn4[3];
-#endif
+	// the association's node state (g, t, R), and per face vertex its canonical position / normal (not NNRT_GATHER_ROWS)
+	[[maybe_unused]] float4 ns4[4], cp4[3], cn4[3];
 	auto gather = [&](float* slots, int count) {
 		d = make_int4(0, -1, -1, -1);
 		int pl = 0;
@@ -650,106 +434,8 @@ __device__ __forceinline__ void node_body(const FitPixelArgs& a, float* slots0, 
 			(void)l;
 			const float q[16] = {rq[0].x, rq[0].y, rq[0].z, rq[0].w, rq[1].x, rq[1].y, rq[1].z, rq[1].w,
 			                     rq[2].x, rq[2].y, rq[2].z, rq[2].w, rq[3].x, rq[3].y, rq[3].z, rq[3].w};
-			const float dr_dV[9] = {q[0], q[1], q[2], q[3], q[4], q[5], q[6], q[7], q[8]};
-			const float rn[3] = {q[9], q[10], q[11]};
-			const float rho[3] = {q[12], q[13], q[14]};
-			float jr[3] = {0.f, 0.f, 0.f}, jt[3] = {0.f, 0.f, 0.f};
-#if NNRT_JAC_FMA && !NNRT_GATHER_ROWS
-			// Fused form (round 5): per face vertex, with ws = w if the vertex is anchored to the node, else 0,
-			//   jt += ws dv,   jr += -ws (dv x R (v - g) + dn x R n)
-			// i.e. the reference's dv [-w R (v - g)]_x + dn [-w R n]_x (PixelVertexAnchorJacobiansImpl.h:179-363,
-			// WarpedSurfaceJacobiansImpl.h:117-156) with -w factored out of the cross products and every product-sum an
-			// FMA (the build is -ffp-contract=off), as nvcc's default contraction of the reference's CUDA path also
-			// does: 43 VALU per face vertex instead of 78, the terms within a few float ulps of the unfused rows (the
-			// unfused, oracle-bit-identical form: -DNNRT_JAC_FMA=0). A vertex not anchored to the node adds ws = 0
-			// products, i.e. +-0, which leave the +0-started sums unchanged bit for bit (finite inputs: the vertex's own
-			// canonical position / normal, the pixel's record and the node's state, never the padding row's data).
-			{
-				float R[9];
-				f3 g = make3(0.f, 0.f, 0.f);
-				if (MODE != NNRT_ITERATION_TRANSLATION_ONLY) {
-					g = make3(ns4[0].x, ns4[0].y, ns4[0].z);
-					if (a.state_identity) {
-#pragma unroll
-						for (int i = 0; i < 9; i++) R[i] = (i % 4 == 0) ? 1.f : 0.f;
-					} else {
-						const float Rl[9] = {ns4[1].z, ns4[1].w, ns4[2].x, ns4[2].y, ns4[2].z, ns4[2].w, ns4[3].x, ns4[3].y, ns4[3].z};
-#pragma unroll
-						for (int i = 0; i < 9; i++) R[i] = Rl[i];
-					}
-				}
-#pragma unroll
-				for (int fv = 0; fv < 3; fv++) {
-					const float ws = rows[fv] >= 0 ? jv[fv].w : 0.f;
-					const f3 dv = make3(dr_dV[3 * fv], dr_dV[3 * fv + 1], dr_dV[3 * fv + 2]);
-					if (MODE != NNRT_ITERATION_ROTATION_ONLY) {
-						jt[0] = fmaf(dv.x, ws, jt[0]);
-						jt[1] = fmaf(dv.y, ws, jt[1]);
-						jt[2] = fmaf(dv.z, ws, jt[2]);
-					}
-					if (MODE != NNRT_ITERATION_TRANSLATION_ONLY) {
-						const f3 d3 = sub3(make3(cp4[fv].x, cp4[fv].y, cp4[fv].z), g);
-						const f3 n3 = make3(cn4[fv].x, cn4[fv].y, cn4[fv].z);
-						const f3 p = make3(fmaf(R[0], d3.x, fmaf(R[1], d3.y, R[2] * d3.z)), fmaf(R[3], d3.x, fmaf(R[4], d3.y, R[5] * d3.z)),
-						                   fmaf(R[6], d3.x, fmaf(R[7], d3.y, R[8] * d3.z)));
-						const f3 q = make3(fmaf(R[0], n3.x, fmaf(R[1], n3.y, R[2] * n3.z)), fmaf(R[3], n3.x, fmaf(R[4], n3.y, R[5] * n3.z)),
-						                   fmaf(R[6], n3.x, fmaf(R[7], n3.y, R[8] * n3.z)));
-						const f3 dn = make3(rn[0] * rho[fv], rn[1] * rho[fv], rn[2] * rho[fv]);
-						// dv x p + dn x q
-						const float cx = fmaf(dv.y, p.z, fmaf(-dv.z, p.y, fmaf(dn.y, q.z, -dn.z * q.y)));
-						const float cy = fmaf(dv.z, p.x, fmaf(-dv.x, p.z, fmaf(dn.z, q.x, -dn.x * q.z)));
-						const float cz = fmaf(dv.x, p.y, fmaf(-dv.y, p.x, fmaf(dn.x, q.y, -dn.y * q.x)));
-						jr[0] = fmaf(-ws, cx, jr[0]);
-						jr[1] = fmaf(-ws, cy, jr[1]);
-						jr[2] = fmaf(-ws, cz, jr[2]);
-					}
-				}
-			}
-#else
-#if !NNRT_GATHER_ROWS
-			if (MODE != NNRT_ITERATION_TRANSLATION_ONLY) {
-				// (-w R (v - g), -w R n) per face vertex: warp_slot's expressions (kernels.hpp), bit-identical to its rows
-				const f3 g = make3(ns4[0].x, ns4[0].y, ns4[0].z);
-				float R[9];
-				if (a.state_identity) {
-#pragma unroll
-					for (int i = 0; i < 9; i++) R[i] = (i % 4 == 0) ? 1.f : 0.f;
-				} else {
-					const float Rl[9] = {ns4[1].z, ns4[1].w, ns4[2].x, ns4[2].y, ns4[2].z, ns4[2].w, ns4[3].x, ns4[3].y, ns4[3].z};
-#pragma unroll
-					for (int i = 0; i < 9; i++) R[i] = Rl[i];
-				}
-#pragma unroll
-				for (int fv = 0; fv < 3; fv++) {
-					const float w = jv[fv].w;
-					const f3 Rj = matvec3(R, sub3(make3(cp4[fv].x, cp4[fv].y, cp4[fv].z), g));
-					const f3 Rnj = matvec3(R, make3(cn4[fv].x, cn4[fv].y, cn4[fv].z));
-					jv[fv] = make_float4(-w * Rj.x, -w * Rj.y, -w * Rj.z, w);
-					jn[fv] = make_float4(-w * Rnj.x, -w * Rnj.y, -w * Rnj.z, 0.f);
-				}
-			}
-#endif
-			// branch-free over the face vertices: a vertex not anchored to the node adds an exact +0 (selected, so the
-			// row it loaded in its place -- row 0 -- never reaches the sums, NaN or not)
-#pragma unroll
-			for (int fv = 0; fv < 3; fv++) {
-				const bool on = rows[fv] >= 0;
-				const f3 dv = make3(dr_dV[3 * fv], dr_dV[3 * fv + 1], dr_dV[3 * fv + 2]);
-				if (MODE != NNRT_ITERATION_ROTATION_ONLY) {
-					jt[0] += on ? dv.x * jv[fv].w : 0.f;
-					jt[1] += on ? dv.y * jv[fv].w : 0.f;
-					jt[2] += on ? dv.z * jv[fv].w : 0.f;
-				}
-				if (MODE != NNRT_ITERATION_TRANSLATION_ONLY) {
-					const f3 dn = make3(rn[0] * rho[fv], rn[1] * rho[fv], rn[2] * rho[fv]);
-					const f3 t1 = row_times_skew(dv, make3(jv[fv].x, jv[fv].y, jv[fv].z));
-					const f3 t2 = row_times_skew(dn, make3(jn[fv].x, jn[fv].y, jn[fv].z));
-					jr[0] += on ? t1.x + t2.x : 0.f;
-					jr[1] += on ? t1.y + t2.y : 0.f;
-					jr[2] += on ? t1.z + t2.z : 0.f;
-				}
-			}
-#endif
+			float jr[3], jt[3];
+			pixel_node_row<MODE>(rows, jv, jn, ns4, cp4, cn4, q, a.state_identity != 0, jr, jt);
 			float J[8];
 			if (MODE == NNRT_ITERATION_ALL) {
 				J[0] = jr[0];
@@ -1209,10 +895,11 @@ nnrt_status launch_fit_pixels(int mode, const FitPixelArgs& args, hipStream_t st
 
 // =====================================================================================================================
 // Coupled data term (NNRT_DATA_COUPLED, mode ALL): the off-diagonal blocks J_a^T J_b of every pair
-// a < b of a contributing pixel's face nodes, a second launch after the fused one. Pass 1 reset the raster keys, so each
-// lane puts its pixel's face (the fused launch's pixel_face output) back into its key and runs pixel_body again: the
-// same re-resolve from the warped mesh, the same record (kept in registers), the key reset once more. The pixel-node
-// Jacobian rows restate pass 2's (2b) arithmetic, build switches included.
+// a < b of a contributing pixel's face nodes, a second launch after the fused one. It reads pass 1's pixel_face and
+// residual_mask outputs and writes only pair_acc: each lane resolves its pixel's face again from the warped mesh and
+// forms the pixel's record in registers with pass 1's own functions (pixel_terms.hpp: resolve_face, resolve_distance,
+// pixel_penalty -- the same `contributes` decision -- and pixel_record), then every node's Jacobian row with pass 2's
+// (pixel_node_row).
 //
 // One wave per 8 x 8 pixels (the fused launch's arithmetic tile mapping). Per lane: the face's table row and the J row of
 // every entry, parked in LDS (lane-private columns). The lane's pairs (a < b over its ascending row) are ascending in the
@@ -1234,116 +921,35 @@ __device__ __forceinline__ int pair_slot(const int* __restrict__ row_off, const 
 	return -1;
 }
 
-// the pixel-node Jacobian row (mode ALL: rotation 3, translation 3) of face-table entry `code` for the pixel whose face
-// has vertices vid and whose record is rk: node_body's (2a) loads and (2b) expressions
-__device__ __forceinline__ void pair_node_jacobian(const FitPixelArgs& a, uint32_t code, const int (&vid)[3], const float (&rk)[16], float (&J)[6]) {
-	const int KA = a.anchor_count;
-	const int node = static_cast<int>(code >> FACE_NODE_SHIFT);
-	int rows[3];
+// what pixel_node_row takes for face-table entry `code` of a face with vertices vid: node_body's (2a) loads, one
+// association at a time
+__device__ __forceinline__ void pair_row_loads(const FitPixelArgs& a, uint32_t code, const int (&vid)[3], int (&rows)[3], float4 (&jv)[3], float4 (&jn)[3],
+                                               float4 (&ns4)[4], float4 (&cp4)[3], float4 (&cn4)[3]) {
 #pragma unroll
 	for (int fv = 0; fv < 3; fv++) {
 		const int k = static_cast<int>((code >> (4 * fv)) & 0xFu);
-		rows[fv] = k != 0xF ? vid[fv] * KA + k : -1;
-	}
-	float4 jv[3];
-	[[maybe_unused]] float4 jn[3];
-#if NNRT_GATHER_ROWS
-#pragma unroll
-	for (int fv = 0; fv < 3; fv++) {
+		rows[fv] = k != 0xF ? vid[fv] * a.anchor_count + k : -1;
 		const int r = rows[fv] >= 0 ? rows[fv] : 0;
-		const float w = a.weights[r];
+#if NNRT_GATHER_ROWS
 		const float2* row = a.jrows + 3 * static_cast<int64_t>(r);
 		const float2 j0 = row[0], j1 = row[1], j2 = row[2];
-		jv[fv] = make_float4(j0.x, j0.y, j1.x, w);
+		jv[fv] = make_float4(j0.x, j0.y, j1.x, a.weights[r]);
 		jn[fv] = make_float4(j1.y, j2.x, j2.y, 0.f);
-	}
 #else
-	float4 ns4[4], cp4[3], cn4[3];
-#pragma unroll
-	for (int fv = 0; fv < 3; fv++) {
-		const int r = rows[fv] >= 0 ? rows[fv] : 0;
 		jv[fv].w = a.weights[r];
 		cp4[fv] = a.cmesh_p[vid[fv]];
 		cn4[fv] = a.cmesh_n[vid[fv]];
-	}
-	{
-		const float4* ns = a.state_in + 4 * static_cast<int64_t>(node);
-		ns4[0] = ns[0];
-		if (!a.state_identity) {
-			ns4[1] = ns[1];
-			ns4[2] = ns[2];
-			ns4[3] = ns[3];
-		}
-	}
-	const f3 g = make3(ns4[0].x, ns4[0].y, ns4[0].z);
-	float R[9];
-	if (a.state_identity) {
-#pragma unroll
-		for (int i = 0; i < 9; i++) R[i] = (i % 4 == 0) ? 1.f : 0.f;
-	} else {
-		const float Rl[9] = {ns4[1].z, ns4[1].w, ns4[2].x, ns4[2].y, ns4[2].z, ns4[2].w, ns4[3].x, ns4[3].y, ns4[3].z};
-#pragma unroll
-		for (int i = 0; i < 9; i++) R[i] = Rl[i];
-	}
 #endif
-	const float dr_dV[9] = {rk[0], rk[1], rk[2], rk[3], rk[4], rk[5], rk[6], rk[7], rk[8]};
-	const float rn[3] = {rk[9], rk[10], rk[11]};
-	const float rho[3] = {rk[12], rk[13], rk[14]};
-	float jr[3] = {0.f, 0.f, 0.f}, jt[3] = {0.f, 0.f, 0.f};
-#if NNRT_JAC_FMA && !NNRT_GATHER_ROWS
-#pragma unroll
-	for (int fv = 0; fv < 3; fv++) {
-		const float ws = rows[fv] >= 0 ? jv[fv].w : 0.f;
-		const f3 dv = make3(dr_dV[3 * fv], dr_dV[3 * fv + 1], dr_dV[3 * fv + 2]);
-		jt[0] = fmaf(dv.x, ws, jt[0]);
-		jt[1] = fmaf(dv.y, ws, jt[1]);
-		jt[2] = fmaf(dv.z, ws, jt[2]);
-		const f3 d3 = sub3(make3(cp4[fv].x, cp4[fv].y, cp4[fv].z), g);
-		const f3 n3 = make3(cn4[fv].x, cn4[fv].y, cn4[fv].z);
-		const f3 p = make3(fmaf(R[0], d3.x, fmaf(R[1], d3.y, R[2] * d3.z)), fmaf(R[3], d3.x, fmaf(R[4], d3.y, R[5] * d3.z)),
-		                   fmaf(R[6], d3.x, fmaf(R[7], d3.y, R[8] * d3.z)));
-		const f3 q = make3(fmaf(R[0], n3.x, fmaf(R[1], n3.y, R[2] * n3.z)), fmaf(R[3], n3.x, fmaf(R[4], n3.y, R[5] * n3.z)),
-		                   fmaf(R[6], n3.x, fmaf(R[7], n3.y, R[8] * n3.z)));
-		const f3 dn = make3(rn[0] * rho[fv], rn[1] * rho[fv], rn[2] * rho[fv]);
-		const float cx = fmaf(dv.y, p.z, fmaf(-dv.z, p.y, fmaf(dn.y, q.z, -dn.z * q.y)));
-		const float cy = fmaf(dv.z, p.x, fmaf(-dv.x, p.z, fmaf(dn.z, q.x, -dn.x * q.z)));
-		const float cz = fmaf(dv.x, p.y, fmaf(-dv.y, p.x, fmaf(dn.x, q.y, -dn.y * q.x)));
-		jr[0] = fmaf(-ws, cx, jr[0]);
-		jr[1] = fmaf(-ws, cy, jr[1]);
-		jr[2] = fmaf(-ws, cz, jr[2]);
 	}
-#else
 #if !NNRT_GATHER_ROWS
-#pragma unroll
-	for (int fv = 0; fv < 3; fv++) {
-		const float w = jv[fv].w;
-		const f3 Rj = matvec3(R, sub3(make3(cp4[fv].x, cp4[fv].y, cp4[fv].z), g));
-		const f3 Rnj = matvec3(R, make3(cn4[fv].x, cn4[fv].y, cn4[fv].z));
-		jv[fv] = make_float4(-w * Rj.x, -w * Rj.y, -w * Rj.z, w);
-		jn[fv] = make_float4(-w * Rnj.x, -w * Rnj.y, -w * Rnj.z, 0.f);
+	const float4* ns = a.state_in + 4 * static_cast<int64_t>(code >> FACE_NODE_SHIFT);
+	ns4[0] = ns[0];
+	if (!a.state_identity) {
+		ns4[1] = ns[1];
+		ns4[2] = ns[2];
+		ns4[3] = ns[3];
 	}
 #endif
-#pragma unroll
-	for (int fv = 0; fv < 3; fv++) {
-		const bool on = rows[fv] >= 0;
-		const f3 dv = make3(dr_dV[3 * fv], dr_dV[3 * fv + 1], dr_dV[3 * fv + 2]);
-		jt[0] += on ? dv.x * jv[fv].w : 0.f;
-		jt[1] += on ? dv.y * jv[fv].w : 0.f;
-		jt[2] += on ? dv.z * jv[fv].w : 0.f;
-		const f3 dn = make3(rn[0] * rho[fv], rn[1] * rho[fv], rn[2] * rho[fv]);
-		const f3 t1 = row_times_skew(dv, make3(jv[fv].x, jv[fv].y, jv[fv].z));
-		const f3 t2 = row_times_skew(dn, make3(jn[fv].x, jn[fv].y, jn[fv].z));
-		jr[0] += on ? t1.x + t2.x : 0.f;
-		jr[1] += on ? t1.y + t2.y : 0.f;
-		jr[2] += on ? t1.z + t2.z : 0.f;
-	}
-#endif
-	J[0] = jr[0];
-	J[1] = jr[1];
-	J[2] = jr[2];
-	J[3] = jt[0];
-	J[4] = jt[1];
-	J[5] = jt[2];
 }
 
 constexpr int PAIR_ROW = 13;   // LDS stride of a filed (J_a, J_b) row (12 floats; odd: the lanes' stores spread over the banks)
@@ -1354,7 +960,7 @@ template <int MAXK, int LW>
 __global__ __launch_bounds__(PIX_BLOCK) void k_fit_pairs(FitPixelArgs a, FitPairArgs pa) {
 	constexpr int NSLOT = 3 * MAXK;
 	constexpr int WORDS = NSLOT * 6 * 64 + NSLOT * 64 + 64 * PAIR_ROW;
-	static_assert(NSLOT * 6 >= 27, "pass 1's parked terms alias the Jacobian rows");
+	static_assert(NSLOT * 6 >= 27, "the record's parked terms alias the Jacobian rows");
 	__shared__ float s_u[LW][WORDS];
 	const int wave = static_cast<int>(threadIdx.x >> 6), lane = static_cast<int>(threadIdx.x & 63);
 	if (wave < pa.wave_base || wave >= pa.wave_base + LW) return;   // wave-uniform
@@ -1362,7 +968,9 @@ __global__ __launch_bounds__(PIX_BLOCK) void k_fit_pairs(FitPixelArgs a, FitPair
 	float* jst = w;                                                       // [(entry * 6 + c) * 64 + lane]
 	uint32_t* ent = reinterpret_cast<uint32_t*>(w + NSLOT * 6 * 64);      // [entry * 64 + lane]
 	float* filed = w + NSLOT * 6 * 64 + NSLOT * 64;                       // [rank * PAIR_ROW + 0..11]
-	// this lane's pixel (pixel_body's mapping): its key takes the fused launch's face back
+	// this lane's pixel (pixel_body's mapping), the face and mask pass 1 left for it, and its record, in registers
+	int face = -1, vid[3] = {0, 0, 0}, n = 0;
+	float rk[16];
 	{
 		const int tiles = a.tiles_x * a.tiles_y;
 		const int qd = pix_quadrant(a), tile = qd >> 2, quad = qd & 3;
@@ -1370,18 +978,25 @@ __global__ __launch_bounds__(PIX_BLOCK) void k_fit_pairs(FitPixelArgs a, FitPair
 		const int u = tu * PIX_TILE + (quad & 1) * 8 + (lane & 7), v = tv * PIX_TILE + (quad >> 1) * 8 + (lane >> 3);
 		if (tile < tiles && u < a.W && v < a.H) {
 			const int64_t p = static_cast<int64_t>(v) * a.W + u;
-			const int32_t f = a.pixel_face[p];
-			a.keys[p] = f >= 0 ? static_cast<uint64_t>(static_cast<uint32_t>(f)) : EMPTY_KEY;
+			const PixelResolveView vw = pixel_resolve_view(a);
+			const int32_t f = a.residual_mask[p] ? a.pixel_face[p] : -1;
+			PixelResolve r = resolve_pixel(vw, u, v);
+			if (f >= 0 && resolve_face(vw, f, r)) {
+				resolve_distance(vw, u, v, p, true, true, r);   // (the mask says that pass 1 found the depth valid)
+				const PixelPenalty pen = pixel_penalty(a.use_tukey, a.tukey_c, true, r.nl, r.d, r.dist);
+				if (pen.contributes) {
+					pixel_record<true>(vw, r, pen, w + lane, 64, nullptr, rk);
+					face = f;
+					n = r.nodes;
+#pragma unroll
+					for (int i = 0; i < 3; i++) vid[i] = r.vid[i];
+				}
+			}
 		}
 	}
-	int face = -1, vid[3] = {0, 0, 0}, n = 0;
-	float rk[16];
-#pragma unroll
-	for (int i = 0; i < 16; i++) rk[i] = 0.f;
-	pixel_body<NNRT_ITERATION_ALL, true>(a, w + lane, 64, face, vid, rk, n);
-	__builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-	__builtin_amdgcn_wave_barrier();
-	__builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+	// No fence or barrier here: nothing was stored to global memory, and the record's parked terms, jst and ent are
+	// lane-private LDS columns, written and read by the same lane in program order (`filed`, the one region lanes share, is
+	// guarded by wave_sync below).
 	// the face's table row and every entry's J row into this lane's LDS columns
 	if (face < 0) n = 0;
 	n = n < NSLOT ? n : NSLOT;
@@ -1392,10 +1007,17 @@ __global__ __launch_bounds__(PIX_BLOCK) void k_fit_pairs(FitPixelArgs a, FitPair
 			break;
 		}
 		ent[i * 64 + lane] = code;
-		float J[6];
-		pair_node_jacobian(a, code, vid, rk, J);
+		int rows[3];
+		float4 jv[3];
+		[[maybe_unused]] float4 jn[3], ns4[4], cp4[3], cn4[3];
+		pair_row_loads(a, code, vid, rows, jv, jn, ns4, cp4, cn4);
+		float jr[3], jt[3];
+		pixel_node_row<NNRT_ITERATION_ALL>(rows, jv, jn, ns4, cp4, cn4, rk, a.state_identity != 0, jr, jt);
 #pragma unroll
-		for (int c = 0; c < 6; c++) jst[(i * 6 + c) * 64 + lane] = J[c];
+		for (int c = 0; c < 3; c++) {
+			jst[(i * 6 + c) * 64 + lane] = jr[c];
+			jst[(i * 6 + 3 + c) * 64 + lane] = jt[c];
+		}
 	}
 	// the lane's next pair (ia < ib over its row) and its slot; INT_MAX: none left
 	constexpr int NONE = 0x7fffffff;

@@ -122,9 +122,9 @@ __global__ __launch_bounds__(STEP_COST_THREADS) void k_step_cost(StepCostArgs a)
 // The cost under NNRT_STEP_OBJECTIVE_ROBUST. Same structure as k_step_cost, one lane per item, the
 // items being the P pixels and then the E edges. The fused pixel launch leaves the scaled residual s r behind, from which
 // r cannot be recovered, so a masked pixel is resolved again from what the iteration has left on the device: the pixel's
-// face (pixel_face), the warped mesh and the reference point, by pass 1's operations in pass 1's order (pixel_body in
-// fitter_kernels.hip, from face_test to `dist`; -ffp-contract=off: the same IEEE operations give the same bits). r goes
-// to raw[p] (0 outside the mask). Per pixel, in fp64: r^2, or with the IRLS Tukey penalty (c^2 / 3)(1 - (1 - q^2)^3),
+// face (pixel_face), the warped mesh and the reference point, by pass 1's own resolve (resolve_face and resolve_distance
+// in pixel_terms.hpp; -ffp-contract=off: the same IEEE operations give the same bits). r goes to raw[p] (0 outside the
+// mask). Per pixel, in fp64: r^2, or with the IRLS Tukey penalty (c^2 / 3)(1 - (1 - q^2)^3),
 // q = r / c, formed as (c^2 / 3) q^2 (3 + q^2 (q^2 - 3)) (no cancellation for small q), c^2 / 3 beyond the cutoff; NaN
 // where r is not finite. Per edge: m^2 = the fp64 sum of squares of its three stored entries, or with the IRLS Huber
 // penalty m^2 if m^2 <= delta^2 else 2 m^2 - delta^2 (the stored entries are sqrt(delta / n) e, so m^2 = delta n).
@@ -152,44 +152,10 @@ __global__ __launch_bounds__(STEP_COST_THREADS) void k_step_cost_robust(StepCost
 			const int32_t face = mask ? ra.pixel_face[i] : -1;
 			if (face >= 0 && face < ra.F) {
 				const int u = static_cast<int>(i % ra.W), v = static_cast<int>(i / ra.W);
-				RasterHit h{0.f, 0.f, 0.f, 0.f, 0.f};
-				f3 V3[3], N3[3];
-				FaceNdc fn;
-				const float px = pixel_ndc(u, ra.ax), py = pixel_ndc(v, ra.ay);
-				const int4 fi = ra.faces4[face];
-				const int vid[3] = {fi.x, fi.y, fi.z};
-#pragma unroll
-				for (int q = 0; q < 3; q++) {
-					const float4 wp = ra.wpos[vid[q]];
-					const float4 wn = ra.wnrm[vid[q]];
-					V3[q] = make3(wp.x, wp.y, wp.z);
-					N3[q] = make3(wn.x, wn.y, wn.z);
-					ra.ndc.ndc.project(V3[q].x, V3[q].y, V3[q].z, &fn.x[q], &fn.y[q]);
-					fn.z[q] = V3[q].z;
-				}
-				if (face_test<false>(fn, px, py, ra.blur, ra.perspective, false, true, h)) {
-					const float depth = h.depth;   // (the mask says that pass 1 found it valid)
-					f3 nl = make3(0.f, 0.f, 0.f);
-					float acc;
-					acc = 0.0f;
-					acc += h.b0 * N3[0].x;
-					acc += h.b1 * N3[1].x;
-					acc += h.b2 * N3[2].x;
-					nl.x = acc;
-					acc = 0.0f;
-					acc += h.b0 * N3[0].y;
-					acc += h.b1 * N3[1].y;
-					acc += h.b2 * N3[2].y;
-					nl.y = acc;
-					acc = 0.0f;
-					acc += h.b0 * N3[0].z;
-					acc += h.b1 * N3[1].z;
-					acc += h.b2 * N3[2].z;
-					nl.z = acc;
-					const f3 prast = make3((static_cast<float>(u) - ra.pix.cx) * depth / ra.pix.fx, (static_cast<float>(v) - ra.pix.cy) * depth / ra.pix.fy, depth);
-					const float4 qr = ra.ref_points[i];
-					const f3 d = sub3(prast, make3(qr.x, qr.y, qr.z));   // point map vector w_l - o_l
-					dist = dot3(nl, d);
+				PixelResolve r = resolve_pixel(ra.view, u, v);
+				if (resolve_face(ra.view, face, r)) {
+					resolve_distance(ra.view, u, v, i, true, true, r);   // (the mask says that pass 1 found the depth valid)
+					dist = r.dist;
 				}
 			}
 			ra.raw[i] = dist;

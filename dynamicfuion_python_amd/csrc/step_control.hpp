@@ -5,7 +5,7 @@
 // place: the same tail, the robust cost of the raw residuals it resolves again.
 #pragma once
 
-#include "common.hpp"
+#include "pixel_terms.hpp"
 
 namespace nnrt {
 
@@ -49,21 +49,13 @@ struct StepCostArgs {
 // (one per pixel, one per edge); base.residuals is not read
 struct StepCostRobustArgs {
 	StepCostArgs base;
+	PixelResolveView view;         // what the resolve reads, as the fused pixel launch received it
 	int64_t F;                     // faces (pixel_face is checked against it)
 	int E;                         // ARAP edges
 	int W;
-	int perspective;
 	int use_tukey, use_huber;      // 1: the IRLS form of the penalty is on
 	float tukey_c, huber_delta;
-	float blur;
-	PixelAxis ax, ay;
-	NdcSetup ndc;
-	Camera pix;
 	const int32_t* pixel_face;     // [P] the face pass 1 resolved (-1: none)
-	const int4* faces4;            // [F]
-	const float4* wpos;            // [V] the warped mesh as pass 1 read it
-	const float4* wnrm;
-	const float4* ref_points;      // [P]
 	float* raw;                    // [P] out: the raw point-to-plane distance (0 outside the mask)
 };
 

@@ -121,6 +121,56 @@ def test_system_parity(nn, oracle_mod, scenes, start, anchor_count):
     assert blocks[touched].any()
 
 
+def test_system_parity_at_image_edges(nn, oracle_mod, scenes):
+    """test_system_parity's `identity, 4 anchors` case on S1 cropped to 74 x 102 about its centre: neither side is a multiple
+    of 8, so the last quadrant of every row and column of the pair launch holds lanes outside the image, and the mesh
+    overflows the crop, so the lanes beside them contribute."""
+    import dataclasses
+    s1, _ = scenes["S1"]
+    H, W = 74, 102
+    K = s1.K.copy()
+    K[0, 2], K[1, 2] = W / 2, H / 2
+    sc = dataclasses.replace(s1, H=H, W=W, K=K)
+    depth = scene_target(oracle_mod, sc)
+    wf, ft = _fitter(nn, sc)
+    R, t = _motion(wf)
+    ft.prepare(wf, _mesh(nn, sc), depth, None, sc.K, None, 1.0)
+    ft.iterate(wf, 0, 1)
+    ft.check()
+    want = coupled_system(oracle_mod, sc, depth, R, t, lm=LM)
+    contributes = want["data"]["contributes"].reshape(H, W)
+    assert contributes[:, W - W % 8:].any() and contributes[H - H % 8:].any(), "no contributing pixel in the partial quadrants"
+    diag, pairs, blocks, rhs = _check_system(ft, want, _hg_bar(), f"S1 cropped to {H} x {W}")
+    touched = want["data"]["touched"][pairs[:, 0], pairs[:, 1]]
+    assert not blocks[~touched].any()
+    assert blocks[touched].any()
+
+
+# ---- 2b. the pair launch has no say in pass 1's outputs -------------------------------------------------------------------
+@pytest.mark.parametrize("tukey", [False, True])
+def test_pair_launch_leaves_pass_one_outputs(nn, oracle_mod, scenes, tukey):
+    """One eager iteration from the same S1 start, block-diagonal and coupled: residuals, residual mask and pixel faces
+    are pass 1's alone, bit for bit. With IRLS Tukey: the target and cutoff test_gpu_robust_step.py takes for S1_coupled."""
+    import _robust_step_util as RU
+    sc, depth = scenes["S1"]
+    kw = {}
+    if tukey:
+        sc, depth, c, _ = RU.config_inputs(oracle_mod, scenes, "S1_coupled")
+        kw = dict(use_tukey_penalty_for_data_term=True, tukey_penalty_cutoff_cm=c, penalty_form=nn.alignment.PenaltyForm.IRLS)
+    out = []
+    for coupled in (False, True):
+        wf, ft = _fitter(nn, sc, coupled=coupled, **kw)
+        ft.prepare(wf, _mesh(nn, sc), depth, None, sc.K, None, 1.0)
+        ft.iterate(wf, 0, 1)
+        ft.check()
+        out.append(ft.diagnostics())
+    assert out[0]["residual_mask"].any() and (out[0]["pixel_faces"] >= 0).any()
+    if tukey:   # some masked pixels lie beyond the cutoff: their stored residual is the exact 0 of a pixel without weight
+        assert (out[0]["residuals"][out[0]["residual_mask"]] == 0).any()
+    for key in ("residuals", "residual_mask", "pixel_faces"):
+        assert np.array_equal(out[0][key], out[1][key], equal_nan=True), key
+
+
 # ---- 3. system parity with ARAP and IRLS --------------------------------------------------------------------------------
 @pytest.mark.parametrize("irls", [False, True])
 def test_system_parity_arap(nn, oracle_mod, scenes, irls):

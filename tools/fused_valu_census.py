@@ -10,7 +10,8 @@ k_fit_pixels_fused (default <0,4,5>: ALL, 4 anchors, 5 waves per SIMD):
 Regions are line ranges of fitter_kernels.hip found from the source's own anchors (the lambdas of node_body, pixel_body,
 the branch of sums that walks a batch slot by slot). An instruction belongs to the region of the .loc in force where it
 stands; the .loc's comment carries the chain of inlined call sites, and the innermost fitter_kernels.hip line of the
-chain that lies in a named region decides (so div_rn, face_test, matvec3, ... count with their caller). A compiler
+chain that lies in a named region decides (so div_rn, face_test, matvec3 and the functions of pixel_terms.hpp count with
+their caller). A compiler
 generated instruction without a line keeps the region before it. The counts are static: a loop body counts once, both
 sides of a branch count.
 
