@@ -125,6 +125,11 @@ _SIGNATURES = {
     "nnrt_rigid_align_point_to_plane": (c_int32, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int32, c_int32, c_float, c_float, c_float,
                                                   c_float, c_void_p, c_int32, c_float, c_float, c_int32, c_int32, c_void_p, c_void_p, c_int32,
                                                   c_void_p, c_void_p]),
+    "nnrt_rigid_align_hybrid": (c_int32, [c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_float, c_float,
+                                          c_float, c_float, c_void_p, c_int32, c_float, c_float, c_int32, c_int32, c_float, c_float, c_void_p,
+                                          c_void_p, c_int32, c_void_p, c_void_p]),
+    "nnrt_intensity_from_rgb8": (c_int32, [c_void_p, c_int32, c_int32, c_void_p, c_void_p]),
+    "nnrt_intensity_halve": (c_int32, [c_void_p, c_int32, c_int32, c_void_p, c_void_p]),
     "nnrt_warp_mesh": (c_int32, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_int32,
                                  c_void_p, c_void_p, c_void_p, c_void_p]),
     "nnrt_warp_points": (c_int32, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_int32, c_float,

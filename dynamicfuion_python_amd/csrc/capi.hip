@@ -303,11 +303,12 @@ nnrt_status nnrt_compute_anchors_and_weights_shortest_path(const float* d_points
 	                                    static_cast<hipStream_t>(stream));
 }
 
-nnrt_status nnrt_rigid_align_point_to_plane(const float* d_points, const float* d_normals, int64_t V, const float* d_target_points,
-                                            const float* d_target_normals, int32_t H, int32_t W, float fx, float fy, float cx, float cy,
-                                            const double* h_T_init, int32_t iterations, float distance_threshold, float normal_agreement_cos,
-                                            int32_t cull_back_faces, int32_t minimum_correspondence_count, double* h_T_out, double* h_log,
-                                            int32_t log_row_capacity, int32_t* h_status, void* stream) {
+// the argument checks the two rigid alignment entry points share; log_columns: 2, or 4 for the hybrid log
+static nnrt_status check_rigid_align_arguments(const float* d_points, const float* d_normals, int64_t V, const float* d_target_points,
+                                               const float* d_target_normals, int32_t H, int32_t W, float fx, float fy, float cx, float cy,
+                                               const double* h_T_init, int32_t iterations, float distance_threshold, float normal_agreement_cos,
+                                               int32_t minimum_correspondence_count, const double* h_T_out, const double* h_log,
+                                               int32_t log_row_capacity, const int32_t* h_status) {
 	NNRT_CHECK_ARG(V >= 0, "points: negative vertex count");
 	NNRT_CHECK_ARG(V == 0 || d_points, "points: null pointer");
 	NNRT_CHECK_ARG(V == 0 || d_normals, "normals: null pointer");
@@ -326,6 +327,18 @@ nnrt_status nnrt_rigid_align_point_to_plane(const float* d_points, const float* 
 	NNRT_CHECK_ARG(log_row_capacity >= iterations, "log: room for " + std::to_string(log_row_capacity) + " rows, " +
 	                                                    std::to_string(iterations) + " iterations need as many");
 	NNRT_CHECK_ARG(h_status, "status: null pointer");
+	return NNRT_OK;
+}
+
+nnrt_status nnrt_rigid_align_point_to_plane(const float* d_points, const float* d_normals, int64_t V, const float* d_target_points,
+                                            const float* d_target_normals, int32_t H, int32_t W, float fx, float fy, float cx, float cy,
+                                            const double* h_T_init, int32_t iterations, float distance_threshold, float normal_agreement_cos,
+                                            int32_t cull_back_faces, int32_t minimum_correspondence_count, double* h_T_out, double* h_log,
+                                            int32_t log_row_capacity, int32_t* h_status, void* stream) {
+	if (nnrt_status st = check_rigid_align_arguments(d_points, d_normals, V, d_target_points, d_target_normals, H, W, fx, fy, cx, cy, h_T_init,
+	                                                 iterations, distance_threshold, normal_agreement_cos, minimum_correspondence_count, h_T_out,
+	                                                 h_log, log_row_capacity, h_status))
+		return st;
 	if (V == 0) {   // nothing to align: an ordinary result
 		for (int k = 0; k < 16; k++) h_T_out[k] = h_T_init[k];
 		for (int k = 0; k < 2 * iterations; k++) h_log[k] = 0.0;
@@ -335,6 +348,61 @@ nnrt_status nnrt_rigid_align_point_to_plane(const float* d_points, const float* 
 	return launch_rigid_align(d_points, d_normals, V, d_target_points, d_target_normals, H, W, fx, fy, cx, cy, h_T_init, iterations,
 	                          distance_threshold, normal_agreement_cos, cull_back_faces, minimum_correspondence_count, h_T_out, h_log, h_status,
 	                          static_cast<hipStream_t>(stream));
+}
+
+nnrt_status nnrt_rigid_align_hybrid(const float* d_points, const float* d_normals, const float* d_colors, int64_t V, const float* d_target_points,
+                                    const float* d_target_normals, const float* d_target_intensity, int32_t H, int32_t W, float fx, float fy,
+                                    float cx, float cy, const double* h_T_init, int32_t iterations, float distance_threshold,
+                                    float normal_agreement_cos, int32_t cull_back_faces, int32_t minimum_correspondence_count,
+                                    float photometric_weight, float photometric_residual_threshold, double* h_T_out, double* h_log,
+                                    int32_t log_row_capacity, int32_t* h_status, void* stream) {
+	if (nnrt_status st = check_rigid_align_arguments(d_points, d_normals, V, d_target_points, d_target_normals, H, W, fx, fy, cx, cy, h_T_init,
+	                                                 iterations, distance_threshold, normal_agreement_cos, minimum_correspondence_count, h_T_out,
+	                                                 h_log, log_row_capacity, h_status))
+		return st;
+	NNRT_CHECK_ARG(V == 0 || d_colors, "colors: null pointer");
+	NNRT_CHECK_ARG(V == 0 || d_target_intensity, "target_intensity: null pointer");
+	NNRT_CHECK_ARG(std::isfinite(photometric_weight) && photometric_weight > 0.f, "photometric_weight must be positive and finite");
+	NNRT_CHECK_ARG(!std::isnan(photometric_residual_threshold), "photometric_residual_threshold is NaN");
+	// the host outputs are written after the inputs were read, but a log or status inside T_out (or one another) would be clobbered
+	const size_t log_bytes = sizeof(double) * 4 * static_cast<size_t>(iterations);
+	NNRT_CHECK_ARG(!ranges_overlap(h_T_out, sizeof(double) * 16, h_log, log_bytes) && !ranges_overlap(h_T_out, sizeof(double) * 16, h_status, 4) &&
+	                   !ranges_overlap(h_log, log_bytes, h_status, 4),
+	               "T_out, log and status must not overlap");
+	NNRT_CHECK_ARG(!ranges_overlap(h_T_init, sizeof(double) * 16, h_log, log_bytes) && !ranges_overlap(h_T_init, sizeof(double) * 16, h_status, 4),
+	               "log and status must not overlap T_init");
+	if (V == 0) {
+		for (int k = 0; k < 16; k++) h_T_out[k] = h_T_init[k];
+		for (int k = 0; k < 4 * iterations; k++) h_log[k] = 0.0;
+		*h_status = NNRT_RIGID_ALIGN_DEGENERATE;
+		return NNRT_OK;
+	}
+	return launch_rigid_align(d_points, d_normals, V, d_target_points, d_target_normals, H, W, fx, fy, cx, cy, h_T_init, iterations,
+	                          distance_threshold, normal_agreement_cos, cull_back_faces, minimum_correspondence_count, h_T_out, h_log, h_status,
+	                          static_cast<hipStream_t>(stream), d_colors, d_target_intensity, photometric_weight,
+	                          photometric_residual_threshold);
+}
+
+nnrt_status nnrt_intensity_from_rgb8(const uint8_t* d_rgb, int32_t height, int32_t width, float* d_out, void* stream) {
+	NNRT_CHECK_ARG(height >= 0 && width >= 0, "negative height or width");
+	const size_t pixels = static_cast<size_t>(height) * static_cast<size_t>(width);
+	if (pixels == 0) return NNRT_OK;
+	NNRT_CHECK_ARG(d_rgb, "null d_rgb");
+	NNRT_CHECK_ARG(d_out, "null d_out");
+	NNRT_CHECK_ARG(!ranges_overlap(d_rgb, 3 * pixels, d_out, sizeof(float) * pixels), "d_out must not overlap d_rgb");
+	return launch_intensity_rgb8(d_rgb, height, width, d_out, static_cast<hipStream_t>(stream));
+}
+
+nnrt_status nnrt_intensity_halve(const float* d_in, int32_t height, int32_t width, float* d_out, void* stream) {
+	NNRT_CHECK_ARG(height >= 0 && width >= 0, "negative height or width");
+	const size_t pixels = static_cast<size_t>(height) * static_cast<size_t>(width);
+	if (pixels == 0) return NNRT_OK;
+	NNRT_CHECK_ARG(d_in, "null d_in");
+	NNRT_CHECK_ARG(d_out, "null d_out");
+	const size_t out_pixels = static_cast<size_t>((height + 1) / 2) * static_cast<size_t>((width + 1) / 2);
+	NNRT_CHECK_ARG(!ranges_overlap(d_in, sizeof(float) * pixels, d_out, sizeof(float) * out_pixels),
+	               "d_out must not overlap d_in (the filter reads every pixel's neighbours)");
+	return launch_intensity_halve(d_in, height, width, d_out, static_cast<hipStream_t>(stream));
 }
 
 nnrt_status nnrt_compute_anchors_and_weights(const float* d_points, int64_t V, const float* d_nodes, int32_t N, int32_t K, float coverage,

@@ -93,11 +93,18 @@ nnrt_status launch_anchors_shortest_path(const float* points, int64_t V, const f
                                          bool edges_checked = false);
 nnrt_status check_anchor_edges(const int32_t* edges, int N, int D, hipStream_t stream);
 // rigid_align.hip: `iterations` point-to-plane Gauss-Newton steps of the rigid pose on the device (arguments checked by the
-// caller, V >= 1); h_T_out [16], h_log [iterations, 2]. Synchronizes `stream` once, at the end.
+// caller, V >= 1); h_T_out [16], h_log [iterations, 2]. Synchronizes `stream` once, at the end. With `colors` [V, 3] the
+// hybrid build runs: `target_intensity` [H, W], the photometric rows scaled by
+// `photometric_weight`, dropped beyond `photometric_residual_threshold` (<= 0: no test); h_log is then [iterations, 4].
 nnrt_status launch_rigid_align(const float* points, const float* normals, int64_t V, const float* target_points, const float* target_normals, int H,
                                int W, float fx, float fy, float cx, float cy, const double* h_T_init, int iterations, float distance_threshold,
                                float normal_agreement_cos, int cull_back_faces, int minimum_correspondence_count, double* h_T_out, double* h_log,
-                               int32_t* h_status, hipStream_t stream);
+                               int32_t* h_status, hipStream_t stream, const float* colors = nullptr, const float* target_intensity = nullptr,
+                               float photometric_weight = 0.f, float photometric_residual_threshold = 0.f);
+// photometric.hip: uint8 [H, W, 3] -> float32 luminance [H, W] in [0, 1]; [H, W] -> [ceil(H / 2), ceil(W / 2)] by the 3 x 3
+// binomial mean centred on (2 i, 2 j) (arguments checked by the caller, non-empty images)
+nnrt_status launch_intensity_rgb8(const uint8_t* rgb, int H, int W, float* out, hipStream_t stream);
+nnrt_status launch_intensity_halve(const float* in, int H, int W, float* out, hipStream_t stream);
 // vertex_path: the lane-per-vertex kernels where K <= 4 and no rows are gathered (launch_plan.hpp choose_warp_vertex)
 nnrt_status launch_warp_mesh(const float* points, const float* normals, int64_t V, const float* node_state, const int32_t* anchors,
                              const float* weights, int K, const WarpExtrinsics& E, float4* out_p, float4* out_n, float2* jrows,

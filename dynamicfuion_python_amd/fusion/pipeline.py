@@ -17,7 +17,8 @@ clusters) -- both need nothing but depth frames --, uses the DeepDeformGraph fil
 first frame (`FIRST_FRAME_LOADED_GRAPH`) or nodes supplied by the caller.
 
 Camera motion: with `FusionParameters.rigid_alignment=True` every tracked frame first aligns the previous frame's warped
-mesh rigidly to the live point image on the GPU (`nnrt.alignment.align_rigid_point_to_plane`; the reference
+mesh rigidly to the live point image on the GPU (`nnrt.alignment.align_rigid_point_to_plane`, DESIGN §17, or with
+`rigid_alignment_photometric_weight > 0` the hybrid `align_rigid_hybrid`; the reference
 calls Open3D's `rgbd_odometry_multi_scale` at pipeline.py:338-354 and drops its result) and hands the estimated
 extrinsics to the fit and to the TSDF calls, so the warp field is left with the non-rigid residual. Off (the default),
 the extrinsics stay the identity: a static camera.
@@ -66,7 +67,7 @@ from ..data.frame import FrameSequenceDataset
 from ..nnrt import geometry as G
 from ..nnrt import image_proc
 from ..nnrt import rendering
-from ..nnrt.alignment import NDC_CONSISTENT, DataCoupling, StepControl, StepObjective, align_rigid_point_to_plane
+from ..nnrt.alignment import NDC_CONSISTENT, DataCoupling, StepControl, StepObjective, align_rigid_hybrid, align_rigid_point_to_plane
 from ..warp_field.graph_warp_field import build_graph_nodes_from_depth_image, extend_warp_field, sample_graph_nodes_from_mesh
 
 
@@ -144,6 +145,12 @@ class FusionParameters:
     rigid_alignment_iteration_counts: tuple = (6, 3, 1)   # coarse to fine
     rigid_alignment_distance_threshold: float = 0.07
     rigid_alignment_normal_agreement_cos: float = 0.5
+    # the hybrid alignment (align_rigid_hybrid): above 0, and where the previous warped mesh has vertex colours,
+    # the rigid step adds a photometric term of this weight against the frame's colour image, which holds the directions
+    # point-to-plane slides along. Metres per unit of intensity; 0.1 is 5 mm of assumed depth noise over 0.05 of assumed
+    # intensity noise and has not been tuned on any sequence. 0 (the default): the geometric call, bit for bit as before.
+    rigid_alignment_photometric_weight: float = 0.0
+    rigid_alignment_photometric_residual_threshold: float = 0.0   # drop photometric rows with |rI| above this; <= 0: keep all
     # grow the motion graph over surface fused beyond its nodes' support, after every tracked frame (extend_warp_field,
     # DESIGN §18), and let non-rigid integration take newly seen surface into the model
     # (NonRigidSurfaceVoxelBlockGrid.set_non_rigid_surface_growth); off: the nodes are the first frame's for the whole run
@@ -196,6 +203,8 @@ class FrameResult:
     seconds: float = 0.0
     rigid_correspondence_count: int = 0   # rigid alignment: correspondences and RMSE of its last iteration (0 when it did not run)
     rigid_inlier_rmse: float = 0.0
+    rigid_photometric_count: int = 0      # hybrid rigid alignment: photometric rows and intensity RMSE of its last iteration
+    rigid_photometric_rmse: float = 0.0
     extrinsics: Optional[np.ndarray] = None   # a copy of the world -> camera matrix this frame was tracked and fused with
     node_count: int = 0       # nodes of the motion graph after this frame
     new_node_count: int = 0   # of them, added by this frame's warp field extension
@@ -483,13 +492,21 @@ class FusionPipeline:
             if p.rigid_alignment and self.warped_mesh is not None and self.warped_mesh.triangle_indices.shape[0] > 0:
                 # the camera's motion since the previous frame, before the non-rigid fit (pipeline.py:338-354): the warped
                 # surface as of the previous frame (world coordinates) against the live points
-                rigid = align_rigid_point_to_plane(
-                    self.warped_mesh.vertex_positions, self.warped_mesh.vertex_normals, points, self.K,
-                    initial_transformation=self.extrinsics, iteration_counts=p.rigid_alignment_iteration_counts,
-                    distance_threshold=p.rigid_alignment_distance_threshold, normal_agreement_cos=p.rigid_alignment_normal_agreement_cos)
+                schedule = dict(initial_transformation=self.extrinsics, iteration_counts=p.rigid_alignment_iteration_counts,
+                                distance_threshold=p.rigid_alignment_distance_threshold,
+                                normal_agreement_cos=p.rigid_alignment_normal_agreement_cos)
+                if p.rigid_alignment_photometric_weight > 0 and self.warped_mesh.vertex_colors is not None:
+                    rigid = align_rigid_hybrid(
+                        self.warped_mesh.vertex_positions, self.warped_mesh.vertex_normals, self.warped_mesh.vertex_colors, points, color,
+                        self.K, photometric_weight=p.rigid_alignment_photometric_weight,
+                        photometric_residual_threshold=p.rigid_alignment_photometric_residual_threshold, **schedule)
+                else:
+                    rigid = align_rigid_point_to_plane(self.warped_mesh.vertex_positions, self.warped_mesh.vertex_normals, points, self.K,
+                                                       **schedule)
                 if rigid.status == 0:
                     self.extrinsics = rigid.transformation
                 res.rigid_correspondence_count, res.rigid_inlier_rmse = rigid.correspondence_count, rigid.inlier_rmse
+                res.rigid_photometric_count, res.rigid_photometric_rmse = rigid.photometric_count, rigid.photometric_rmse
             if res.canonical_triangle_count > 0:
                 self.optimizer.optimize_graph(self.active_graph, canonical, points, extrinsics=self.extrinsics)
                 res.tracked = True

@@ -12,7 +12,8 @@ import torch
 from .. import _native as N
 from ._tensors import to_device, to_host_f64
 from .geometry import HierarchicalGraphWarpField, TriangleMesh
-from .rigid_alignment import DEGENERATE, RigidAlignmentResult, align_rigid_point_to_plane  # noqa: F401
+from .rigid_alignment import (DEGENERATE, HybridRigidAlignmentResult, RigidAlignmentResult, align_rigid_hybrid,  # noqa: F401
+                              align_rigid_point_to_plane)
 
 # nnrt_fitter_iterate_timed stage order (include/nnrt_mi355x.h, NNRT_TIMED_STAGES)
 TIMED_STAGES = ("warp", "raster", "pixel_jacobians", "node_reduce", "arap", "solve")

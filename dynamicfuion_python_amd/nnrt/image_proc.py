@@ -180,6 +180,37 @@ def bilateral_filter_depth(depth, radius: int, spatial_sigma: float, range_sigma
     return out
 
 
+def intensity_from_rgb8(color) -> torch.Tensor:
+    """uint8 [H, W, 3] RGB (numpy or torch) -> float32 [H, W] luminance in [0, 1] on the device
+    (csrc/photometric.hip): I = ((0.299 R + 0.587 G) + 0.114 B) / 255 in float32."""
+    dtype = color.dtype if isinstance(color, torch.Tensor) else np.asarray(color).dtype
+    if dtype not in (torch.uint8, np.dtype(np.uint8)) or len(color.shape) != 3 or color.shape[2] != 3:
+        raise ValueError(f"color must be a uint8 [H, W, 3] image, got {dtype} {tuple(color.shape)}")
+    N.require_gpu()
+    dev = device_of(N.current_device())
+    c = (color if isinstance(color, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(color))).to(dev).contiguous()
+    H, W = int(c.shape[0]), int(c.shape[1])
+    out = torch.empty((H, W), dtype=torch.float32, device=dev)
+    N.check(N.lib().nnrt_intensity_from_rgb8(N.ptr(c), H, W, N.ptr(out), N.stream_ptr()))
+    return out
+
+
+def halve_intensity(intensity) -> torch.Tensor:
+    """float32 [H, W] -> [ceil(H / 2), ceil(W / 2)] on the device (csrc/photometric.hip): output pixel (i, j)
+    is the 3 x 3 binomial mean, weights (1, 2, 1) / 4 per axis, centred on input pixel (2i, 2j), indices clamped to the
+    image. Level pixel (i, j) stays image pixel (2i, 2j), as when a point image is decimated by [::2, ::2]."""
+    dtype = intensity.dtype if isinstance(intensity, torch.Tensor) else np.asarray(intensity).dtype
+    if dtype not in (torch.float32, np.dtype(np.float32)) or len(intensity.shape) != 2:
+        raise ValueError(f"intensity must be a float32 [H, W] image, got {dtype} {tuple(intensity.shape)}")
+    N.require_gpu()
+    dev = device_of(N.current_device())
+    a = (intensity if isinstance(intensity, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(intensity))).to(dev).contiguous()
+    H, W = int(a.shape[0]), int(a.shape[1])
+    out = torch.empty(((H + 1) // 2, (W + 1) // 2), dtype=torch.float32, device=dev)
+    N.check(N.lib().nnrt_intensity_halve(N.ptr(a), H, W, N.ptr(out), N.stream_ptr()))
+    return out
+
+
 def backproject_depth(depth_image, fx, fy, cx, cy, depth_scale: float = 1000.0) -> torch.Tensor:
     """image_processing/__init__.py:333-344: float32 depth is taken as metres, anything else as integer units / depth_scale."""
     is_float = (isinstance(depth_image, np.ndarray) and depth_image.dtype == np.float32) or \

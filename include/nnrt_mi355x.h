@@ -610,6 +610,38 @@ nnrt_status nnrt_rigid_align_point_to_plane(const float* d_points, const float* 
                                             float distance_threshold, float normal_agreement_cos, int32_t cull_back_faces,
                                             int32_t minimum_correspondence_count, double* h_T_out, double* h_log,
                                             int32_t log_row_capacity, int32_t* h_status, void* stream);
+/* Luminance of an RGB image for the hybrid alignment below: d_rgb uint8 [height,width,3] -> d_out float32 [height,width],
+ * in float I = ((0.299 R + 0.587 G) + 0.114 B) / 255, one value per pixel in [0, 1]. NNRT_ERROR_ARGUMENT for a negative
+ * height or width, null images of a non-empty size, and images that overlap. An empty image is no error. */
+nnrt_status nnrt_intensity_from_rgb8(const uint8_t* d_rgb, int32_t height, int32_t width, float* d_out, void* stream);
+/* One level of the intensity pyramid: d_in float32 [height,width] -> d_out [ceil(height/2), ceil(width/2)]. Output pixel
+ * (i, j) is the 3 x 3 binomial mean, weights (1, 2, 1) / 4 per axis, centred on input pixel (2 i, 2 j) with indices
+ * clamped to the image, so level pixel (i, j) stays image pixel (2 i, 2 j): the convention of decimating the point image
+ * by [::2, ::2]. In float, each of the three rows first, h = ((left + 2 centre) + right) / 4, then ((h0 + 2 h1) + h2) / 4.
+ * Argument checks as for nnrt_intensity_from_rgb8. */
+nnrt_status nnrt_intensity_halve(const float* d_in, int32_t height, int32_t width, float* d_out, void* stream);
+/* nnrt_rigid_align_point_to_plane with a photometric term (the role of Method.Hybrid in Open3D's RGB-D odometry, which
+ * the reference loop's rigid step calls, apps/fusion/pipeline.py:338-354): every argument of that function with the same
+ * meaning and checks, plus the model's colours d_colors [vertex_count,3] float32 in [0, 1] and the live intensity image
+ * d_target_intensity [height,width] float32 of the same level as d_target_points. The geometric row of a vertex is
+ * decided and formed as there. A vertex whose geometric row was kept then, in float:
+ * c = (0.299 cr + 0.587 cg) + 0.114 cb, dropped unless finite; u0 = floor(u), v0 = floor(v) of its unrounded pixel (u, v),
+ * dropped unless u0 >= 0, u0 + 1 <= width - 1, v0 >= 0, v0 + 1 <= height - 1; dropped unless all four taps (v0, u0),
+ * (v0, u0 + 1), (v0 + 1, u0), (v0 + 1, u0 + 1) hold a target point with finite z > 0 and a finite intensity; with
+ * a = u - u0, b = v - v0: top = I00 + a (I01 - I00), bot = I10 + a (I11 - I10), I = top + b (bot - top),
+ * Iu = (I01 - I00) + b ((I11 - I10) - (I01 - I00)), Iv = bot - top; rI = I - c, dropped if
+ * photometric_residual_threshold > 0 and not |rI| <= it; gI = ((Iu fx) / q.z, (Iv fy) / q.z,
+ * -(((Iu fx) q.x + (Iv fy) q.y) / (q.z q.z))), row [q x gI, gI]; row and rI times photometric_weight (finite, > 0; metres
+ * per unit of intensity), dropped if any entry is not finite. The scaled row joins the same float64 normal equations
+ * after the vertex's geometric products. h_log [iterations,4] receives (correspondence count, sum r^2, photometric
+ * count, sum rI^2 unscaled). photometric_residual_threshold <= 0 disables its test; NaN is refused. No atomics, the
+ * same fixed summation order: bit-reproducible. vertex_count == 0: DEGENERATE, h_T_out = h_T_init, a zero log. */
+nnrt_status nnrt_rigid_align_hybrid(const float* d_points, const float* d_normals, const float* d_colors, int64_t vertex_count,
+                                    const float* d_target_points, const float* d_target_normals, const float* d_target_intensity,
+                                    int32_t height, int32_t width, float fx, float fy, float cx, float cy, const double* h_T_init,
+                                    int32_t iterations, float distance_threshold, float normal_agreement_cos, int32_t cull_back_faces,
+                                    int32_t minimum_correspondence_count, float photometric_weight, float photometric_residual_threshold,
+                                    double* h_T_out, double* h_log, int32_t log_row_capacity, int32_t* h_status, void* stream);
 /* nnrt.core.matmul3d(array_of_matrices_a, array_of_matrices_b) (cpp/pybind/core/core.cpp:32 -> cpp/core/linalg/Matmul3D.cpp:25-83):
  * d_c [batch, m, n] = d_a [batch, m, k] x d_b [batch, k, n] per batch entry, float32 row-major (n = 1: array of vectors). */
 nnrt_status nnrt_matmul3d(const float* d_a, const float* d_b, int64_t batch, int32_t m, int32_t k, int32_t n, float* d_c, void* stream);
