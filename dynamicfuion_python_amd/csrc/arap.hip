@@ -401,6 +401,54 @@ StemSchurLists build_stem_schur_lists(const int32_t* edges, int E, int n0, int N
 	return L;
 }
 
+nnrt_status ArrowheadStructure::build(const int32_t* edges, int E_, int n0_, int N_, const float* corner_positions, bool with_incidences) {
+	N = N_;
+	n0 = n0_;
+	E = E_;
+	moved = false;
+	const uint64_t plan = corner.generation;
+	nnrt_status st = corner.prepare(edges, E, n0, N, corner_positions);   // (a failure has bumped the generation)
+	moved = corner.generation != plan;
+	if (st) return st;
+	if ((st = ensure(dinv, 36 * static_cast<size_t>(std::max(n0, 1)), &moved)) || (st = ensure(dinv_b, 36 * static_cast<size_t>(std::max(E, 1)), &moved))) return st;
+	// (each table is uploaded as soon as it is built: the next one's host work then runs beside the copy)
+	const StemEdgeCsr stem = build_stem_edge_csr(edges, E, n0);
+	if ((st = upload(edge_offsets, stem.offsets, &moved)) || (st = upload(edge_list, stem.list, &moved))) return st;
+	if (with_incidences) {
+		// by node (source: 2 e, target: 2 e + 1), and the slot of each incidence in that order: the ARAP edge kernel writes
+		// its two nodes' terms there (node-major, so k_arrow_prepare reads each node's terms contiguously, without the list)
+		std::vector<int> off, list;
+		incidence_csr(edges, E, N, off, list);
+		if ((st = upload(inc_off, off, &moved)) || (st = upload(inc_list, list, &moved)) || (st = upload(inc_slot, incidence_slots(list), &moved))) return st;
+	}
+	const StemSchurLists sl = build_stem_schur_lists(edges, E, n0, N);
+	targets = static_cast<int>(sl.tgt_ab.size());
+	if ((st = upload(tgt_off, sl.tgt_off, &moved)) || (st = upload(tgt_ab, sl.tgt_ab, &moved)) || (st = upload(pairs, sl.pairs, &moved)) ||
+	    (st = upload(rhs_off, sl.rhs_off, &moved)) || (st = upload(rhs_edges, sl.rhs_edges, &moved)))
+		return st;
+	return NNRT_OK;
+}
+
+void ArrowheadStructure::bind(ArrowheadWorkspace& ws) const {
+	ws.N = N;
+	ws.n0 = n0;
+	ws.E = E;
+	ws.m = 6 * (N - n0);
+	ws.corner = &corner;
+	ws.dinv = dinv.ptr;
+	ws.dinv_b = dinv_b.ptr;
+	ws.edge_offsets = edge_offsets.ptr;
+	ws.edge_list = edge_list.ptr;
+	ws.inc_off = inc_off.ptr;
+	ws.inc_list = inc_list.ptr;
+	ws.targets = targets;
+	ws.tgt_off = tgt_off.ptr;
+	ws.tgt_ab = tgt_ab.ptr;
+	ws.pairs = pairs.ptr;
+	ws.rhs_off = rhs_off.ptr;
+	ws.rhs_edges = rhs_edges.ptr;
+}
+
 // ---- stem back-substitution: x_D = D^-1 (b_D - B x_C) (arrow_device.hpp: arrow_back_node) ----
 // gate (refinement; nullable): mode 1 = the first pass of a gated refinement: x_i always, the update only when the
 // refinement does not run, else the stem residual r_i -> res; mode 2 = the refinement's last pass: runs only when it does.

@@ -1085,38 +1085,24 @@ nnrt_status nnrt_invert_triangular_blocks(const float* d_blocks, int32_t block_c
 } // extern "C"
 
 namespace {
-// Everything the arrowhead solve derives from the wing structure alone -- the stem CSR, the target-grouped Schur lists,
-// the tile-sparse corner plan and its buffers, the per-call scratch -- kept per (device, N, n0, coordinates) so a
+// Everything the arrowhead solve derives from the wing structure alone (ArrowheadStructure, which the fitter holds too)
+// and the call's error word, kept per (device, N, n0, coordinates) so a
 // repeated structure (a fixed hierarchy, solved every iteration) skips the host planning and the allocations. An entry
 // is owned by one call at a time (taken out of the pool, returned after the call has synchronised its stream), so
 // concurrent calls never share device scratch; the pool holds the ARROW_POOL_MAX most recently used structures.
 struct ArrowheadPlan {
-	int device = -1, N = 0, n0 = 0, E = 0, targets = 0;
+	int device = -1;
 	std::vector<int32_t> coords;
-	CornerSolver corner;
-	DeviceBuffer<float> dinv, dinv_b;
-	DeviceBuffer<int> edge_offsets, edge_list, flag, tgt_off, rhs_off, rhs_edges;
-	DeviceBuffer<int2> tgt_ab, pairs;
+	ArrowheadStructure arrow;
+	DeviceBuffer<int> flag;
 	bool matches(int dev, int32_t n, int32_t base, const std::vector<int32_t>& c) const {
-		return device == dev && N == n && n0 == base && coords == c;
+		return device == dev && arrow.N == n && arrow.n0 == base && coords == c;
 	}
 	nnrt_status build(int dev, int32_t n, int32_t base, std::vector<int32_t> c) {
 		device = dev;
-		N = n;
-		n0 = base;
 		coords = std::move(c);
-		E = static_cast<int>(coords.size() / 2);
-		const StemEdgeCsr stem = build_stem_edge_csr(coords.data(), E, n0);
-		nnrt_status st = corner.prepare(coords.data(), E, n0, N);
-		if (st) return st;
-		const StemSchurLists sl = build_stem_schur_lists(coords.data(), E, n0, N);
-		targets = static_cast<int>(sl.tgt_ab.size());
-		if ((st = dinv.ensure(36 * static_cast<size_t>(std::max(n0, 1)))) || (st = dinv_b.ensure(36 * static_cast<size_t>(std::max(E, 1)))) ||
-		    (st = flag.ensure(1)) || (st = upload(edge_offsets, stem.offsets)) || (st = upload(edge_list, stem.list)) || (st = upload(tgt_off, sl.tgt_off)) ||
-		    (st = upload(tgt_ab, sl.tgt_ab)) || (st = upload(pairs, sl.pairs)) || (st = upload(rhs_off, sl.rhs_off)) ||
-		    (st = upload(rhs_edges, sl.rhs_edges)))
-			return st;
-		return NNRT_OK;
+		const nnrt_status st = arrow.build(coords.data(), static_cast<int>(coords.size() / 2), base, n, nullptr, false);
+		return st ? st : flag.ensure(1);
 	}
 };
 constexpr size_t ARROW_POOL_MAX = 4;
@@ -1169,21 +1155,7 @@ nnrt_status nnrt_solve_block_sparse_arrowhead_cholesky(const float* d_diag, cons
 		if ((st = plan->build(device, N, n0, std::move(coords)))) return st;
 	}
 	ArrowheadWorkspace ws;
-	ws.N = N;
-	ws.n0 = n0;
-	ws.E = E;
-	ws.m = 6 * (N - n0);
-	ws.corner = &plan->corner;
-	ws.dinv = plan->dinv.ptr;
-	ws.dinv_b = plan->dinv_b.ptr;
-	ws.edge_offsets = plan->edge_offsets.ptr;
-	ws.edge_list = plan->edge_list.ptr;
-	ws.targets = plan->targets;
-	ws.tgt_off = plan->tgt_off.ptr;
-	ws.tgt_ab = plan->tgt_ab.ptr;
-	ws.pairs = plan->pairs.ptr;
-	ws.rhs_off = plan->rhs_off.ptr;
-	ws.rhs_edges = plan->rhs_edges.ptr;
+	plan->arrow.bind(ws);
 	ws.diag = const_cast<float*>(d_diag);
 	ws.rhs = const_cast<float*>(d_b);
 	ws.x = d_x;

@@ -32,6 +32,7 @@
 #include <tuple>
 
 #include "arrow_device.hpp"
+#include "launch_plan.hpp"
 
 namespace nnrt {
 
@@ -2075,11 +2076,7 @@ __global__ __launch_bounds__(WT) void k_corner_walk(CornerWalkArgs a) {
 // development switches (A/B builds without rebuilding): NNRT_CORNER_WALK=1 enables the single-workgroup walk for small
 // corners (round 4's default; the dataflow launch measured faster at C1_ARAP, 7,636 vs 7,500 GN it/s, and equal at
 // C2_ARAP in round 5), NNRT_CORNER_FLOW=0 disables the dataflow substitution launch, NNRT_CORNER_TRIM=0 the
-// padding-trimmed eliminations
-static bool env_flag(const char* name, bool dflt) {
-	const char* v = std::getenv(name);
-	return v ? std::strcmp(v, "0") != 0 : dflt;
-}
+// padding-trimmed eliminations (env_flag, launch_plan.hpp)
 
 // The dynamic-LDS cap of k_corner_walk is a property of the kernel on each device, not of a plan: several plans with
 // different walk_lds are live at once (every fitter, the arrowhead pool), so the cap is raised once per device to the

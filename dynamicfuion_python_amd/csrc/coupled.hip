@@ -55,14 +55,6 @@ __global__ __launch_bounds__(256) void k_coupled_assemble(const double* __restri
 	pair_blocks[t] = v;
 }
 
-template <class Buf, class Vec>
-nnrt_status upload_moved(Buf& buf, const Vec& host, bool* moved) {
-	const auto* old = buf.ptr;
-	const nnrt_status st = upload(buf, host);
-	if (buf.ptr != old) *moved = true;
-	return st;
-}
-
 } // namespace
 
 nnrt_status build_pair_structure(PairStructure& ps, const uint32_t* face_nodes, int64_t F, int K, const int32_t* d_edges,
@@ -103,9 +95,9 @@ nnrt_status build_pair_structure(PairStructure& ps, const uint32_t* face_nodes, 
 		set_error("coupled data term: " + err);
 		return NNRT_ERROR_ARGUMENT;
 	}
-	if ((st = upload_moved(ps.pairs, ps.h_pairs, moved)) || (st = upload_moved(ps.row_off, t.row_off, moved)) ||
-	    (st = upload_moved(ps.edge_off, t.edge_off, moved)) || (st = upload_moved(ps.edge_list, t.edge_list, moved)) ||
-	    (st = upload_moved(ps.inc_off, t.inc_off, moved)) || (st = upload_moved(ps.inc_list, t.inc_list, moved)))
+	if ((st = upload(ps.pairs, ps.h_pairs, moved)) || (st = upload(ps.row_off, t.row_off, moved)) ||
+	    (st = upload(ps.edge_off, t.edge_off, moved)) || (st = upload(ps.edge_list, t.edge_list, moved)) ||
+	    (st = upload(ps.inc_off, t.inc_off, moved)) || (st = upload(ps.inc_list, t.inc_list, moved)))
 		return st;
 	return NNRT_OK;
 }

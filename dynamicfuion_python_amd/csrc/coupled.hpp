@@ -17,6 +17,21 @@ struct PairStructure {
 	DeviceBuffer<uint64_t> keys, keys_sorted;
 	DeviceBuffer<int> d_count;
 	DeviceBuffer<uint8_t> tmp;
+	// The coupled solve is the arrowhead solve over the pairs with an empty stem (arrow base 0: every node is in the
+	// corner, which `corner` plans over h_pairs), a different shape from ArrowheadStructure's: no stem blocks, no Schur
+	// lists. The structure-derived fields of its workspace; no_dinv [>= 1] and no_edges [1] = {0} stand for the stem's
+	// buffers, which no launch reads past.
+	void bind(ArrowheadWorkspace& ws, const CornerSolver& corner, int N, float* no_dinv, int* no_edges) const {
+		ws.N = N;
+		ws.n0 = 0;
+		ws.E = M;
+		ws.m = 6 * N;
+		ws.corner = &corner;
+		ws.dinv = ws.dinv_b = no_dinv;
+		ws.edge_offsets = ws.edge_list = no_edges;
+		ws.inc_off = inc_off.ptr;
+		ws.inc_list = inc_list.ptr;
+	}
 };
 // builds ps on stream s (device: keys, sort, unique; one host round trip for the count and the coordinates, which the
 // solver's plan needs; then the host tables). h_edges / d_edges: the hierarchy's edges [E, 2] (virtual order).

@@ -46,6 +46,25 @@ inline int find_pair(const std::vector<int>& row_off, const int32_t* pairs, int 
 	return -1;
 }
 
+// CSR of the incidences of M index pairs [M, 2] by node: off [N + 1] into list [2 M], which holds 2 s + t for entry t of
+// pair s (t = 1: the node is the pair's second index), ascending s per node. Every index must lie in [0, N). The pairs of
+// the coupled data term, and the ARAP edges of the arrowhead solve (source 2 e, target 2 e + 1), are both listed this way.
+inline void incidence_csr(const int32_t* pairs, int M, int N, std::vector<int>& off, std::vector<int>& list) {
+	off.assign(static_cast<size_t>(N) + 1, 0);
+	for (size_t q = 0; q < 2 * static_cast<size_t>(M); q++) off[static_cast<size_t>(pairs[q]) + 1]++;
+	for (int n = 0; n < N; n++) off[static_cast<size_t>(n) + 1] += off[static_cast<size_t>(n)];
+	list.assign(2 * static_cast<size_t>(M), 0);
+	std::vector<int> fill(off.begin(), off.end() - 1);
+	for (size_t q = 0; q < 2 * static_cast<size_t>(M); q++) list[static_cast<size_t>(fill[static_cast<size_t>(pairs[q])]++)] = static_cast<int>(q);
+}
+
+// the inverse of such a list: slot[2 s + t] is where the incidence stands in it
+inline std::vector<int> incidence_slots(const std::vector<int>& list) {
+	std::vector<int> slot(list.size());
+	for (size_t q = 0; q < list.size(); q++) slot[static_cast<size_t>(list[q])] = static_cast<int>(q);
+	return slot;
+}
+
 // pairs [M, 2] strictly ascending in (i, j) with 0 <= i < j < N; edges [E, 2] (virtual order), each of which must lie on a
 // pair. false + *err on malformed input (nothing is indexed out of range).
 inline bool build_pair_tables(const int32_t* pairs, int M, int N, const int32_t* edges, int E, PairTables& t, std::string* err) {
@@ -55,7 +74,6 @@ inline bool build_pair_tables(const int32_t* pairs, int M, int N, const int32_t*
 	};
 	if (M < 0 || N < 0 || E < 0) return fail("negative count");
 	t.row_off.assign(static_cast<size_t>(N) + 1, 0);
-	t.inc_off.assign(static_cast<size_t>(N) + 1, 0);
 	for (int s = 0; s < M; s++) {
 		const int i = pairs[2 * static_cast<size_t>(s)], j = pairs[2 * static_cast<size_t>(s) + 1];
 		if (i < 0 || j <= i || j >= N) return fail("pair outside 0 <= i < j < node count");
@@ -64,21 +82,9 @@ inline bool build_pair_tables(const int32_t* pairs, int M, int N, const int32_t*
 			if (pi > i || (pi == i && pj >= j)) return fail("pair list not strictly ascending");
 		}
 		t.row_off[static_cast<size_t>(i) + 1]++;
-		t.inc_off[static_cast<size_t>(i) + 1]++;
-		t.inc_off[static_cast<size_t>(j) + 1]++;
 	}
-	for (int n = 0; n < N; n++) {
-		t.row_off[static_cast<size_t>(n) + 1] += t.row_off[static_cast<size_t>(n)];
-		t.inc_off[static_cast<size_t>(n) + 1] += t.inc_off[static_cast<size_t>(n)];
-	}
-	t.inc_list.assign(2 * static_cast<size_t>(M), 0);
-	{
-		std::vector<int> fill(t.inc_off.begin(), t.inc_off.end() - 1);
-		for (int s = 0; s < M; s++) {
-			t.inc_list[static_cast<size_t>(fill[static_cast<size_t>(pairs[2 * static_cast<size_t>(s)])]++)] = 2 * s;
-			t.inc_list[static_cast<size_t>(fill[static_cast<size_t>(pairs[2 * static_cast<size_t>(s) + 1])]++)] = 2 * s + 1;
-		}
-	}
+	for (int n = 0; n < N; n++) t.row_off[static_cast<size_t>(n) + 1] += t.row_off[static_cast<size_t>(n)];
+	incidence_csr(pairs, M, N, t.inc_off, t.inc_list);
 	// the ARAP edges on each pair, ascending edge index per pair
 	std::vector<int> slot(static_cast<size_t>(E), 0);
 	t.edge_off.assign(static_cast<size_t>(M) + 1, 0);

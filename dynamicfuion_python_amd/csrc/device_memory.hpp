@@ -72,6 +72,23 @@ nnrt_status upload(DeviceBuffer<T>& buf, const std::vector<T>& host) {
 	return NNRT_OK;
 }
 
+// The same two for buffers whose address a captured graph may hold: *moved is set when the pointer changed, a pointer
+// lost to a failed allocation included (it is never cleared here, so one flag can watch many buffers).
+template <typename T>
+nnrt_status ensure(DeviceBuffer<T>& buf, size_t n, bool* moved) {
+	const T* old = buf.ptr;
+	const nnrt_status st = buf.ensure(n);
+	if (buf.ptr != old) *moved = true;
+	return st;
+}
+template <typename T>
+nnrt_status upload(DeviceBuffer<T>& buf, const std::vector<T>& host, bool* moved) {
+	const T* old = buf.ptr;
+	const nnrt_status st = upload(buf, host);
+	if (buf.ptr != old) *moved = true;
+	return st;
+}
+
 template <typename T>
 struct StreamScratch {
 	T* ptr = nullptr;

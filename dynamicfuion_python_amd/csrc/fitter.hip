@@ -74,11 +74,9 @@ struct nnrt_fitter {
 	DeviceBuffer<float> updates, gradient, hessian;
 	DeviceBuffer<int> error_flag;
 	// ARAP / arrowhead
-	DeviceBuffer<float> wing, edge_residuals, a_diag, a_dinv, a_dinvb, a_rhs, a_x, a_res, a_dx;
-	CornerSolver corner;   // Schur corner of the arrowhead solve (tile-sparse Cholesky plan + storage)
-	DeviceBuffer<int> a_offsets, a_list, a_tgt_off, a_rhs_off, a_rhs_edges, a_inc_off, a_inc_list, a_inc_slot;
-	DeviceBuffer<int2> a_tgt_ab, a_pairs;
-	ArrowheadWorkspace aw;
+	DeviceBuffer<float> wing, edge_residuals;
+	ArrowheadStructure arap;   // what the solve derives from the hierarchy's edges, the Schur corner's plan and storage included
+	DeviceBuffer<float> a_diag, a_rhs, a_x, a_res, a_dx;   // the solve's vectors (the coupled mode's too)
 	float refine_ratio = NNRT_REFINE_PIVOT_RATIO;   // refinement gate threshold (nnrt_fitter_set_refine_ratio)
 	float refine_ratio_used = NNRT_REFINE_PIVOT_RATIO;   // the threshold the last launched iterations ran with (refine_info)
 	// nnrt_fitter_set_robust_options: the form the Tukey / Huber penalties take where the parameters enable them, and
@@ -95,7 +93,6 @@ struct nnrt_fitter {
 	DeviceBuffer<int> zero_inc;         // [N + 1] zeros: the prepare launch's incidence offsets without a hierarchy
 	DeviceBuffer<int> c_edge_off;       // [1] the empty stem's edge CSR
 	DeviceBuffer<float> c_dinv;         // [1] (no stem blocks)
-	ArrowheadWorkspace cw;
 	// nnrt_fitter_set_step_control: the settings, and the state machine's device state (allocated by
 	// prepare() while the mode is on)
 	bool step_on = false;
@@ -339,7 +336,7 @@ FitPixelArgs fit_pixel_args(const nnrt_fitter* ft, const nnrt_warp_field* wf, co
 		aa.node_weights = wf->node_weights.ptr;
 		aa.node_state = state_in;
 		aa.edge_jr = ft->edge_jr.ptr;
-		aa.inc_slot = ft->a_inc_slot.ptr;
+		aa.inc_slot = ft->arap.inc_slot.ptr;
 		aa.wing = ft->wing.ptr;
 		aa.edge_residuals = ft->edge_residuals.ptr;
 		aa.error_flag = ft->error_flag.ptr;
@@ -410,6 +407,30 @@ SolveArgsT<Lm> solve_args(const nnrt_fitter* ft, const nnrt_warp_field* wf, cons
 	return sa;
 }
 
+// the two tile-sparse solves' workspaces, built where they are launched: the structure-derived fields from the structure's
+// bind(), the vectors and the two launch settings from the fitter (their only home)
+ArrowheadWorkspace with_solve_vectors(const nnrt_fitter* ft, ArrowheadWorkspace ws) {
+	ws.diag = ft->a_diag.ptr;
+	ws.rhs = ft->a_rhs.ptr;
+	ws.x = ft->a_x.ptr;
+	ws.res = ft->a_res.ptr;
+	ws.dx = ft->a_dx.ptr;
+	ws.refine = NNRT_ARAP_REFINE != 0;
+	ws.refine_ratio = ft->refine_ratio;
+	ws.guard_zero_rotation = ft->guard_zero_rotation;
+	return ws;
+}
+ArrowheadWorkspace arrowhead_workspace(const nnrt_fitter* ft) {
+	ArrowheadWorkspace ws;
+	ft->arap.bind(ws);
+	return with_solve_vectors(ft, ws);
+}
+ArrowheadWorkspace coupled_workspace(const nnrt_fitter* ft) {
+	ArrowheadWorkspace ws;
+	ft->ps.bind(ws, ft->pair_corner, ft->key.N, ft->c_dinv.ptr, ft->c_edge_off.ptr);
+	return with_solve_vectors(ft, ws);
+}
+
 nnrt_status enqueue_iteration(nnrt_fitter* ft, const nnrt_warp_field* wf, int mode, hipStream_t s, hipEvent_t* marks = nullptr,
                               bool from_identity = false, const float* state_in = nullptr, unsigned stages = STAGE_ALL) {
 	if (!state_in) state_in = wf->state.ptr;
@@ -457,18 +478,15 @@ nnrt_status enqueue_iteration(nnrt_fitter* ft, const nnrt_warp_field* wf, int mo
 		// diagonal blocks (data + ARAP + LM) and right-hand side as on the arrowhead path, the pair blocks, then the
 		// tile-sparse solve with arrow base 0 and the node updates
 		if ((st = launch_arrow_prepare(ft->key.N, ft->p.preconditioning_dampening_factor, ft->acc.ptr,
-		                               ft->key.E > 0 ? ft->a_inc_off.ptr : ft->zero_inc.ptr, ft->edge_jr.ptr, ft->a_diag.ptr, ft->a_rhs.ptr,
+		                               ft->key.E > 0 ? ft->arap.inc_off.ptr : ft->zero_inc.ptr, ft->edge_jr.ptr, ft->a_diag.ptr, ft->a_rhs.ptr,
 		                               ft->gradient.ptr, ft->hessian.ptr, s, lm_device)) ||
 		    (st = launch_coupled_assemble(ft->pair_acc.ptr, ft->ps.M, ft->ps.edge_off.ptr, ft->ps.edge_list.ptr, ft->wing.ptr, ft->pair_blocks.ptr, s)))
 			return st;
-		ArrowheadWorkspace cw = ft->cw;
-		cw.refine_ratio = ft->refine_ratio;
-		cw.guard_zero_rotation = ft->guard_zero_rotation;
-		if ((st = arrowhead_solve_core(cw, ft->ps.pairs.ptr, ft->pair_blocks.ptr, ft->error_flag.ptr, s, false, wf->state.ptr, ft->updates.ptr, state_in)))
+		if ((st = arrowhead_solve_core(coupled_workspace(ft), ft->ps.pairs.ptr, ft->pair_blocks.ptr, ft->error_flag.ptr, s, false, wf->state.ptr, ft->updates.ptr, state_in)))
 			return st;
 	} else if (ft->key.E > 0) {
 		const float lm = ft->p.preconditioning_dampening_factor;
-		if ((st = launch_arrowhead_iteration(ft->aw, ft->acc.ptr, lm, wf->edges.ptr, ft->wing.ptr, wf->state.ptr, ft->edge_jr.ptr,
+		if ((st = launch_arrowhead_iteration(arrowhead_workspace(ft), ft->acc.ptr, lm, wf->edges.ptr, ft->wing.ptr, wf->state.ptr, ft->edge_jr.ptr,
 		                                     ft->updates.ptr, ft->gradient.ptr, ft->hessian.ptr, ft->error_flag.ptr, s, state_in, lm_device)))
 			return st;
 	} else if (step) {
@@ -559,277 +577,238 @@ struct FrameReference {
 	float depth_scale = 1.f;
 };
 
-nnrt_status prepare_frame(nnrt_fitter* ft, nnrt_warp_field* wf, const float* d_vertices, const float* d_normals, int64_t V,
-                          const int64_t* d_faces, int64_t F, const FrameReference& ref, int32_t H, int32_t W, const double* h_K,
-                          const double* h_E, void* stream) {
-	NNRT_CHECK_ARG(ft && wf && d_vertices && d_normals && d_faces && (ref.depth || ref.points) && h_K, "null pointer");
-	NNRT_CHECK_ARG(V > 0 && F > 0 && H > 0 && W > 0, "empty mesh or image");
-	NNRT_CHECK_ARG(V < (int64_t(1) << 31) && F < (int64_t(1) << 31), "mesh too large for int32 indexing");
-	NNRT_CHECK_ARG(ref.depth_scale > 0.f, "depth_scale must be positive");
+// what prepare() is given besides the fitter, the warp field and the stream
+struct FrameInputs {
+	const float *vertices, *normals;
+	int64_t V;
+	const int64_t* faces;
+	int64_t F;
+	FrameReference ref;
+	int32_t H, W;
+	const double *K, *E;
+};
+
+// prepare()'s steps, in calling order (prepare_frame below); static: this unnamed namespace stands inside extern "C", where
+// a function's unmangled name would be exported. The refusals that leave the fitter as it was:
+static nnrt_status check_frame_arguments(const nnrt_fitter* ft, const nnrt_warp_field* wf, const FrameInputs& in) {
+	NNRT_CHECK_ARG(ft && wf && in.vertices && in.normals && in.faces && (in.ref.depth || in.ref.points) && in.K, "null pointer");
+	NNRT_CHECK_ARG(in.V > 0 && in.F > 0 && in.H > 0 && in.W > 0, "empty mesh or image");
+	NNRT_CHECK_ARG(in.V < (int64_t(1) << 31) && in.F < (int64_t(1) << 31), "mesh too large for int32 indexing");
+	NNRT_CHECK_ARG(in.ref.depth_scale > 0.f, "depth_scale must be positive");
 	NNRT_CHECK_ARG(wf->device == ft->device, "the warp field and the fitter live on different devices");
-	DeviceGuard guard(ft->device);
-	// until this frame is fully prepared the fitter is not: a failure below (allocation, corner plan) leaves iterate()
-	// refusing rather than replaying graphs over buffers that may have been released
-	ft->prepared = false;
-	hipStream_t us = static_cast<hipStream_t>(stream);
-	const int64_t P = static_cast<int64_t>(H) * W;
-	const int N = wf->N, K = wf->anchor_count, E = wf->E();
-	NNRT_CHECK_ARG(N >= K, "the warp field has fewer nodes than anchors per vertex");
-	NNRT_CHECK_ARG(N < FACE_NODE_MAX_NODES, "node count exceeds the face-node table's 20-bit node field");
-	NNRT_CHECK_ARG(ft->graph_degree == 0 || ft->graph_nodes == N, "the anchor graph's node_count differs from the warp field's");
-	if (E > 0) {
+	return NNRT_OK;
+}
+
+// and those of a warp field this fitter cannot take (by then the fitter counts as unprepared)
+static nnrt_status check_frame_warp_field(const nnrt_fitter* ft, const nnrt_warp_field* wf) {
+	NNRT_CHECK_ARG(wf->N >= wf->anchor_count, "the warp field has fewer nodes than anchors per vertex");
+	NNRT_CHECK_ARG(wf->N < FACE_NODE_MAX_NODES, "node count exceeds the face-node table's 20-bit node field");
+	NNRT_CHECK_ARG(ft->graph_degree == 0 || ft->graph_nodes == wf->N, "the anchor graph's node_count differs from the warp field's");
+	if (wf->E() > 0) {
 		for (int i = 0; i < ft->p.iteration_mode_count; i++)
 			if (ft->p.iteration_modes[i] != NNRT_ITERATION_ALL) {
 				set_error("the regularized (ARAP) solve supports IterationMode ALL only (reference A15: the ARAP Hessian is 6x6-only)");
 				return NNRT_ERROR_UNSUPPORTED;
 			}
 	}
-	// This frame's key. The launch choices come first: they size the order tables below.
+	return NNRT_OK;
+}
+
+// This frame's key, as far as it is known before any device work: the two solver plans' generations and the coupled
+// mode's pair count are entered by the steps that build them, before the key is compared.
+static FrameKey make_frame_key(const nnrt_fitter* ft, const nnrt_warp_field* wf, const FrameInputs& in) {
 	int cus = 0;
 	if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, ft->device) != hipSuccess || cus <= 0) cus = 256;
 	FrameKey key;
 	std::memset(&key, 0, sizeof(key));
-	key.V = V;
-	key.F = F;
+	key.V = in.V;
+	key.F = in.F;
 	key.wf = wf;
 	key.wf_id = wf->id;
-	key.H = H;
-	key.W = W;
-	key.N = N;
-	key.K = K;
-	key.E = E;
-	key.n0 = wf->h.layer_counts.empty() ? N : wf->h.layer_counts[0];
+	key.H = in.H;
+	key.W = in.W;
+	key.N = wf->N;
+	key.K = wf->anchor_count;
+	key.E = wf->E();
+	key.n0 = wf->h.layer_counts.empty() ? wf->N : wf->h.layer_counts[0];
 	key.quad_slots = 4 * 4 * cus;
-	key.ndc = make_ndc_setup(h_K, H, W, ft->p.ndc_convention == NNRT_NDC_CONSISTENT);
-	key.pix = pixel_camera(h_K);
-	key.extr = make_extrinsics(h_E);
+	key.ndc = make_ndc_setup(in.K, in.H, in.W, ft->p.ndc_convention == NNRT_NDC_CONSISTENT);
+	key.pix = pixel_camera(in.K);
+	key.extr = make_extrinsics(in.E);
 	key.coupled = ft->data_coupling == NNRT_DATA_COUPLED;
-	// the pair structure is known only after the device has built it (below): until then the last frame's
-	key.pair_generation = key.coupled ? ft->key.pair_generation : 0;
-	key.M = key.coupled ? ft->key.M : 0;
-	key.launch = choose_launches(read_launch_switches(), V, F, H, W, N, K, cus, fit_pixels_tile_order_supported());
-	// (re)allocate. Captured graphs bake every buffer's address into their kernel arguments, so every allocation of the
-	// frame goes through these two, and a buffer that moved (or was lost to a failed allocation) drops the graphs.
+	key.launch = choose_launches(read_launch_switches(), in.V, in.F, in.H, in.W, key.N, key.K, cus, fit_pixels_tile_order_supported());
+	return key;
+}
+
+// Graph invalidation's one owner in prepare(). Captured graphs bake every buffer's address and the frame's key into
+// their kernel arguments, so a step that moves or loses a buffer or re-plans a solver sets `stale`, as does a key that
+// differs from the last frame's; the graphs are dropped once, on every path out, the error returns included.
+struct GraphInvalidation {
+	nnrt_fitter* ft;
+	bool stale = false;
+	explicit GraphInvalidation(nnrt_fitter* f) : ft(f) {}
+	GraphInvalidation(const GraphInvalidation&) = delete;
+	GraphInvalidation& operator=(const GraphInvalidation&) = delete;
+	~GraphInvalidation() {
+		if (stale) ft->drop_graphs();
+	}
+};
+
+// (re)allocates the frame's buffers, grouped by what needs them; every allocation of the frame reports a moved pointer
+static nnrt_status allocate_frame(nnrt_fitter* ft, const FrameKey& key, bool* moved) {
+	const size_t V = static_cast<size_t>(key.V), F = static_cast<size_t>(key.F), N = static_cast<size_t>(key.N), K = static_cast<size_t>(key.K);
+	const size_t E = static_cast<size_t>(key.E), P = static_cast<size_t>(key.H) * static_cast<size_t>(key.W);
 	nnrt_status st;
-	auto ensure = [&](auto& buf, size_t n) {
-		const auto* old = buf.ptr;
-		const nnrt_status r = buf.ensure(n);
-		if (buf.ptr != old) ft->drop_graphs();
-		return r;
-	};
-	auto upload_to = [&](auto& buf, const auto& host) {
-		const auto* old = buf.ptr;
-		const nnrt_status r = upload(buf, host);
-		if (buf.ptr != old) ft->drop_graphs();
-		return r;
-	};
-	if ((st = ensure(ft->mesh_p, 3 * V)) || (st = ensure(ft->mesh_n, 3 * V)) || (st = ensure(ft->faces4, F)) ||
-	    (st = ensure(ft->anchors, static_cast<size_t>(V) * K)) || (st = ensure(ft->weights, static_cast<size_t>(V) * K)) ||
-	    (st = ensure(ft->face_nodes, static_cast<size_t>(F) * face_node_slots(K))) ||
-	    (st = ensure(ft->wpos, V)) || (st = ensure(ft->wnrm, V)) ||
-	    (st = ensure(ft->jrows, NNRT_GATHER_ROWS ? 3 * static_cast<size_t>(V) * K : 1)) || (st = ensure(ft->mesh_p4, V)) ||
-	    (st = ensure(ft->mesh_n4, V)) || (st = ensure(ft->anchors16, K == 4 && N < 65535 ? static_cast<size_t>(V) : 1)) ||
-	    (st = ensure(ft->ref_points, P)) || (st = ensure(ft->records, 4 * P)) || (st = ensure(ft->keys, P)) ||
-	    (st = ensure(ft->residuals, P)) || (st = ensure(ft->residual_mask, P)) || (st = ensure(ft->pixel_face, P)) ||
-	    (st = ensure(ft->acc, static_cast<size_t>(N) * ACC_STRIDE)) ||
-	    (st = ensure(ft->updates, static_cast<size_t>(N) * 6)) || (st = ensure(ft->gradient, static_cast<size_t>(N) * 6)) ||
-	    (st = ensure(ft->hessian, static_cast<size_t>(N) * 36)))
+	// every frame
+	if ((st = ensure(ft->mesh_p, 3 * V, moved)) || (st = ensure(ft->mesh_n, 3 * V, moved)) || (st = ensure(ft->faces4, F, moved)) ||
+	    (st = ensure(ft->anchors, V * K, moved)) || (st = ensure(ft->weights, V * K, moved)) ||
+	    (st = ensure(ft->face_nodes, F * face_node_slots(key.K), moved)) || (st = ensure(ft->wpos, V, moved)) || (st = ensure(ft->wnrm, V, moved)) ||
+	    (st = ensure(ft->jrows, NNRT_GATHER_ROWS ? 3 * V * K : 1, moved)) || (st = ensure(ft->mesh_p4, V, moved)) ||
+	    (st = ensure(ft->mesh_n4, V, moved)) || (st = ensure(ft->anchors16, key.K == 4 && key.N < 65535 ? V : 1, moved)) ||
+	    (st = ensure(ft->ref_points, P, moved)) || (st = ensure(ft->records, 4 * P, moved)) || (st = ensure(ft->keys, P, moved)) ||
+	    (st = ensure(ft->residuals, P, moved)) || (st = ensure(ft->residual_mask, P, moved)) || (st = ensure(ft->pixel_face, P, moved)) ||
+	    (st = ensure(ft->acc, N * ACC_STRIDE, moved)) || (st = ensure(ft->updates, N * 6, moved)) || (st = ensure(ft->gradient, N * 6, moved)) ||
+	    (st = ensure(ft->hessian, N * 36, moved)))
 		return st;
 	// the pixel launch's order table (one per launch: choose_launches)
-	const size_t tiles = static_cast<size_t>(ceil_div(W, 16)) * static_cast<size_t>(ceil_div(H, 16));
-	if (key.launch.quad_order && ((st = ensure(ft->quad_scratch, quad_order_scratch(static_cast<int>(4 * tiles)))) ||
-	                              (st = ensure(ft->quad_order, 4 * static_cast<size_t>(quad_order_blocks(static_cast<int>(4 * tiles)))))))
+	const int tiles = static_cast<int>(ceil_div(key.W, 16) * ceil_div(key.H, 16));
+	if (key.launch.quad_order && ((st = ensure(ft->quad_scratch, quad_order_scratch(4 * tiles), moved)) ||
+	                              (st = ensure(ft->quad_order, 4 * static_cast<size_t>(quad_order_blocks(4 * tiles)), moved))))
 		return st;
 	if (key.launch.tile_order &&
-	    ((st = ensure(ft->tile_flags, tiles)) || (st = ensure(ft->tile_order, static_cast<size_t>(tile_order_blocks(static_cast<int>(tiles)))))))
+	    ((st = ensure(ft->tile_flags, tiles, moved)) || (st = ensure(ft->tile_order, static_cast<size_t>(tile_order_blocks(tiles)), moved))))
 		return st;
-	// ARAP workspace
-	if (E > 0) {
-		const int n0 = key.n0, m = 6 * (N - n0);
-		{   // corner node positions (virtual order) for the nested-dissection bisection
-			std::vector<float> cpos(3 * static_cast<size_t>(N - n0));
-			for (int a = 0; a < N - n0; a++) {
-				const int64_t o = wf->h.virtual_indices.empty() ? n0 + a : wf->h.virtual_indices[static_cast<size_t>(n0 + a)];
-				for (int c = 0; c < 3; c++) cpos[3 * static_cast<size_t>(a) + c] = wf->nodes_original[3 * static_cast<size_t>(o) + c];
-			}
-			if ((st = ft->corner.prepare(wf->h.edges.data(), E, n0, N, cpos.data()))) {
-				ft->drop_graphs();
-				return st;
-			}
-		}
-		if ((st = ensure(ft->wing, static_cast<size_t>(E) * 36)) || (st = ensure(ft->edge_residuals, 3 * static_cast<size_t>(E))) ||
-		    (st = ensure(ft->a_diag, static_cast<size_t>(N) * 36)) || (st = ensure(ft->a_dinv, static_cast<size_t>(n0) * 36)) ||
-		    (st = ensure(ft->a_dinvb, static_cast<size_t>(E) * 36)) ||
-		    (st = ensure(ft->edge_jr, 2 * static_cast<size_t>(E) * EDGE_TERMS)) ||
-		    (st = ensure(ft->a_rhs, 6 * static_cast<size_t>(N))) || (st = ensure(ft->a_x, 6 * static_cast<size_t>(N))) ||
-		    (st = ensure(ft->a_res, 6 * static_cast<size_t>(N))) || (st = ensure(ft->a_dx, 6 * static_cast<size_t>(N))))
-			return st;
-		const StemEdgeCsr stem = build_stem_edge_csr(wf->h.edges.data(), E, n0);
-		if ((st = upload_to(ft->a_offsets, stem.offsets)) || (st = upload_to(ft->a_list, stem.list))) return st;
-		// CSR of edge incidences by node (source: 2 e, target: 2 e + 1), ascending e per node
-		std::vector<int> inc_off(static_cast<size_t>(N) + 1, 0), inc_list(2 * static_cast<size_t>(E));
-		for (int e = 0; e < E; e++) {
-			inc_off[static_cast<size_t>(wf->h.edges[2 * e]) + 1]++;
-			inc_off[static_cast<size_t>(wf->h.edges[2 * e + 1]) + 1]++;
-		}
-		for (int n = 0; n < N; n++) inc_off[static_cast<size_t>(n) + 1] += inc_off[static_cast<size_t>(n)];
-		{
-			std::vector<int> fill_inc(inc_off.begin(), inc_off.end() - 1);
-			for (int e = 0; e < E; e++) {
-				inc_list[static_cast<size_t>(fill_inc[static_cast<size_t>(wf->h.edges[2 * e])]++)] = 2 * e;
-				inc_list[static_cast<size_t>(fill_inc[static_cast<size_t>(wf->h.edges[2 * e + 1])]++)] = 2 * e + 1;
-			}
-		}
-		// the slot of each incidence in that order: the ARAP edge kernel writes its two nodes' terms there (node-major, so
-		// k_arrow_prepare reads each node's terms contiguously, without the incidence list)
-		std::vector<int> inc_slot(2 * static_cast<size_t>(E));
-		for (size_t q = 0; q < inc_list.size(); q++) inc_slot[static_cast<size_t>(inc_list[q])] = static_cast<int>(q);
-		if ((st = upload_to(ft->a_inc_off, inc_off)) || (st = upload_to(ft->a_inc_list, inc_list)) || (st = upload_to(ft->a_inc_slot, inc_slot))) return st;
-		ft->aw.inc_off = ft->a_inc_off.ptr;
-		ft->aw.inc_list = ft->a_inc_list.ptr;
-		const StemSchurLists sl = build_stem_schur_lists(wf->h.edges.data(), E, n0, N);
-		if ((st = upload_to(ft->a_tgt_off, sl.tgt_off)) || (st = upload_to(ft->a_tgt_ab, sl.tgt_ab)) || (st = upload_to(ft->a_pairs, sl.pairs)) ||
-		    (st = upload_to(ft->a_rhs_off, sl.rhs_off)) || (st = upload_to(ft->a_rhs_edges, sl.rhs_edges)))
-			return st;
-		ft->aw.targets = static_cast<int>(sl.tgt_ab.size());
-		ft->aw.tgt_off = ft->a_tgt_off.ptr;
-		ft->aw.tgt_ab = ft->a_tgt_ab.ptr;
-		ft->aw.pairs = ft->a_pairs.ptr;
-		ft->aw.rhs_off = ft->a_rhs_off.ptr;
-		ft->aw.rhs_edges = ft->a_rhs_edges.ptr;
-		ft->aw.N = N;
-		ft->aw.n0 = n0;
-		ft->aw.E = E;
-		ft->aw.m = m;
-		ft->aw.corner = &ft->corner;
-		ft->aw.diag = ft->a_diag.ptr;
-		ft->aw.dinv = ft->a_dinv.ptr;
-		ft->aw.dinv_b = ft->a_dinvb.ptr;
-		ft->aw.rhs = ft->a_rhs.ptr;
-		ft->aw.x = ft->a_x.ptr;
-		ft->aw.refine = NNRT_ARAP_REFINE != 0;
-		ft->aw.refine_ratio = ft->refine_ratio;
-		ft->aw.guard_zero_rotation = ft->guard_zero_rotation;
-		ft->aw.res = ft->a_res.ptr;
-		ft->aw.dx = ft->a_dx.ptr;
-		ft->aw.edge_offsets = ft->a_offsets.ptr;
-		ft->aw.edge_list = ft->a_list.ptr;
-	}
-	if (key.coupled && E == 0) {   // the coupled solve's vectors (with a hierarchy the arrowhead path's, above)
-		if ((st = ensure(ft->a_diag, static_cast<size_t>(N) * 36)) || (st = ensure(ft->a_rhs, 6 * static_cast<size_t>(N))) ||
-		    (st = ensure(ft->a_x, 6 * static_cast<size_t>(N))) || (st = ensure(ft->a_res, 6 * static_cast<size_t>(N))) ||
-		    (st = ensure(ft->a_dx, 6 * static_cast<size_t>(N))) || (st = ensure(ft->edge_jr, 1)))
-			return st;
-	}
+	// ARAP: the edge terms; and the tile-sparse solves' vectors, the coupled mode's too (without a hierarchy its prepare
+	// launch still takes an edge-term pointer)
+	if (E > 0 && ((st = ensure(ft->wing, E * 36, moved)) || (st = ensure(ft->edge_residuals, 3 * E, moved)))) return st;
+	if ((E > 0 || key.coupled) &&
+	    ((st = ensure(ft->a_diag, N * 36, moved)) || (st = ensure(ft->edge_jr, 2 * E * EDGE_TERMS, moved)) || (st = ensure(ft->a_rhs, 6 * N, moved)) ||
+	     (st = ensure(ft->a_x, 6 * N, moved)) || (st = ensure(ft->a_res, 6 * N, moved)) || (st = ensure(ft->a_dx, 6 * N, moved))))
+		return st;
+	// coupled: what stands for the empty stem, and the prepare launch's incidence offsets without a hierarchy
 	if (key.coupled) {
-		if ((st = ensure(ft->zero_inc, static_cast<size_t>(N) + 1)) || (st = ensure(ft->c_edge_off, 1)) || (st = ensure(ft->c_dinv, 36))) return st;
-		NNRT_HIP(hipMemset(ft->zero_inc.ptr, 0, sizeof(int) * (static_cast<size_t>(N) + 1)));
+		if ((st = ensure(ft->zero_inc, N + 1, moved)) || (st = ensure(ft->c_edge_off, 1, moved)) || (st = ensure(ft->c_dinv, 36, moved))) return st;
+		NNRT_HIP(hipMemset(ft->zero_inc.ptr, 0, sizeof(int) * (N + 1)));
 		NNRT_HIP(hipMemset(ft->c_edge_off.ptr, 0, sizeof(int)));
 	}
-	if (ft->step_on) {   // step control's device state (a moved buffer drops the graphs, as above)
-		if ((st = ensure(ft->step_state, 1)) || (st = ensure(ft->step_history, NNRT_STEP_HISTORY_CAPACITY)) ||
-		    (st = ensure(ft->step_best, static_cast<size_t>(N) * STEP_BEST_STRIDE)) ||
-		    (st = ensure(ft->step_partials, static_cast<size_t>(step_cost_blocks(P + 3 * static_cast<int64_t>(E))))))
+	// step control's device state
+	if (ft->step_on) {
+		if ((st = ensure(ft->step_state, 1, moved)) || (st = ensure(ft->step_history, NNRT_STEP_HISTORY_CAPACITY, moved)) ||
+		    (st = ensure(ft->step_best, N * STEP_BEST_STRIDE, moved)) ||
+		    (st = ensure(ft->step_partials, static_cast<size_t>(step_cost_blocks(static_cast<int64_t>(P + 3 * E))), moved)))
 			return st;
-		if (ft->step_objective == NNRT_STEP_OBJECTIVE_ROBUST && (st = ensure(ft->step_raw, P))) return st;
+		if (ft->step_objective == NNRT_STEP_OBJECTIVE_ROBUST && (st = ensure(ft->step_raw, P, moved))) return st;
 	}
-	key.corner_generation = ft->corner.generation;
-	// any other change of what the graphs bake in drops them too
-	if (std::memcmp(&key, &ft->key, sizeof(key)) != 0) ft->drop_graphs();
-	ft->key = key;
-	ft->snapshot_valid = false;
-	WorkScope scope(ft, us);   // the work stream runs after the caller's stream, and the caller's after it again on every return
-	if ((st = scope.enter())) return st;
-	hipStream_t s = ft->work;
-	NNRT_HIP(hipMemcpyAsync(ft->mesh_p.ptr, d_vertices, sizeof(float) * 3 * V, hipMemcpyDeviceToDevice, s));
-	NNRT_HIP(hipMemcpyAsync(ft->mesh_n.ptr, d_normals, sizeof(float) * 3 * V, hipMemcpyDeviceToDevice, s));
-	k_faces_to_int4<<<static_cast<unsigned>(ceil_div(F, 256)), 256, 0, s>>>(d_faces, F, V, ft->p.ndc_convention == NNRT_NDC_CONSISTENT,
+	return NNRT_OK;
+}
+
+// the arrowhead solve's structure over the hierarchy's edges (host planning and uploads; an unchanged hierarchy keeps it)
+static nnrt_status build_arap_structure(nnrt_fitter* ft, const nnrt_warp_field* wf, FrameKey& key, bool* moved) {
+	nnrt_status st = NNRT_OK;
+	if (key.E > 0) {
+		st = ft->arap.build(wf->h.edges.data(), key.E, key.n0, key.N, virtual_node_positions(wf, key.n0, key.N - key.n0).data(), true);
+		if (ft->arap.moved) *moved = true;
+	}
+	key.corner_generation = ft->arap.corner.generation;
+	return st;
+}
+
+// the mesh side of the frame on the work stream: copies, conversions, anchors and the face-node table
+static nnrt_status enqueue_mesh_setup(nnrt_fitter* ft, const nnrt_warp_field* wf, const FrameKey& key, const FrameInputs& in, hipStream_t s) {
+	const int64_t V = key.V, F = key.F;
+	nnrt_status st;
+	NNRT_HIP(hipMemcpyAsync(ft->mesh_p.ptr, in.vertices, sizeof(float) * 3 * V, hipMemcpyDeviceToDevice, s));
+	NNRT_HIP(hipMemcpyAsync(ft->mesh_n.ptr, in.normals, sizeof(float) * 3 * V, hipMemcpyDeviceToDevice, s));
+	k_faces_to_int4<<<static_cast<unsigned>(ceil_div(F, 256)), 256, 0, s>>>(in.faces, F, V, ft->p.ndc_convention == NNRT_NDC_CONSISTENT,
 	                                                                        ft->faces4.ptr, ft->error_flag.ptr);
 	NNRT_LAUNCH_CHECK();
-	k_to_float4<<<static_cast<unsigned>(ceil_div(V, 256)), 256, 0, s>>>(d_vertices, d_normals, V, ft->mesh_p4.ptr, ft->mesh_n4.ptr);
+	k_to_float4<<<static_cast<unsigned>(ceil_div(V, 256)), 256, 0, s>>>(in.vertices, in.normals, V, ft->mesh_p4.ptr, ft->mesh_n4.ptr);
 	NNRT_LAUNCH_CHECK();
 	// once per frame (:96-106): anchors & weights on the canonical mesh in virtual node order
 	const float* anchor_node_weights = wf->coverage_method == NNRT_MINIMAL_K_NEIGHBOR_NODE_DISTANCE ? wf->node_weights.ptr : nullptr;
 	if (ft->graph_degree > 0) {
 		// along the anchor graph's edges (PlanarGraphWarpField::PrecomputeAnchorsAndWeights, SHORTEST_PATH): no distance
 		// threshold in this mode
-		if ((st = launch_anchors_shortest_path(ft->mesh_p.ptr, V, wf->node_positions.ptr, N, ft->graph_edges.ptr, ft->graph_degree, K,
+		if ((st = launch_anchors_shortest_path(ft->mesh_p.ptr, V, wf->node_positions.ptr, key.N, ft->graph_edges.ptr, ft->graph_degree, key.K,
 		                                       wf->coverage, anchor_node_weights, ft->anchors.ptr, ft->weights.ptr, s, true)))
 			return st;
-	} else if ((st = launch_compute_anchors(ft->mesh_p.ptr, V, wf->node_positions.ptr, N, K, wf->coverage, anchor_node_weights,
+	} else if ((st = launch_compute_anchors(ft->mesh_p.ptr, V, wf->node_positions.ptr, key.N, key.K, wf->coverage, anchor_node_weights,
 	                                        wf->threshold ? wf->minimum_valid : 0, ft->anchors.ptr, ft->weights.ptr, s)))
 		return st;
 	// the faces' distinct anchor nodes (AssociateFacesWithAnchors, :105), consumed by the node pass of every iteration
-	if ((st = launch_face_node_table(ft->faces4.ptr, F, ft->anchors.ptr, K, ft->face_nodes.ptr, s))) return st;
-	if (ft->key.launch.anchors16 && (st = launch_pack_anchors16(ft->anchors.ptr, V, ft->anchors16.ptr, s))) return st;
-	if (ft->key.coupled) {
-		// the frame's node pairs from the face table (+ the hierarchy's edges), then the solver plan over them: the one
-		// host round trip of the coupled mode (the plan needs the coordinates); iterate() plans nothing
-		bool moved = false;
-		if ((st = build_pair_structure(ft->ps, ft->face_nodes.ptr, F, K, wf->edges.ptr, wf->h.edges.data(), E, N, s, &moved))) {
-			ft->drop_graphs();
-			return st;
-		}
-		const int M = ft->ps.M;
-		std::vector<float> cpos(3 * static_cast<size_t>(N));   // node positions (virtual order) for the nested-dissection bisection
-		for (int a = 0; a < N; a++) {
-			const int64_t o = wf->h.virtual_indices.empty() ? a : wf->h.virtual_indices[static_cast<size_t>(a)];
-			for (int c = 0; c < 3; c++) cpos[3 * static_cast<size_t>(a) + c] = wf->nodes_original[3 * static_cast<size_t>(o) + c];
-		}
-		if ((st = ft->pair_corner.prepare(ft->ps.h_pairs.data(), M, 0, N, cpos.data()))) {
-			ft->drop_graphs();
-			return st;
-		}
-		if ((st = ensure(ft->pair_acc, 36 * static_cast<size_t>(M))) || (st = ensure(ft->pair_blocks, 36 * static_cast<size_t>(M)))) return st;
-		if (moved || ft->pair_corner.generation != ft->key.pair_generation || M != ft->key.M) ft->drop_graphs();
-		ft->key.pair_generation = ft->pair_corner.generation;
-		ft->key.M = M;
-		ArrowheadWorkspace& cw = ft->cw;
-		cw = ArrowheadWorkspace();
-		cw.N = N;
-		cw.n0 = 0;
-		cw.E = M;
-		cw.m = 6 * N;
-		cw.corner = &ft->pair_corner;
-		cw.diag = ft->a_diag.ptr;
-		cw.dinv = ft->c_dinv.ptr;
-		cw.dinv_b = ft->c_dinv.ptr;
-		cw.rhs = ft->a_rhs.ptr;
-		cw.x = ft->a_x.ptr;
-		cw.refine = NNRT_ARAP_REFINE != 0;
-		cw.res = ft->a_res.ptr;
-		cw.dx = ft->a_dx.ptr;
-		cw.edge_offsets = ft->c_edge_off.ptr;
-		cw.edge_list = ft->c_edge_off.ptr;
-		cw.inc_off = ft->ps.inc_off.ptr;
-		cw.inc_list = ft->ps.inc_list.ptr;
+	if ((st = launch_face_node_table(ft->faces4.ptr, F, ft->anchors.ptr, key.K, ft->face_nodes.ptr, s))) return st;
+	if (key.launch.anchors16 && (st = launch_pack_anchors16(ft->anchors.ptr, V, ft->anchors16.ptr, s))) return st;
+	return NNRT_OK;
+}
+
+// Coupled mode: the frame's node pairs from the face-node table (+ the hierarchy's edges) on the work stream, then the
+// solver plan over them: the one host round trip of the mode (the plan needs the coordinates); iterate() plans nothing.
+// The plan's generation and the pair count enter the key here.
+static nnrt_status build_coupled_structure(nnrt_fitter* ft, const nnrt_warp_field* wf, FrameKey& key, hipStream_t s, bool* moved) {
+	if (!key.coupled) return NNRT_OK;
+	nnrt_status st = build_pair_structure(ft->ps, ft->face_nodes.ptr, key.F, key.K, wf->edges.ptr, wf->h.edges.data(), key.E, key.N, s, moved);
+	if (!st) st = ft->pair_corner.prepare(ft->ps.h_pairs.data(), ft->ps.M, 0, key.N, virtual_node_positions(wf, 0, key.N).data());
+	if (st) {   // what the pair buffers and the plan hold now is unknown
+		*moved = true;
+		return st;
 	}
+	key.pair_generation = ft->pair_corner.generation;
+	key.M = ft->ps.M;
+	const size_t M = static_cast<size_t>(ft->ps.M);
+	if ((st = ensure(ft->pair_acc, 36 * M, moved)) || (st = ensure(ft->pair_blocks, 36 * M, moved))) return st;
+	return NNRT_OK;
+}
+
+// the image side of the frame on the work stream: reference points, the pixel launch's order table, the raster keys and
+// the accumulators, step control's restart
+static nnrt_status enqueue_reference_setup(nnrt_fitter* ft, const FrameKey& key, const FrameReference& ref, hipStream_t s) {
+	const int H = key.H, W = key.W, tiles_x = static_cast<int>(ceil_div(W, 16)), tiles_y = static_cast<int>(ceil_div(H, 16));
+	const int64_t P = static_cast<int64_t>(H) * W;
+	nnrt_status st;
 	// reference point cloud (:289-306): depth / scale with 0 < d < max_depth, AND the user mask; stored as depth (0 = masked)
 	if (ref.depth)
 		k_prepare_reference_depth<<<static_cast<unsigned>(ceil_div(P, 256)), 256, 0, s>>>(ref.depth, ref.mask, H, W, ref.depth_scale,
-		                                                                                  ft->p.max_depth, ft->key.pix, ft->ref_points.ptr);
+		                                                                                  ft->p.max_depth, key.pix, ft->ref_points.ptr);
 	else
 		k_prepare_reference_points<<<static_cast<unsigned>(ceil_div(P, 256)), 256, 0, s>>>(ref.points, ref.mask, P, ft->ref_points.ptr);
 	NNRT_LAUNCH_CHECK();
 	// the pixel launch's tile order for this frame's reference points
-	if (ft->key.launch.tile_order &&
-	    (st = launch_tile_order(ft->ref_points.ptr, H, W, static_cast<int>(ceil_div(W, 16)), static_cast<int>(ceil_div(H, 16)), ft->tile_flags.ptr,
-	                            ft->tile_order.ptr, s)))
-		return st;
-	if (ft->key.launch.quad_order &&
-	    (st = launch_quad_order(ft->ref_points.ptr, H, W, static_cast<int>(ceil_div(W, 16)), static_cast<int>(ceil_div(H, 16)), ft->key.quad_slots,
-	                            ft->quad_scratch.ptr, ft->quad_order.ptr, s)))
+	if (key.launch.tile_order && (st = launch_tile_order(ft->ref_points.ptr, H, W, tiles_x, tiles_y, ft->tile_flags.ptr, ft->tile_order.ptr, s))) return st;
+	if (key.launch.quad_order &&
+	    (st = launch_quad_order(ft->ref_points.ptr, H, W, tiles_x, tiles_y, key.quad_slots, ft->quad_scratch.ptr, ft->quad_order.ptr, s)))
 		return st;
 	NNRT_HIP(hipMemsetAsync(ft->keys.ptr, 0xff, sizeof(uint64_t) * P, s));
-	NNRT_HIP(hipMemsetAsync(ft->acc.ptr, 0, sizeof(double) * N * ACC_STRIDE, s));
+	NNRT_HIP(hipMemsetAsync(ft->acc.ptr, 0, sizeof(double) * key.N * ACC_STRIDE, s));
 	if (ft->step_on) {
 		if ((st = launch_step_reset(ft->step_state.ptr, step_initial_lambda(ft), s))) return st;
 		// an edge the ARAP launch refuses (A3, error bit 2) writes no residual: the cost then sums zeros there, not stale values
-		if (E > 0) NNRT_HIP(hipMemsetAsync(ft->edge_residuals.ptr, 0, sizeof(float) * 3 * static_cast<size_t>(E), s));
+		if (key.E > 0) NNRT_HIP(hipMemsetAsync(ft->edge_residuals.ptr, 0, sizeof(float) * 3 * static_cast<size_t>(key.E), s));
 		// nnrt_fitter_get_raw_residuals before the first iteration reads zeros
 		if (ft->step_objective == NNRT_STEP_OBJECTIVE_ROBUST) NNRT_HIP(hipMemsetAsync(ft->step_raw.ptr, 0, sizeof(float) * static_cast<size_t>(P), s));
 	}
-	if ((st = scope.leave())) return st;
+	return NNRT_OK;
+}
+
+nnrt_status prepare_frame(nnrt_fitter* ft, nnrt_warp_field* wf, const FrameInputs& in, void* stream) {
+	nnrt_status st;
+	if ((st = check_frame_arguments(ft, wf, in))) return st;
+	DeviceGuard guard(ft->device);
+	// until this frame is fully prepared the fitter is not: a failure below (allocation, corner plan) leaves iterate()
+	// refusing rather than replaying graphs over buffers that may have been released
+	ft->prepared = false;
+	if ((st = check_frame_warp_field(ft, wf))) return st;
+	FrameKey key = make_frame_key(ft, wf, in);
+	GraphInvalidation graphs(ft);
+	if ((st = allocate_frame(ft, key, &graphs.stale)) || (st = build_arap_structure(ft, wf, key, &graphs.stale))) return st;
+	hipStream_t us = static_cast<hipStream_t>(stream), s = ft->work;
+	WorkScope scope(ft, us);   // the work stream runs after the caller's stream, and the caller's after it again on every return
+	if ((st = scope.enter()) || (st = enqueue_mesh_setup(ft, wf, key, in, s)) || (st = build_coupled_structure(ft, wf, key, s, &graphs.stale)))
+		return st;
+	// the key is complete: any other change of what the graphs bake in drops them too
+	if (std::memcmp(&key, &ft->key, sizeof(key)) != 0) graphs.stale = true;
+	ft->key = key;
+	ft->snapshot_valid = false;
+	if ((st = enqueue_reference_setup(ft, key, in.ref, s)) || (st = scope.leave())) return st;
 	ft->prepared = true;
 	return NNRT_OK;
 }
@@ -843,7 +822,7 @@ nnrt_status nnrt_fitter_prepare(nnrt_fitter* ft, nnrt_warp_field* wf, const floa
 	ref.mask = d_mask;
 	ref.depth_scale = depth_scale;
 	NNRT_CHECK_ARG(d_depth, "null depth image");
-	return prepare_frame(ft, wf, d_vertices, d_normals, V, d_faces, F, ref, H, W, h_K, h_E, stream);
+	return prepare_frame(ft, wf, FrameInputs{d_vertices, d_normals, V, d_faces, F, ref, H, W, h_K, h_E}, stream);
 }
 
 int32_t nnrt_fit_quad_order_blocks(int32_t quadrants) { return quadrants > 0 ? quad_order_blocks(quadrants) : 0; }
@@ -876,7 +855,7 @@ nnrt_status nnrt_fitter_prepare_point_cloud(nnrt_fitter* ft, nnrt_warp_field* wf
 	ref.points = d_points;
 	ref.mask = d_point_mask;
 	NNRT_CHECK_ARG(d_points, "null reference point cloud");
-	return prepare_frame(ft, wf, d_vertices, d_normals, V, d_faces, F, ref, H, W, h_K, h_E, stream);
+	return prepare_frame(ft, wf, FrameInputs{d_vertices, d_normals, V, d_faces, F, ref, H, W, h_K, h_E}, stream);
 }
 
 namespace {
@@ -1005,7 +984,7 @@ nnrt_status nnrt_fitter_iterate_from_identity(nnrt_fitter* ft, nnrt_warp_field* 
 
 nnrt_status nnrt_fitter_corner_info(const nnrt_fitter* ft, int64_t* h_out) {
 	NNRT_CHECK_ARG(ft && h_out, "null pointer");
-	const CornerSolver& c = ft->corner;
+	const CornerSolver& c = ft->arap.corner;
 	const bool on = ft->key.E > 0;
 	h_out[0] = on ? ft->key.N - ft->key.n0 : 0;
 	h_out[1] = on ? c.tile_columns() : 0;
@@ -1062,7 +1041,7 @@ nnrt_status nnrt_fitter_get_arrowhead_system(nnrt_fitter* ft, float* h_diag, flo
 
 nnrt_status nnrt_fitter_corner_work(const nnrt_fitter* ft, int64_t* h_out) {
 	NNRT_CHECK_ARG(ft && h_out, "null pointer");
-	const CornerSolver& c = ft->corner;
+	const CornerSolver& c = ft->arap.corner;
 	const bool on = ft->key.E > 0;
 	h_out[0] = on ? c.mfma_flops() : 0;
 	h_out[1] = on ? c.update_terms() : 0;
@@ -1080,11 +1059,11 @@ nnrt_status nnrt_fitter_refine_info(nnrt_fitter* ft, float* h_out, void* stream)
 	h_out[2] = 0.f;
 	h_out[3] = 0.f;
 	h_out[4] = 0.f;
-	if (ft->key.E > 0 && ft->corner.pivot_ratio()) {
+	if (ft->key.E > 0 && ft->arap.corner.pivot_ratio()) {
 		NNRT_HIP(hipStreamSynchronize(static_cast<hipStream_t>(stream)));
 		NNRT_HIP(hipStreamSynchronize(ft->work));
 		unsigned w[REFINE_WORDS] = {};
-		NNRT_HIP(hipMemcpy(w, ft->corner.pivot_ratio(), sizeof(w), hipMemcpyDeviceToHost));
+		NNRT_HIP(hipMemcpy(w, ft->arap.corner.pivot_ratio(), sizeof(w), hipMemcpyDeviceToHost));
 		float r, dm, xm;
 		std::memcpy(&r, &w[0], sizeof(r));
 		std::memcpy(&dm, &w[REFINE_GUARD_D], sizeof(dm));
@@ -1105,7 +1084,6 @@ nnrt_status nnrt_fitter_set_refine_ratio(nnrt_fitter* ft, float ratio) {
 	DeviceGuard guard(ft->device);
 	NNRT_HIP(hipStreamSynchronize(ft->work));
 	ft->refine_ratio = ratio;
-	ft->aw.refine_ratio = ratio;
 	ft->drop_graphs();   // the threshold is a launch argument of the captured sequences
 	return NNRT_OK;
 }
@@ -1125,7 +1103,6 @@ nnrt_status nnrt_fitter_set_robust_options(nnrt_fitter* ft, int32_t penalty_form
 	NNRT_HIP(hipStreamSynchronize(ft->work));
 	ft->penalty_form = penalty_form;
 	ft->guard_zero_rotation = guard_zero_rotation;
-	ft->aw.guard_zero_rotation = guard_zero_rotation;
 	ft->drop_graphs();   // both are launch arguments of the captured sequences; the prepared frame stays
 	return NNRT_OK;
 }

@@ -520,7 +520,27 @@ struct StemSchurLists {
 };
 // host: group the stem's edge pairs by Schur target block (edges [E,2] host, virtual order; stem = first n0 nodes)
 StemSchurLists build_stem_schur_lists(const int32_t* edges, int E, int n0, int N);
-// acc -> diagonal blocks (+lm) + rhs ; arrowhead solve ; update node state
+// Everything the arrowhead solve derives from the wing structure alone, and its one owner: the stem CSR, the
+// target-grouped Schur lists, the tile-sparse corner plan with its storage, D^-1 and D^-1 B, and (the fitter's
+// k_arrow_prepare and refinement) the edge incidences by node. The fitter holds one per handle, the stand-alone solve
+// one per pooled structure; a workspace's structure-derived fields come from bind() and from nowhere else.
+struct ArrowheadStructure {
+	int N = 0, n0 = 0, E = 0, targets = 0;
+	CornerSolver corner;   // Schur corner (tile-sparse Cholesky plan + storage)
+	DeviceBuffer<float> dinv, dinv_b;
+	DeviceBuffer<int> edge_offsets, edge_list, tgt_off, rhs_off, rhs_edges;
+	DeviceBuffer<int2> tgt_ab, pairs;
+	DeviceBuffer<int> inc_off, inc_list, inc_slot;   // with_incidences only; inc_slot [2E]: the inverse of inc_list (ArapArgs)
+	// the last build() changed a device pointer held here or the corner's plan (its generation), or lost one to a
+	// failure: whatever captured them (the fitter's graphs) is stale. A failed build() always sets it if it released anything.
+	bool moved = false;
+	// edges [E,2] host, virtual order; corner_positions [N - n0, 3] (nullable: the corner plan bisects by coordinates
+	// where it has them). An unchanged structure keeps every buffer and the plan.
+	nnrt_status build(const int32_t* edges, int E, int n0, int N, const float* corner_positions, bool with_incidences);
+	// the structure-derived fields of a workspace; the caller adds its own vectors (diag, rhs, x, res, dx) and settings
+	void bind(ArrowheadWorkspace& ws) const;
+};
+// acc ->diagonal blocks (+lm) + rhs ; arrowhead solve ; update node state
 nnrt_status launch_arrowhead_iteration(const ArrowheadWorkspace& ws, const double* acc, float lm, const int32_t* edges, const float* wing,
                                        float* node_state, const float* edge_jr, float* updates_out, float* gradient_out, float* hessian_out,
                                        int* error_flag, hipStream_t stream, const float* state_in = nullptr, const float* lm_device = nullptr);

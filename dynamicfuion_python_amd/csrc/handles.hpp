@@ -33,6 +33,15 @@ struct nnrt_warp_field {
 };
 
 namespace nnrt {
+// positions [count, 3] of the nodes first .. first + count - 1 in virtual order (the corner plans' coordinate bisection)
+inline std::vector<float> virtual_node_positions(const nnrt_warp_field* wf, int first, int count) {
+	std::vector<float> pos(3 * static_cast<size_t>(count));
+	for (int a = 0; a < count; a++) {
+		const int64_t o = wf->h.virtual_indices.empty() ? first + a : wf->h.virtual_indices[static_cast<size_t>(first + a)];
+		for (int c = 0; c < 3; c++) pos[3 * static_cast<size_t>(a) + c] = wf->nodes_original[3 * static_cast<size_t>(o) + c];
+	}
+	return pos;
+}
 Camera pixel_camera(const double* K);
 // node motion -> identity (k_reset_motion); node state [N,16] copy (k_copy_state), on s (inside or outside a capture)
 nnrt_status launch_reset_motion(float* state, int N, hipStream_t s);

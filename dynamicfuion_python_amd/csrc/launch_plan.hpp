@@ -13,18 +13,25 @@ struct LaunchSwitches {
 	int tile_order = -1, pix_wpe4 = -1, quad_order = -1, anchors16 = -1, warp_vertex = -1, raster_dense = -1;
 };
 
+// a development switch of the library's, read from the environment in that form (the only getenv of the fitter's code)
+inline int env_switch(const char* name) {
+	const char* v = std::getenv(name);
+	return v ? static_cast<int>(static_cast<unsigned char>(*v)) : -1;
+}
+// an on / off switch: unset = dflt, a value beginning with 0 = off, any other value = on (the corner's switches)
+inline bool env_flag(const char* name, bool dflt) {
+	const int v = env_switch(name);
+	return v < 0 ? dflt : v != '0';
+}
+
 inline LaunchSwitches read_launch_switches() {
-	auto first = [](const char* name) {
-		const char* v = std::getenv(name);
-		return v ? static_cast<int>(static_cast<unsigned char>(*v)) : -1;
-	};
 	LaunchSwitches sw;
-	sw.tile_order = first("NNRT_TILE_ORDER");
-	sw.pix_wpe4 = first("NNRT_PIX_WPE4");
-	sw.quad_order = first("NNRT_QUAD_ORDER");
-	sw.anchors16 = first("NNRT_ANCHORS16");
-	sw.warp_vertex = first("NNRT_WARP_VERTEX");
-	sw.raster_dense = first("NNRT_RASTER_DENSE");
+	sw.tile_order = env_switch("NNRT_TILE_ORDER");
+	sw.pix_wpe4 = env_switch("NNRT_PIX_WPE4");
+	sw.quad_order = env_switch("NNRT_QUAD_ORDER");
+	sw.anchors16 = env_switch("NNRT_ANCHORS16");
+	sw.warp_vertex = env_switch("NNRT_WARP_VERTEX");
+	sw.raster_dense = env_switch("NNRT_RASTER_DENSE");
 	return sw;
 }
 

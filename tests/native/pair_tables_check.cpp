@@ -1,7 +1,10 @@
 // Host-only check of the coupled data term's per-frame bookkeeping (csrc/coupled_host.hpp), test infrastructure: the
 // product header compiled alone, with the host sanitizers. Random node-pair structures with edges on some pairs (both
 // orientations, and doubled) are turned into keys and back, the tables are built and every entry is checked against a
-// brute-force search; malformed input must be refused without indexing anything. Exit code 0 = all checks pass.
+// brute-force search; malformed input must be refused without indexing anything. incidence_csr, which also lists the ARAP
+// edges of the arrowhead solve by node, is called directly on the degenerate sizes and, given a file of edges
+// ([E, N] then E x 2 int32: the 8 x 8 node grid's two-layer hierarchy, written by tests/test_pair_tables.py), on those,
+// each against an O(N M) restatement, with incidence_slots as its inverse. Exit code 0 = all checks pass.
 #include "coupled_host.hpp"
 
 #include <cstdio>
@@ -15,7 +18,64 @@ static int fail(const char* what, int c) {
 	return 1;
 }
 
-int main() {
+// incidence_csr / incidence_slots of pairs [M, 2] over N nodes against the definition, stated naively
+static const char* check_incidences(const std::vector<int32_t>& pairs, int N) {
+	const int M = static_cast<int>(pairs.size() / 2);
+	std::vector<int> off, list;
+	incidence_csr(pairs.data(), M, N, off, list);
+	if (static_cast<int>(off.size()) != N + 1 || static_cast<int>(list.size()) != 2 * M || off[0] != 0 || off[N] != 2 * M) return "incidence sizes";
+	for (int n = 0; n < N; n++) {   // node n's list is exactly: every (s, t) with pairs[2 s + t] == n, ascending s, then t
+		int u = off[n];
+		for (int s = 0; s < M; s++)
+			for (int t = 0; t < 2; t++)
+				if (pairs[2 * s + t] == n) {
+					if (u >= off[n + 1] || list[u] != 2 * s + t) return "incidence list differs from the naive one";
+					u++;
+				}
+		if (u != off[n + 1]) return "incidence count differs from the naive one";
+	}
+	const std::vector<int> slot = incidence_slots(list);
+	if (slot.size() != list.size()) return "slot size";
+	for (int q = 0; q < 2 * M; q++)
+		if (slot[q] < 0 || slot[q] >= 2 * M || list[slot[q]] != q || slot[list[q]] != q) return "inc_slot does not invert inc_list";
+	return nullptr;
+}
+
+int main(int argc, char** argv) {
+	if (argc > 1) {   // an edge list from a file
+		FILE* f = fopen(argv[1], "rb");
+		int32_t head[2] = {0, 0};
+		if (!f || fread(head, sizeof(int32_t), 2, f) != 2 || head[0] < 0 || head[1] < 0) return fail("edge file header", -2);
+		std::vector<int32_t> edges(2 * static_cast<size_t>(head[0]));
+		const bool ok = fread(edges.data(), sizeof(int32_t), edges.size(), f) == edges.size();
+		fclose(f);
+		if (!ok) return fail("edge file body", -2);
+		for (int32_t v : edges)
+			if (v < 0 || v >= head[1]) return fail("edge file index out of range", -2);
+		if (const char* what = check_incidences(edges, head[1])) return fail(what, -2);
+		printf("%d edges over %d nodes ok\n", head[0], head[1]);
+		return 0;
+	}
+	{   // incidence_csr at the degenerate sizes
+		struct {
+			int N;
+			std::vector<int32_t> pairs;
+		} const fixed[] = {
+		    {0, {}},                                        // nothing at all
+		    {5, {}},                                        // M = 0
+		    {1, {}},                                        // N = 1, no pair
+		    {1, {0, 0, 0, 0}},                              // N = 1: only self loops can exist (the edge form allows them)
+		    {2, {0, 1}},                                    // one pair
+		    {6, {0, 1, 1, 4, 0, 4}},                        // nodes 2, 3, 5 in no pair
+		    {5, {2, 0, 2, 1, 3, 2, 2, 4}},                  // node 2 in every pair, on either side
+		    {4, {3, 0, 3, 0, 0, 3}},                        // a doubled edge and its reverse
+		};
+		int c = 0;
+		for (const auto& fx : fixed) {
+			if (const char* what = check_incidences(fx.pairs, fx.N)) return fail(what, -100 - c);
+			c++;
+		}
+	}
 	std::mt19937 rng(17);
 	int cases = 0;
 	for (int c = 0; c < 200; c++, cases++) {
@@ -47,6 +107,8 @@ int main() {
 		PairTables t;
 		std::string err;
 		if (!build_pair_tables(pairs.data(), M, N, edges.data(), E, t, &err)) return fail(err.c_str(), c);
+		if (const char* what = check_incidences(pairs, N)) return fail(what, c);
+		if (const char* what = check_incidences(edges, N)) return fail(what, c);
 		if (static_cast<int>(t.row_off.size()) != N + 1 || t.row_off[N] != M || static_cast<int>(t.inc_off.size()) != N + 1 || t.inc_off[N] != 2 * M ||
 		    static_cast<int>(t.edge_off.size()) != M + 1 || t.edge_off[M] != E || static_cast<int>(t.edge_list.size()) != E)
 			return fail("table sizes", c);

@@ -63,28 +63,33 @@ def warp_field(M, layer_count):
     return M.G.HierarchicalGraphWarpField(nodes, COVERAGE, False, 4, 0, M.G.WarpNodeCoverageComputationMethod.FIXED_NODE_COVERAGE, layer_count)
 
 
-def fitter(M):
+def fitter(M, **kw):
     return M.A.DeformableMeshToImageFitter(2, [M.A.IterationMode.ALL], preconditioning_dampening_factor=0.001,
-                                           use_hip_graph=M.A.GRAPH_ALWAYS)
+                                           use_hip_graph=M.A.GRAPH_ALWAYS, **kw)
 
 
-def fit_sequence(M, ft, wf, frames):
+def fit_sequence(M, ft, wf, frames, from_snapshot=None):
     """prepare (each frame in turn), two iterations, snapshot, one iteration from the snapshot; then the last frame is
-    prepared a second time, which must keep every buffer pointer: the captured graph survives it."""
+    prepared a second time, which must keep every buffer pointer: the captured graph survives it. Returns the number
+    of captured graphs. from_snapshot: the call that iterates from the snapshot (step control refuses the default)."""
+    if from_snapshot is None:
+        from_snapshot = lambda: ft.iterate_from_snapshot(wf, 0, 1)   # noqa: E731
     for mesh, depth, K in frames:
         ft.prepare(wf, M.G.TriangleMesh(*mesh), depth, None, K, None, 1.0)
     ft.iterate(wf, 0, 2)
     ft.snapshot_motion(wf)            # the first snapshot allocates its buffer and drops the graphs
-    ft.iterate_from_snapshot(wf, 0, 1)
+    from_snapshot()
     graphs = ft.graph_count
     assert graphs >= 1                # use_hip_graph always: the sequence was captured
     mesh, depth, K = frames[-1]
     ft.prepare(wf, M.G.TriangleMesh(*mesh), depth, None, K, None, 1.0)
     assert ft.graph_count == graphs   # ensure(n <= count) kept every pointer, so no graph was dropped
     ft.snapshot_motion(wf)
-    ft.iterate_from_snapshot(wf, 0, 1)
+    from_snapshot()
     assert ft.graph_count == graphs   # and the kept graph is the one replayed
+    ft.check()
     torch.cuda.synchronize()
+    return graphs
 
 
 def test_fitter_with_arap_returns_its_memory(M):
@@ -116,6 +121,82 @@ def test_single_layer_fitter_returns_its_memory_after_growing(M):
     assert in_use(M) > after_small     # the larger frame took larger buffers
     destroy(ft)
     destroy(wf)
+    assert in_use(M) == base
+
+
+@pytest.mark.parametrize("layer_count", [2, 1], ids=["two_layers", "one_layer"])
+def test_coupled_fitter_keeps_its_graphs_and_returns_its_memory(M, layer_count):
+    """NNRT_DATA_COUPLED: the pair structure, the solver plan over it and the pair blocks exist; with one layer E == 0,
+    so the prepare launch reads the zero incidence offsets and the solve's vectors are the coupled mode's own. The
+    repeated prepare() rebuilds the pair structure on the device; it finds the same pairs, so the uploads keep their
+    pointers and the plan its generation, and the graph is kept. The graph count (1 after the repeated prepare(), in
+    both cases) was taken from the parent of the refactor that gave prepare() its steps, by running this test against
+    that library."""
+    base = in_use(M)
+    wf = warp_field(M, layer_count)
+    assert (M.N.lib().nnrt_warp_field_edge_count(wf.handle) > 0) == (layer_count == 2)
+    ft = fitter(M)
+    ft.set_data_coupling(M.A.DataCoupling.COUPLED)
+    held = in_use(M)
+    assert fit_sequence(M, ft, wf, [frame(21, 15, H, W, FX)]) == 1
+    assert ft.coupled_pair_count > 0
+    assert in_use(M) > held + 36 * 8 * ft.coupled_pair_count   # pair_acc (fp64) alone
+    destroy(ft)
+    destroy(wf)
+    assert in_use(M) == base
+
+
+@pytest.mark.parametrize("robust", [False, True], ids=["square_one_layer", "robust_irls_two_layers"])
+def test_step_control_fitter_keeps_its_graphs_and_returns_its_memory(M, robust):
+    """Step control on: its state, history, best motion and partial sums exist; under the robust objective (IRLS Tukey
+    and Huber penalties, two layers) the raw residuals too. Iterations that restart from the snapshot every time are
+    refused in this mode, so the sequence fits from the snapshot instead. The graph count (1) was taken from the parent
+    of the refactor that gave prepare() its steps, by running this test against that library."""
+    A = M.A
+    base = in_use(M)
+    wf = warp_field(M, 2 if robust else 1)
+    ft = fitter(M, use_tukey_penalty_for_data_term=True, use_huber_penalty_for_arap_term=True, penalty_form=A.PenaltyForm.IRLS,
+                step_objective=A.StepObjective.ROBUST) if robust else fitter(M)
+    without = in_use(M)
+    ft.set_step_control(A.StepControl())
+    assert fit_sequence(M, ft, wf, [frame(21, 15, H, W, FX)], from_snapshot=lambda: ft.fit_from_snapshot(wf, 1)) == 1
+    assert len(ft.step_history()) == 1
+    if robust:
+        assert ft.raw_residuals().shape == (H * W,)
+    assert in_use(M) > without + 64 * 16 * 4
+    destroy(ft)
+    destroy(wf)
+    assert in_use(M) == base
+
+
+def test_layer_switch_on_one_fitter_drops_graphs_and_returns_memory(M):
+    """Two layers, one layer, two layers again with the same node count on one fitter: each switch changes the frame's
+    key (the warp field, E, n0), so the graphs are dropped at each; the arrowhead structure of the first frame is kept
+    across the one-layer frame and found unchanged by the third."""
+    base = in_use(M)
+    wf2, wf1 = warp_field(M, 2), warp_field(M, 1)
+    ft = fitter(M)
+    mesh, depth, K = frame(21, 15, H, W, FX)
+
+    def fit(wf):
+        ft.prepare(wf, M.G.TriangleMesh(*mesh), depth, None, K, None, 1.0)
+        dropped = ft.graph_count == 0
+        ft.iterate(wf, 0, 2)
+        ft.check()
+        return dropped, ft.graph_count
+
+    assert fit(wf2) == (True, 1)
+    corner = ft.corner_info()
+    with_arap = in_use(M)
+    assert fit(wf1) == (True, 1)
+    assert in_use(M) == with_arap            # nothing of the two-layer frame was released, nothing new was needed
+    assert fit(wf2) == (True, 1)
+    assert ft.corner_info() == corner and in_use(M) == with_arap
+    assert fit(wf2) == (False, 1)            # the same frame again keeps the graph
+    torch.cuda.synchronize()
+    destroy(ft)
+    destroy(wf1)
+    destroy(wf2)
     assert in_use(M) == base
 
 
