@@ -1,8 +1,7 @@
 // The fitter's coupled data term, outside the pixel launches: the per-frame node-pair structure
-// (device keys, hipcub sort + unique, host tables) and the assembly of the pair blocks the tile-sparse solver factors.
-#include <hipcub/hipcub.hpp>
-
+// (device keys, sort + unique, host tables) and the assembly of the pair blocks the tile-sparse solver factors.
 #include "coupled.hpp"
+#include "device_primitives.hpp"
 
 namespace nnrt {
 
@@ -75,13 +74,10 @@ nnrt_status build_pair_structure(PairStructure& ps, const uint32_t* face_nodes, 
 	}
 	int unique = 0;
 	if (total > 0) {
-		size_t sort_bytes = 0, select_bytes = 0;
-		const int n = static_cast<int>(total);
-		NNRT_HIP(hipcub::DeviceRadixSort::SortKeys(nullptr, sort_bytes, ps.keys.ptr, ps.keys_sorted.ptr, n, 0, 64, s));
-		NNRT_HIP(hipcub::DeviceSelect::Unique(nullptr, select_bytes, ps.keys_sorted.ptr, ps.keys.ptr, ps.d_count.ptr, n, s));
-		if ((st = ps.tmp.ensure(std::max<size_t>(std::max(sort_bytes, select_bytes), 1)))) return st;
-		NNRT_HIP(hipcub::DeviceRadixSort::SortKeys(ps.tmp.ptr, sort_bytes, ps.keys.ptr, ps.keys_sorted.ptr, n, 0, 64, s));
-		NNRT_HIP(hipcub::DeviceSelect::Unique(ps.tmp.ptr, select_bytes, ps.keys_sorted.ptr, ps.keys.ptr, ps.d_count.ptr, n, s));
+		// ps.tmp only grows, and no captured graph holds it (nor keys, keys_sorted, d_count): `moved` does not watch them
+		if ((st = sort_keys(ps.keys.ptr, ps.keys_sorted.ptr, total, 64, ps.tmp, s)) ||
+		    (st = unique_keys(ps.keys_sorted.ptr, ps.keys.ptr, ps.d_count.ptr, total, ps.tmp, s)))
+			return st;
 		NNRT_HIP(hipMemcpyAsync(&unique, ps.d_count.ptr, sizeof(int), hipMemcpyDeviceToHost, s));
 		NNRT_HIP(hipStreamSynchronize(s));
 	}

@@ -23,9 +23,8 @@
 #include <limits>
 #include <vector>
 
-#include <hipcub/hipcub.hpp>
-
 #include "common.hpp"
+#include "device_primitives.hpp"
 #include "kernels.hpp"
 
 namespace nnrt {
@@ -157,17 +156,6 @@ __global__ __launch_bounds__(GB) void k_scatter_faces(const uint8_t* __restrict_
 		faces[3 * f + 1] = pixel_vertex[i10];
 		faces[3 * f + 2] = pixel_vertex[i01];
 	}
-}
-
-nnrt_status exclusive_sum(const int* in, int* out, int n, hipStream_t s) {
-	size_t bytes = 0;
-	NNRT_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, bytes, in, out, n, s));
-	DeviceBuffer<uint8_t> tmp;
-	nnrt_status st = tmp.ensure(std::max<size_t>(bytes, 1));
-	if (st) return st;
-	NNRT_HIP(hipcub::DeviceScan::ExclusiveSum(tmp.ptr, bytes, in, out, n, s));
-	NNRT_HIP(hipStreamSynchronize(s));   // tmp is freed on return
-	return NNRT_OK;
 }
 
 // -------------------------------------------------------------- adjacency ----
@@ -378,7 +366,7 @@ nnrt_status launch_mesh_from_depth(const float* pts, int H, int W, float limit, 
 	*h_face_count = 0;
 	if (H < 2 || W < 2) return NNRT_OK;
 	const int C = (H - 1) * (W - 1);
-	DeviceBuffer<uint8_t> bits;
+	DeviceBuffer<uint8_t> bits, tmp;
 	DeviceBuffer<int> vcount, fcount, voff, foff, pixel_vertex;
 	nnrt_status st;
 	if ((st = bits.ensure(C)) || (st = vcount.ensure(C + 1)) || (st = fcount.ensure(C + 1)) || (st = voff.ensure(C + 1)) || (st = foff.ensure(C + 1))) return st;
@@ -386,7 +374,7 @@ nnrt_status launch_mesh_from_depth(const float* pts, int H, int W, float limit, 
 	NNRT_LAUNCH_CHECK();
 	k_cell_counts<<<gblocks(C + 1), GB, 0, s>>>(bits.ptr, H, W, vcount.ptr, fcount.ptr);
 	NNRT_LAUNCH_CHECK();
-	if ((st = exclusive_sum(vcount.ptr, voff.ptr, C + 1, s)) || (st = exclusive_sum(fcount.ptr, foff.ptr, C + 1, s))) return st;
+	if ((st = exclusive_sum(vcount.ptr, voff.ptr, C + 1, tmp, s)) || (st = exclusive_sum(fcount.ptr, foff.ptr, C + 1, tmp, s))) return st;
 	int nv = 0, nf = 0;
 	NNRT_HIP(hipMemcpyAsync(&nv, voff.ptr + C, sizeof(int), hipMemcpyDeviceToHost, s));
 	NNRT_HIP(hipMemcpyAsync(&nf, foff.ptr + C, sizeof(int), hipMemcpyDeviceToHost, s));
@@ -453,14 +441,10 @@ nnrt_status launch_edges_shortest_path(const float* vertices, int64_t V, const u
 	if (F > 0) {
 		k_face_pairs<<<gblocks(F), GB, 0, s>>>(faces, F, V, keys.ptr, ctrl.ptr);
 		NNRT_LAUNCH_CHECK();
-		size_t bytes = 0, select_bytes = 0;
-		NNRT_HIP(hipcub::DeviceRadixSort::SortKeys(nullptr, bytes, keys.ptr, sorted.ptr, static_cast<int>(P), 0, 64, s));
-		NNRT_HIP(hipcub::DeviceSelect::Flagged(nullptr, select_bytes, sorted.ptr, flags.ptr, pairs.ptr, d_count.ptr, static_cast<int>(P), s));
-		if ((st = tmp.ensure(std::max<size_t>(std::max(bytes, select_bytes), 1)))) return st;
-		NNRT_HIP(hipcub::DeviceRadixSort::SortKeys(tmp.ptr, bytes, keys.ptr, sorted.ptr, static_cast<int>(P), 0, 64, s));
+		if ((st = sort_keys(keys.ptr, sorted.ptr, P, 64, tmp, s))) return st;
 		k_pair_flags<<<gblocks(P), GB, 0, s>>>(sorted.ptr, P, flags.ptr);
 		NNRT_LAUNCH_CHECK();
-		NNRT_HIP(hipcub::DeviceSelect::Flagged(tmp.ptr, select_bytes, sorted.ptr, flags.ptr, pairs.ptr, d_count.ptr, static_cast<int>(P), s));
+		if ((st = select_flagged(sorted.ptr, flags.ptr, pairs.ptr, d_count.ptr, P, tmp, s))) return st;
 		int err = 0;
 		NNRT_HIP(hipMemcpyAsync(&E, d_count.ptr, sizeof(int), hipMemcpyDeviceToHost, s));
 		NNRT_HIP(hipMemcpyAsync(&err, ctrl.ptr, sizeof(int), hipMemcpyDeviceToHost, s));

@@ -24,9 +24,8 @@
 #include <algorithm>
 #include <cmath>
 
-#include <hipcub/hipcub.hpp>
-
 #include "common.hpp"
+#include "device_primitives.hpp"
 #include "kernels.hpp"
 
 namespace nnrt {
@@ -240,23 +239,6 @@ __global__ __launch_bounds__(GB) void k_accepted_by_priority(const float4* __res
 	if (s >= M) return;
 	accepted[__float_as_int(pos[s].w)] = state[s] == ACCEPTED ? 1 : 0;
 }
-
-template <typename In, typename Out>
-nnrt_status select_flagged(In in, const uint8_t* flags, Out out, int64_t* d_count, int64_t n, DeviceBuffer<uint8_t>& tmp, size_t& tmp_bytes, hipStream_t s) {
-	size_t bytes = 0;
-	NNRT_HIP(hipcub::DeviceSelect::Flagged(nullptr, bytes, in, flags, out, d_count, static_cast<int>(n), s));
-	if (bytes > tmp_bytes || !tmp.ptr) {
-		if (tmp.ptr) {
-			NNRT_HIP(hipStreamSynchronize(s));
-			tmp.release();
-		}
-		nnrt_status st = tmp.ensure(std::max<size_t>(bytes, 1));
-		if (st) return st;
-		tmp_bytes = bytes;
-	}
-	NNRT_HIP(hipcub::DeviceSelect::Flagged(tmp.ptr, bytes, in, flags, out, d_count, static_cast<int>(n), s));
-	return NNRT_OK;
-}
 } // namespace
 
 nnrt_status launch_vertex_erosion_mask(int64_t V, const int64_t* faces, int64_t F, int iteration_count, int min_neighbors, uint8_t* mask,
@@ -288,14 +270,13 @@ nnrt_status launch_sample_nodes(const float* pts, int64_t V, const uint8_t* mask
 	DeviceBuffer<int64_t> vertex, cand, d_count;
 	DeviceBuffer<uint8_t> flags, tmp;
 	DeviceBuffer<int> ctrl;
-	size_t tmp_bytes = 0;
 	nnrt_status st;
 	if ((st = vertex.ensure(V)) || (st = cand.ensure(V)) || (st = d_count.ensure(1)) || (st = flags.ensure(V)) || (st = ctrl.ensure(4))) return st;
 	NNRT_HIP(hipMemsetAsync(ctrl.ptr, 0, 4 * sizeof(int), s));
 	k_candidate_flags<<<gblocks(V), GB, 0, s>>>(pts, V, mask, order, vertex.ptr, flags.ptr, ctrl.ptr);
 	NNRT_LAUNCH_CHECK();
 	// stable compaction: a candidate's priority is its position in `cand`
-	if ((st = select_flagged(vertex.ptr, flags.ptr, cand.ptr, d_count.ptr, V, tmp, tmp_bytes, s))) return st;
+	if ((st = select_flagged(vertex.ptr, flags.ptr, cand.ptr, d_count.ptr, V, tmp, s))) return st;
 	int64_t M64 = 0;
 	int err = 0;
 	NNRT_HIP(hipMemcpyAsync(&M64, d_count.ptr, sizeof(int64_t), hipMemcpyDeviceToHost, s));
@@ -312,7 +293,7 @@ nnrt_status launch_sample_nodes(const float* pts, int64_t V, const uint8_t* mask
 	DeviceBuffer<uint64_t> keys, keys_sorted;
 	DeviceBuffer<int> prio, prio_sorted, list_a, list_b;
 	DeviceBuffer<float4> pos;
-	DeviceBuffer<uint8_t> state, still, sort_tmp;
+	DeviceBuffer<uint8_t> state, still;
 	DeviceBuffer<int2> runs;
 	if ((st = lo.ensure(4)) || (st = keys.ensure(M)) || (st = keys_sorted.ensure(M)) || (st = prio.ensure(M)) || (st = prio_sorted.ensure(M)) ||
 	    (st = list_a.ensure(M)) || (st = list_b.ensure(M)) || (st = pos.ensure(M)) || (st = state.ensure(M)) || (st = still.ensure(M)) ||
@@ -324,10 +305,7 @@ nnrt_status launch_sample_nodes(const float* pts, int64_t V, const uint8_t* mask
 	const double edge = static_cast<double>(coverage) * CELL_MARGIN;
 	k_cell_keys<<<gblocks(M), GB, 0, s>>>(pts, cand.ptr, M, lo.ptr, edge, keys.ptr, prio.ptr, ctrl.ptr);
 	NNRT_LAUNCH_CHECK();
-	size_t sort_bytes = 0;
-	NNRT_HIP(hipcub::DeviceRadixSort::SortPairs(nullptr, sort_bytes, keys.ptr, keys_sorted.ptr, prio.ptr, prio_sorted.ptr, M, 0, 3 * CELL_BITS, s));
-	if ((st = sort_tmp.ensure(std::max<size_t>(sort_bytes, 1)))) return st;
-	NNRT_HIP(hipcub::DeviceRadixSort::SortPairs(sort_tmp.ptr, sort_bytes, keys.ptr, keys_sorted.ptr, prio.ptr, prio_sorted.ptr, M, 0, 3 * CELL_BITS, s));
+	if ((st = sort_pairs(keys.ptr, keys_sorted.ptr, prio.ptr, prio_sorted.ptr, M, 3 * CELL_BITS, tmp, s))) return st;
 	k_gather_sorted<<<gblocks(M), GB, 0, s>>>(pts, cand.ptr, prio_sorted.ptr, M, pos.ptr, state.ptr, list_a.ptr);
 	NNRT_LAUNCH_CHECK();
 	k_cell_runs<<<gblocks(M), GB, 0, s>>>(keys_sorted.ptr, M, runs.ptr);
@@ -351,7 +329,7 @@ nnrt_status launch_sample_nodes(const float* pts, int64_t V, const uint8_t* mask
 		k_round<<<gblocks(undecided), GB, 0, s>>>(list, undecided, pos.ptr, state.ptr, runs.ptr, M, coverage_sq, still.ptr);
 		NNRT_LAUNCH_CHECK();
 		rounds++;
-		if ((st = select_flagged(list, still.ptr, next, d_count.ptr, undecided, tmp, tmp_bytes, s))) return st;
+		if ((st = select_flagged(list, still.ptr, next, d_count.ptr, undecided, tmp, s))) return st;
 		int64_t left = 0;
 		NNRT_HIP(hipMemcpyAsync(&left, d_count.ptr, sizeof(int64_t), hipMemcpyDeviceToHost, s));
 		NNRT_HIP(hipStreamSynchronize(s));
@@ -365,7 +343,7 @@ nnrt_status launch_sample_nodes(const float* pts, int64_t V, const uint8_t* mask
 	// `flags` (capacity V >= M) is free again: accepted flag per priority, then the vertices in priority order
 	k_accepted_by_priority<<<gblocks(M), GB, 0, s>>>(pos.ptr, state.ptr, M, flags.ptr);
 	NNRT_LAUNCH_CHECK();
-	if ((st = select_flagged(cand.ptr, flags.ptr, out, d_count.ptr, M, tmp, tmp_bytes, s))) return st;
+	if ((st = select_flagged(cand.ptr, flags.ptr, out, d_count.ptr, M, tmp, s))) return st;
 	NNRT_HIP(hipMemcpyAsync(h_count, d_count.ptr, sizeof(int64_t), hipMemcpyDeviceToHost, s));
 	NNRT_HIP(hipStreamSynchronize(s));
 	if (h_rounds) *h_rounds = rounds;

@@ -16,9 +16,8 @@
 #include <algorithm>
 #include <cfloat>
 
-#include <hipcub/hipcub.hpp>
-
 #include "common.hpp"
+#include "device_primitives.hpp"
 #include "warp_field.hpp"
 
 namespace nnrt {
@@ -273,7 +272,7 @@ nnrt_status launch_median_grid_subsample(const float* pts, int n, float cell, in
 	if (n == 0) return NNRT_OK;
 	DeviceBuffer<float> d_sums;
 	DeviceBuffer<int4> d_keys;
-	DeviceBuffer<uint8_t> d_flags;
+	DeviceBuffer<uint8_t> d_flags, tmp;
 	DeviceBuffer<int64_t> d_count;
 	nnrt_status st;
 	if ((st = d_sums.ensure(n)) || (st = d_keys.ensure(n)) || (st = d_flags.ensure(n)) || (st = d_count.ensure(1))) return st;
@@ -283,12 +282,7 @@ nnrt_status launch_median_grid_subsample(const float* pts, int n, float cell, in
 	NNRT_LAUNCH_CHECK();
 	k_medoid_flags<<<blocks(n), HB, 0, s>>>(d_sums.ptr, d_keys.ptr, n, d_flags.ptr);
 	NNRT_LAUNCH_CHECK();
-	hipcub::CountingInputIterator<int64_t> idx(0);
-	size_t bytes = 0;
-	NNRT_HIP(hipcub::DeviceSelect::Flagged(nullptr, bytes, idx, d_flags.ptr, out, d_count.ptr, n, s));
-	DeviceBuffer<uint8_t> tmp;
-	if ((st = tmp.ensure(std::max<size_t>(bytes, 1)))) return st;
-	NNRT_HIP(hipcub::DeviceSelect::Flagged(tmp.ptr, bytes, idx, d_flags.ptr, out, d_count.ptr, n, s));
+	if ((st = select_flagged_indices(d_flags.ptr, out, d_count.ptr, n, tmp, s))) return st;
 	NNRT_HIP(hipMemcpyAsync(h_count, d_count.ptr, sizeof(int64_t), hipMemcpyDeviceToHost, s));
 	NNRT_HIP(hipStreamSynchronize(s));
 	return NNRT_OK;

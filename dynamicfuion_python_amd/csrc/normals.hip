@@ -3,6 +3,7 @@
 // The reference accumulates vertex normals with float atomics (order-nondeterministic, A18); here every vertex
 // gathers its incident faces in ascending face order from a vertex -> face CSR built on the device, which is the
 // reference's serial (CPU, single-thread) summation order exactly.
+#include "device_primitives.hpp"
 #include "kernels.hpp"
 
 namespace nnrt {
@@ -54,30 +55,6 @@ __global__ void k_vertex_face_count(const int64_t* __restrict__ faces, int64_t F
 		return;
 	}
 	atomicAdd(count + v, 1);
-}
-
-// single-workgroup exclusive scan of the per-vertex counts (V + 1 offsets), 1024 threads, chunked
-__global__ __launch_bounds__(1024) void k_exclusive_scan(const int* __restrict__ in, int64_t n, int* __restrict__ out) {
-	__shared__ int s_part[1024];
-	const int t = threadIdx.x;
-	const int64_t per = (n + 1023) / 1024;
-	const int64_t lo = t * per, hi = lo + per < n ? lo + per : n;
-	int sum = 0;
-	for (int64_t i = lo; i < hi; i++) sum += in[i];
-	s_part[t] = sum;
-	__syncthreads();
-	for (int d = 1; d < 1024; d <<= 1) {   // Hillis-Steele inclusive scan of the chunk sums
-		const int v = t >= d ? s_part[t - d] : 0;
-		__syncthreads();
-		s_part[t] += v;
-		__syncthreads();
-	}
-	int run = t > 0 ? s_part[t - 1] : 0;
-	for (int64_t i = lo; i < hi; i++) {
-		out[i] = run;
-		run += in[i];
-	}
-	if (t == 1023) out[n] = s_part[1023];
 }
 
 __global__ void k_vertex_face_fill(const int64_t* __restrict__ faces, int64_t F, const int* __restrict__ offsets, int* __restrict__ cursor,
@@ -178,12 +155,14 @@ nnrt_status nnrt_compute_vertex_normals(const float* d_vertices, int64_t vertex_
 	if (vertex_count == 0) return NNRT_OK;
 	hipStream_t s = static_cast<hipStream_t>(stream);
 	StreamScratch<int> count, offsets, list, flag;
+	StreamScratch<uint8_t> tmp;
 	const int64_t V = vertex_count, n3 = 3 * face_count;
 	nnrt_status st;
-	if ((st = count.alloc(static_cast<size_t>(V), s)) || (st = offsets.alloc(static_cast<size_t>(V) + 1, s)) ||
+	// count holds a zero at index V, so the exclusive sum over V + 1 items leaves the total in offsets[V]
+	if ((st = count.alloc(static_cast<size_t>(V) + 1, s)) || (st = offsets.alloc(static_cast<size_t>(V) + 1, s)) ||
 	    (st = list.alloc(static_cast<size_t>(n3), s)) || (st = flag.alloc(1, s)))
 		return st;
-	NNRT_HIP(hipMemsetAsync(count.ptr, 0, sizeof(int) * V, s));
+	NNRT_HIP(hipMemsetAsync(count.ptr, 0, sizeof(int) * (V + 1), s));
 	NNRT_HIP(hipMemsetAsync(flag.ptr, 0, sizeof(int), s));
 	if (n3 > 0) k_vertex_face_count<<<static_cast<unsigned>(ceil_div(n3, 256)), 256, 0, s>>>(d_faces, face_count, V, count.ptr, flag.ptr);
 	{   // validate every index before anything gathers through the faces (the fill and the sums index by them)
@@ -199,7 +178,7 @@ nnrt_status nnrt_compute_vertex_normals(const float* d_vertices, int64_t vertex_
 			return NNRT_ERROR_ARGUMENT;
 		}
 	}
-	k_exclusive_scan<<<1, 1024, 0, s>>>(count.ptr, V, offsets.ptr);
+	if ((st = exclusive_sum(count.ptr, offsets.ptr, V + 1, tmp, s))) return st;
 	NNRT_HIP(hipMemsetAsync(count.ptr, 0, sizeof(int) * V, s));
 	if (n3 > 0) k_vertex_face_fill<<<static_cast<unsigned>(ceil_div(n3, 256)), 256, 0, s>>>(d_faces, face_count, offsets.ptr, count.ptr, list.ptr);
 	k_vertex_normals<<<static_cast<unsigned>(ceil_div(V, 256)), 256, 0, s>>>(d_vertices, d_faces, V, offsets.ptr, list.ptr, normalized, d_out);

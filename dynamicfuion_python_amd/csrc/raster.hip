@@ -8,9 +8,9 @@
 // recomputes the winner's barycentrics/depth with the same device function, bit-identically.
 // faces_per_pixel > 1 (API only): per-pixel lists of the faces that pass the full test at the pixel centre (count, scan,
 // fill), each replayed in ascending face order through the reference's bounded queue.
+#include "device_primitives.hpp"
 #include "kernels.hpp"
 
-#include <hipcub/hipcub.hpp>
 #include <cstdlib>
 
 namespace nnrt {
@@ -654,16 +654,13 @@ nnrt_status launch_raster_multi(const float* face_ndc, const uint8_t* mask, int6
 	StreamScratch<int> counts, offsets;
 	StreamScratch<int32_t> lists;
 	StreamScratch<uint8_t> tmp;
-	size_t tmp_bytes = 0;
 	nnrt_status st;
 	if ((st = counts.alloc(static_cast<size_t>(P) + 1, stream)) || (st = offsets.alloc(static_cast<size_t>(P) + 1, stream))) return st;
 	NNRT_HIP(hipMemsetAsync(counts.ptr, 0, sizeof(int) * (P + 1), stream));
 	const unsigned fg = static_cast<unsigned>(ceil_div(F > 0 ? F : 1, 256));
 	if (F > 0) k_hit_lists<false><<<fg, 256, 0, stream>>>(face_ndc, mask, F, o, counts.ptr, nullptr, nullptr);
 	NNRT_LAUNCH_CHECK();
-	NNRT_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, tmp_bytes, counts.ptr, offsets.ptr, static_cast<int>(P + 1), stream));
-	if ((st = tmp.alloc(tmp_bytes, stream))) return st;
-	NNRT_HIP(hipcub::DeviceScan::ExclusiveSum(tmp.ptr, tmp_bytes, counts.ptr, offsets.ptr, static_cast<int>(P + 1), stream));
+	if ((st = exclusive_sum(counts.ptr, offsets.ptr, P + 1, tmp, stream))) return st;
 	int total = 0;
 	NNRT_HIP(hipMemcpyAsync(&total, offsets.ptr + P, sizeof(int), hipMemcpyDeviceToHost, stream));
 	NNRT_HIP(hipMemsetAsync(counts.ptr, 0, sizeof(int) * (P + 1), stream));

@@ -17,8 +17,7 @@
 #include <cmath>
 #include <cstring>
 
-#include <hipcub/hipcub.hpp>
-
+#include "device_primitives.hpp"
 #include "kernels.hpp"
 
 namespace nnrt {
@@ -404,21 +403,13 @@ nnrt_status build_cell_index(CellIndex& ix, const float* pts, int n, float cell,
 	    (st = ix.cell_keys.ensure(n)) || (st = ix.cell_start.ensure(static_cast<size_t>(n) + 1)) || (st = ix.cell_rank.ensure(n)) ||
 	    (st = ix.ctrl.ensure(2)))
 		return st;
-	size_t sort_bytes = 0, scan_bytes = 0;
-	NNRT_HIP(hipcub::DeviceRadixSort::SortPairs(nullptr, sort_bytes, keys.ptr, keys_sorted.ptr, order.ptr, order_sorted.ptr, n, 0, 3 * CELL_BITS, s));
-	NNRT_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, scan_bytes, head.ptr, head_scan.ptr, n, s));
-	size_t tmp_bytes = std::max<size_t>(std::max(sort_bytes, scan_bytes), 1);
-	if ((st = tmp.ensure(tmp_bytes))) return st;
 	NNRT_HIP(hipMemsetAsync(ix.ctrl.ptr, 0, 2 * sizeof(int), s));
 	k_index_keys<<<gblocks(n), GB, 0, s>>>(pts, n, cell, offset[0], offset[1], offset[2], keys.ptr, order.ptr, ix.ctrl.ptr);
 	NNRT_LAUNCH_CHECK();
-	NNRT_HIP(hipcub::DeviceRadixSort::SortPairs(tmp.ptr, sort_bytes, keys.ptr, keys_sorted.ptr, order.ptr, order_sorted.ptr, n, 0, 3 * CELL_BITS, s));
+	if ((st = sort_pairs(keys.ptr, keys_sorted.ptr, order.ptr, order_sorted.ptr, n, 3 * CELL_BITS, tmp, s))) return st;
 	k_index_heads<<<gblocks(n), GB, 0, s>>>(keys_sorted.ptr, order_sorted.ptr, n, head.ptr, first.ptr);
 	NNRT_LAUNCH_CHECK();
-	size_t bytes = tmp_bytes;
-	NNRT_HIP(hipcub::DeviceScan::ExclusiveSum(tmp.ptr, bytes, head.ptr, head_scan.ptr, n, s));
-	bytes = tmp_bytes;
-	NNRT_HIP(hipcub::DeviceScan::ExclusiveSum(tmp.ptr, bytes, first.ptr, first_scan.ptr, n, s));
+	if ((st = exclusive_sum(head.ptr, head_scan.ptr, n, tmp, s)) || (st = exclusive_sum(first.ptr, first_scan.ptr, n, tmp, s))) return st;
 	k_index_cells<<<gblocks(n), GB, 0, s>>>(pts, keys_sorted.ptr, order_sorted.ptr, head.ptr, head_scan.ptr, first_scan.ptr, n, ix.pos.ptr,
 	                                        ix.cell_keys.ptr, ix.cell_start.ptr, ix.cell_rank.ptr, ix.ctrl.ptr);
 	NNRT_LAUNCH_CHECK();
@@ -440,11 +431,7 @@ nnrt_status select_flagged_points(const uint8_t* flags, int n, int cells, int64_
 	DeviceBuffer<uint8_t> tmp;
 	nnrt_status st;
 	if ((st = d_count.ensure(1))) return st;
-	hipcub::CountingInputIterator<int64_t> idx(0);
-	size_t bytes = 0;
-	NNRT_HIP(hipcub::DeviceSelect::Flagged(nullptr, bytes, idx, flags, out, d_count.ptr, n, s));
-	if ((st = tmp.ensure(std::max<size_t>(bytes, 1)))) return st;
-	NNRT_HIP(hipcub::DeviceSelect::Flagged(tmp.ptr, bytes, idx, flags, out, d_count.ptr, n, s));
+	if ((st = select_flagged_indices(flags, out, d_count.ptr, n, tmp, s))) return st;
 	NNRT_HIP(hipMemcpyAsync(h_count, d_count.ptr, sizeof(int64_t), hipMemcpyDeviceToHost, s));
 	NNRT_HIP(hipStreamSynchronize(s));
 	if (*h_count != cells) {

@@ -11,8 +11,6 @@
 //                voxel (x, y, z) of a block at x + res (y + res z) (Open3D ArrayIndexer order)
 // Activation is deterministic: every key takes the lowest input index that carries it (atomicMin), new keys get buffer
 // indices by a prefix sum in input order -- so block order, and everything derived from it, is reproducible.
-#include <hipcub/hipcub.hpp>
-
 #include <algorithm>
 #include <cfloat>
 #include <climits>
@@ -22,6 +20,7 @@
 #include <type_traits>
 #include <vector>
 
+#include "device_primitives.hpp"
 #include "kernels.hpp"
 #include "mc_table.hpp"
 
@@ -1019,7 +1018,7 @@ struct nnrt_voxel_grid {
 	DeviceBuffer<uint64_t> s_slot, s_packed;
 	DeviceBuffer<int> s_flag, s_rank, s_nbr, s_ntri, s_toff, s_vidx, s_eflag, s_found, s_blocks;
 	DeviceBuffer<uint8_t> s_cube, s_mask;
-	DeviceBuffer<unsigned char> s_cub;
+	DeviceBuffer<uint8_t> s_cub;
 	DeviceBuffer<int32_t> s_coords;
 	DeviceBuffer<float> s_boxes, s_rows_all;
 	DeviceBuffer<Seg> s_segs;
@@ -1051,23 +1050,6 @@ struct nnrt_voxel_grid {
 };
 
 namespace {
-// exclusive prefix sum of n ints; returns the total on the host (synchronizes the stream)
-nnrt_status scan_total(nnrt_voxel_grid* vg, const int* in, int* out, int64_t n, hipStream_t s, int64_t* total) {
-	*total = 0;
-	if (n == 0) return NNRT_OK;
-	size_t bytes = 0;
-	NNRT_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, bytes, in, out, static_cast<int>(n), s));
-	nnrt_status st = vg->s_cub.ensure(bytes);
-	if (st) return st;
-	NNRT_HIP(hipcub::DeviceScan::ExclusiveSum(vg->s_cub.ptr, bytes, in, out, static_cast<int>(n), s));
-	int last[2] = {0, 0};
-	NNRT_HIP(hipMemcpyAsync(&last[0], out + n - 1, sizeof(int), hipMemcpyDeviceToHost, s));
-	NNRT_HIP(hipMemcpyAsync(&last[1], in + n - 1, sizeof(int), hipMemcpyDeviceToHost, s));
-	NNRT_HIP(hipStreamSynchronize(s));
-	*total = static_cast<int64_t>(last[0]) + last[1];
-	return NNRT_OK;
-}
-
 nnrt_status rebuild_table(nnrt_voxel_grid* vg, uint64_t size, hipStream_t s) {
 	nnrt_status st;
 	if ((st = vg->hkeys.ensure(size)) || (st = vg->hblock.ensure(size)) || (st = vg->hfirst.ensure(size))) return st;
@@ -1137,7 +1119,7 @@ nnrt_status activate_keys(nnrt_voxel_grid* vg, const int32_t* coords, const uint
 	k_mark_new<<<grid_of(n), 256, 0, s>>>(g.hash, vg->s_slot.ptr, n, vg->s_flag.ptr);
 	NNRT_LAUNCH_CHECK();
 	int64_t total = 0;
-	if ((st = scan_total(vg, vg->s_flag.ptr, vg->s_rank.ptr, n, s, &total))) return st;
+	if ((st = exclusive_sum_total(vg->s_flag.ptr, vg->s_rank.ptr, n, vg->s_cub, s, &total))) return st;
 	// a call with an out-of-range coordinate is refused as a whole: its in-range keys already sit in the table (without
 	// a block), so the table is rebuilt from the block keys and the grid is as it was before the call
 	if (d_error && (st = take_error(d_error, s))) {
@@ -1179,7 +1161,7 @@ nnrt_status unique_packed(nnrt_voxel_grid* vg, const uint64_t* packed, int64_t n
 	k_mark_first<<<grid_of(n), 256, 0, s>>>(h, vg->s_slot.ptr, n, vg->s_flag.ptr);
 	NNRT_LAUNCH_CHECK();
 	int64_t total = 0;
-	if ((st = scan_total(vg, vg->s_flag.ptr, vg->s_rank.ptr, n, s, &total))) return st;
+	if ((st = exclusive_sum_total(vg->s_flag.ptr, vg->s_rank.ptr, n, vg->s_cub, s, &total))) return st;
 	if ((st = vg->r_coords.ensure(3 * static_cast<size_t>(std::max<int64_t>(total, 1))))) return st;
 	k_unique_compact<<<grid_of(n), 256, 0, s>>>(h, packed, vg->s_slot.ptr, vg->s_flag.ptr, vg->s_rank.ptr, n, vg->r_coords.ptr);
 	NNRT_LAUNCH_CHECK();
@@ -1236,7 +1218,7 @@ nnrt_status inactive_neighbors(nnrt_voxel_grid* vg, hipStream_t s, int64_t* n_al
 nnrt_status compact_found_coords(nnrt_voxel_grid* vg, int64_t n, hipStream_t s) {
 	int64_t total = 0;
 	nnrt_status st;
-	if ((st = scan_total(vg, vg->s_found.ptr, vg->s_rank.ptr, n, s, &total))) return st;
+	if ((st = exclusive_sum_total(vg->s_found.ptr, vg->s_rank.ptr, n, vg->s_cub, s, &total))) return st;
 	if ((st = vg->r_coords.ensure(3 * static_cast<size_t>(std::max<int64_t>(total, 1))))) return st;
 	if (n > 0) k_compact_coords<<<grid_of(n), 256, 0, s>>>(vg->s_coords.ptr, vg->s_found.ptr, vg->s_rank.ptr, n, vg->r_coords.ptr);
 	NNRT_LAUNCH_CHECK();
@@ -1455,7 +1437,7 @@ nnrt_status nnrt_voxel_grid_extract_voxel_values_at(nnrt_voxel_grid* vg, const i
 	k_found_mask<<<grid_of(count), 256, 0, s>>>(g, d_query, count, vg->s_found.ptr);
 	NNRT_LAUNCH_CHECK();
 	int64_t total = 0;
-	if ((st = scan_total(vg, vg->s_found.ptr, vg->s_rank.ptr, count, s, &total))) return st;
+	if ((st = exclusive_sum_total(vg->s_found.ptr, vg->s_rank.ptr, count, vg->s_cub, s, &total))) return st;
 	if ((st = vg->r_rows.ensure(static_cast<size_t>(std::max<int64_t>(total, 1)) * C))) return st;
 	k_compact_rows<<<grid_of(count), 256, 0, s>>>(vg->s_rows_all.ptr, vg->s_found.ptr, vg->s_rank.ptr, count, C, vg->r_rows.ptr);
 	NNRT_LAUNCH_CHECK();
@@ -1579,8 +1561,8 @@ nnrt_status nnrt_voxel_grid_extract_triangle_mesh(nnrt_voxel_grid* vg, float wei
 	k_mc_cubes<<<grid_of(nvox), 256, 0, s>>>(m, nb, vg->s_cube.ptr, vg->s_ntri.ptr, vg->s_eflag.ptr);
 	NNRT_LAUNCH_CHECK();
 	int64_t nv = 0, nt = 0;
-	if ((st = scan_total(vg, vg->s_eflag.ptr, vg->s_vidx.ptr, 3 * nvox, s, &nv))) return st;
-	if ((st = scan_total(vg, vg->s_ntri.ptr, vg->s_toff.ptr, nvox, s, &nt))) return st;
+	if ((st = exclusive_sum_total(vg->s_eflag.ptr, vg->s_vidx.ptr, 3 * nvox, vg->s_cub, s, &nv))) return st;
+	if ((st = exclusive_sum_total(vg->s_ntri.ptr, vg->s_toff.ptr, nvox, vg->s_cub, s, &nt))) return st;
 	if ((st = vg->r_vpos.ensure(3 * static_cast<size_t>(std::max<int64_t>(nv, 1)))) || (st = vg->r_vnrm.ensure(3 * static_cast<size_t>(std::max<int64_t>(nv, 1)))) ||
 	    (st = vg->r_vcol.ensure(3 * static_cast<size_t>(std::max<int64_t>(nv, 1)))) || (st = vg->r_tris.ensure(3 * static_cast<size_t>(std::max<int64_t>(nt, 1)))))
 		return st;
