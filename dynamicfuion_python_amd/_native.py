@@ -113,6 +113,9 @@ _SIGNATURES = {
     "nnrt_fitter_set_step_objective": (c_int32, [c_void_p, c_int32]),
     "nnrt_fitter_get_step_objective": (c_int32, [c_void_p, ctypes.POINTER(c_int32)]),
     "nnrt_fitter_get_raw_residuals": (c_int32, [c_void_p, c_void_p, c_int64, c_void_p]),
+    "nnrt_fitter_set_landmarks": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_float, c_float, c_void_p]),
+    "nnrt_fitter_get_landmark_distances": (c_int32, [c_void_p, c_void_p, c_int64, c_void_p]),
+    "nnrt_fitter_landmark_info": (c_int32, [c_void_p, c_void_p, c_int64]),
     "nnrt_fitter_get_coupled_system": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_void_p]),
     "nnrt_fitter_set_anchor_graph": (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_void_p]),
     "nnrt_fitter_check": (c_int32, [c_void_p, c_void_p]),

@@ -57,6 +57,10 @@ class RenderingAlignmentParameters:
     # and step control run together: what real sequences want.
     step_control: Optional[A.StepControl] = None
     step_objective: A.StepObjective = A.StepObjective.SQUARE
+    # The landmark term (DeformableMeshToImageFitter.set_landmarks) of optimize_graph(landmarks=...):
+    # the fitter-wide residual weight (1.0 is untuned on any real sequence) and the distance cutoff in metres (0: none).
+    landmark_term_weight: float = 1.0
+    landmark_cutoff: float = 0.0
 
 
 def as_triangle_mesh(mesh) -> G.TriangleMesh:
@@ -99,12 +103,21 @@ class RenderingAlignmentOptimizer:
         every later optimize_graph call (AnchorComputationMode.SHORTEST_PATH); None: Euclidean anchors."""
         self.fitter.set_anchor_graph(edges)
 
-    def optimize_graph(self, graph: G.HierarchicalGraphWarpField, tsdf, target_points, target_rgb=None, extrinsics=None):
+    def optimize_graph(self, graph: G.HierarchicalGraphWarpField, tsdf, target_points, target_rgb=None, landmarks=None, extrinsics=None):
         """tsdf: an object with extract_surface_mesh(-1, 0) (NonRigidSurfaceVoxelBlockGrid) or the canonical mesh
         itself; target_points: organized [H,W,3] / [H*W,3] camera-space points (z <= 0 or non-finite = no target);
-        extrinsics: the 4 x 4 world -> camera matrix the fitter applies to the mesh (None: identity)."""
+        extrinsics: the 4 x 4 world -> camera matrix the fitter applies to the mesh (None: identity);
+        landmarks: (vertex_indices, targets, weights | None) for this fit (A.landmarks_from_pixel_matches makes one from
+        2-D matches), None or an empty set: no landmark term."""
         mesh = tsdf.extract_surface_mesh(-1, 0) if hasattr(tsdf, "extract_surface_mesh") else tsdf
         mesh = as_triangle_mesh(mesh)
+        if landmarks is not None and not (isinstance(landmarks, (tuple, list)) and len(landmarks) in (2, 3)):
+            raise TypeError("landmarks must be a (vertex_indices, targets, weights | None) tuple; pass extrinsics by keyword")
+        if landmarks is not None and len(landmarks[0]) > 0:
+            self.fitter.set_landmarks(landmarks[0], landmarks[1], landmarks[2] if len(landmarks) > 2 else None,
+                                      self.parameters.landmark_term_weight, self.parameters.landmark_cutoff)
+        else:
+            self.fitter.clear_landmarks()
         H, W = self.image_size_hw
         pts = target_points.detach() if isinstance(target_points, torch.Tensor) else torch.as_tensor(np.asarray(target_points))
         pts = pts.to(torch.float32).reshape(H * W, 3)

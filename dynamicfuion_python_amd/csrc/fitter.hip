@@ -13,6 +13,7 @@
 
 #include "coupled.hpp"
 #include "handles.hpp"
+#include "landmarks.hpp"
 #include "step_control.hpp"
 
 using namespace nnrt;
@@ -105,6 +106,9 @@ struct nnrt_fitter {
 	// k_step_cost's place and leaves the raw residuals it resolved in step_raw (allocated by prepare() in that mode)
 	int32_t step_objective = NNRT_STEP_OBJECTIVE_SQUARE;
 	DeviceBuffer<float> step_raw;                  // [P]
+	// nnrt_fitter_set_landmarks: the landmarks of the next fit and, once a frame is prepared, their
+	// associations grouped by node and by pair (lm.L == 0: none set, and every launch is as without them)
+	LandmarkSet lm;
 	int last_mode = 0;
 	DeviceBuffer<float> snapshot;   // [N,16] node state stored by nnrt_fitter_snapshot_motion (restore-before-iteration runs)
 	// nnrt_fitter_set_anchor_graph: edge rows [graph_nodes, graph_degree] in the warp field's virtual node order (checked
@@ -366,6 +370,7 @@ StepCostArgs step_cost_args(const nnrt_fitter* ft, const float* state_in) {
 	ca.lambda_min = ft->step.lambda_min;
 	ca.lambda_max = ft->step.lambda_max;
 	ca.relative_cost_tolerance = ft->step.relative_cost_tolerance;
+	ca.landmark_cost = ft->lm.L > 0 ? ft->lm.cost.ptr : nullptr;
 	return ca;
 }
 
@@ -388,6 +393,42 @@ StepCostRobustArgs step_cost_robust_args(const nnrt_fitter* ft, const FitPixelAr
 	ra.pixel_face = fa.pixel_face;
 	ra.raw = ft->step_raw.ptr;
 	return ra;
+}
+
+// k_fit_landmarks' arguments (landmarks set and grouped by prepare())
+FitLandmarkArgs fit_landmark_args(const nnrt_fitter* ft, const float* state_in, bool from_identity) {
+	const LandmarkSet& lm = ft->lm;
+	FitLandmarkArgs la{};
+	la.L = static_cast<int>(lm.L);
+	la.K = ft->key.K;
+	la.term_weight = lm.term_weight;
+	la.cutoff = lm.cutoff;
+	la.state_identity = from_identity;
+	la.index = lm.index.ptr;
+	la.target = lm.target.ptr;
+	la.weight = lm.weight.ptr;
+	la.anchors = ft->anchors.ptr;
+	la.weights = ft->weights.ptr;
+	la.mesh_p = ft->mesh_p.ptr;
+	la.wpos = ft->wpos.ptr;
+	la.state_in = state_in;
+	la.node_keys = lm.node.keys.ptr;
+	la.node_vals = lm.node.vals.ptr;
+	la.node_starts = lm.node.starts.ptr;
+	la.pair_keys = lm.pair.keys.ptr;
+	la.pair_vals = lm.pair.vals.ptr;
+	la.pair_starts = lm.pair.starts.ptr;
+	la.info = lm.info.ptr;
+	la.acc = ft->acc.ptr;
+	la.distances = lm.distances.ptr;
+	la.cost = lm.cost.ptr;
+	constexpr int RUNS_PER_BLOCK = 8;
+	la.node_blocks = static_cast<int>(ceil_div(landmark_node_run_bound(lm.L, la.K, ft->key.N), RUNS_PER_BLOCK));
+	if (ft->key.coupled && ft->ps.M > 0) {
+		la.pair_acc = ft->pair_acc.ptr;
+		la.pair_blocks = static_cast<int>(ceil_div(landmark_pair_run_bound(lm.L, la.K, ft->ps.M), RUNS_PER_BLOCK));
+	}
+	return la;
 }
 
 // the block-diagonal solve + update's, with the damping as a launch argument or a device word
@@ -459,6 +500,8 @@ nnrt_status enqueue_iteration(nnrt_fitter* ft, const nnrt_warp_field* wf, int mo
 		NNRT_HIP(hipMemsetAsync(ft->pair_acc.ptr, 0, sizeof(double) * 36 * static_cast<size_t>(ft->ps.M), s));
 		if ((st = launch_fit_pairs(fa, FitPairArgs{ft->ps.row_off.ptr, ft->ps.pairs.ptr, ft->pair_acc.ptr, 0}, ft->ps.M, s))) return st;
 	}
+	// the landmark term: its sums join the data term's in acc (and pair_acc) before anything reads them
+	if (ft->lm.L > 0 && (stages & STAGE_PIXEL) && (st = launch_fit_landmarks(fit_landmark_args(ft, state_in, from_identity), s))) return st;
 	if ((st = mark(4))) return st;
 	if (!(stages & STAGE_SOLVE)) return mark(6);
 	if ((st = mark(5))) return st;
@@ -759,6 +802,26 @@ static nnrt_status build_coupled_structure(nnrt_fitter* ft, const nnrt_warp_fiel
 	return NNRT_OK;
 }
 
+// The landmarks of this fit against this frame's mesh and anchors: their associations grouped by node and, in coupled
+// mode, by pair (group_landmarks waits for the work stream: the refusals are the host's to report).
+static nnrt_status build_landmark_structure(nnrt_fitter* ft, const FrameKey& key, hipStream_t s, bool* moved) {
+	if (ft->lm.L == 0) return NNRT_OK;
+	LandmarkFrame fr{};
+	fr.V = key.V;
+	fr.F = key.F;
+	fr.N = key.N;
+	fr.K = key.K;
+	fr.faces4 = ft->faces4.ptr;
+	fr.anchors = ft->anchors.ptr;
+	fr.coupled = key.coupled;
+	fr.M = key.coupled ? ft->ps.M : 0;
+	fr.row_off = ft->ps.row_off.ptr;
+	fr.pairs = ft->ps.pairs.ptr;
+	nnrt_status st = allocate_landmark_groups(ft->lm, fr, moved);
+	if (!st) st = group_landmarks(ft->lm, fr, s);
+	return st;
+}
+
 // the image side of the frame on the work stream: reference points, the pixel launch's order table, the raster keys and
 // the accumulators, step control's restart
 static nnrt_status enqueue_reference_setup(nnrt_fitter* ft, const FrameKey& key, const FrameReference& ref, hipStream_t s) {
@@ -802,7 +865,8 @@ nnrt_status prepare_frame(nnrt_fitter* ft, nnrt_warp_field* wf, const FrameInput
 	if ((st = allocate_frame(ft, key, &graphs.stale)) || (st = build_arap_structure(ft, wf, key, &graphs.stale))) return st;
 	hipStream_t us = static_cast<hipStream_t>(stream), s = ft->work;
 	WorkScope scope(ft, us);   // the work stream runs after the caller's stream, and the caller's after it again on every return
-	if ((st = scope.enter()) || (st = enqueue_mesh_setup(ft, wf, key, in, s)) || (st = build_coupled_structure(ft, wf, key, s, &graphs.stale)))
+	if ((st = scope.enter()) || (st = enqueue_mesh_setup(ft, wf, key, in, s)) || (st = build_coupled_structure(ft, wf, key, s, &graphs.stale)) ||
+	    (st = build_landmark_structure(ft, key, s, &graphs.stale)))
 		return st;
 	// the key is complete: any other change of what the graphs bake in drops them too
 	if (std::memcmp(&key, &ft->key, sizeof(key)) != 0) graphs.stale = true;
@@ -1207,6 +1271,78 @@ nnrt_status nnrt_fitter_get_raw_residuals(nnrt_fitter* ft, float* h_out, int64_t
 	NNRT_HIP(hipStreamSynchronize(static_cast<hipStream_t>(stream)));
 	NNRT_HIP(hipStreamSynchronize(ft->work));
 	NNRT_HIP(hipMemcpy(h_out, ft->step_raw.ptr, sizeof(float) * static_cast<size_t>(count), hipMemcpyDeviceToHost));
+	return NNRT_OK;
+}
+
+nnrt_status nnrt_fitter_set_landmarks(nnrt_fitter* ft, const int32_t* d_vertex_indices, const float* d_targets, const float* d_weights, int64_t count,
+                                      float term_weight, float cutoff, void* stream) {
+	// the ranges first: they need no fitter
+	NNRT_CHECK_ARG(count >= 0 && count < (int64_t(1) << 24), "landmarks: count must lie in [0, 2^24)");
+	NNRT_CHECK_ARG(std::isfinite(term_weight) && term_weight > 0.f, "landmarks: term_weight must be finite and > 0");
+	NNRT_CHECK_ARG(std::isfinite(cutoff), "landmarks: cutoff must be finite (<= 0: no cutoff)");
+	NNRT_CHECK_ARG(count == 0 || (d_vertex_indices && d_targets), "landmarks: null d_vertex_indices or d_targets");
+	NNRT_CHECK_ARG(ft, "null pointer");
+	if (count > 0)
+		for (int i = 0; i < ft->p.iteration_mode_count; i++)
+			NNRT_CHECK_ARG(ft->p.iteration_modes[i] == NNRT_ITERATION_ALL,
+			               "landmarks support IterationMode ALL only (6x6 blocks), and the fitter's mode list holds another");
+	LandmarkSet& lm = ft->lm;
+	if (count == 0 && lm.L == 0) return NNRT_OK;
+	DeviceGuard guard(ft->device);
+	hipStream_t us = static_cast<hipStream_t>(stream);
+	NNRT_HIP(hipStreamSynchronize(ft->work));
+	ft->prepared = false;   // the grouping by node and by pair is prepare()'s
+	if (count == 0) {
+		NNRT_HIP(hipStreamSynchronize(us));   // (an iteration enqueued there may still read the buffers)
+		ft->drop_graphs();
+		lm.release_all();
+		return NNRT_OK;
+	}
+	// the captured sequences bake the count (their grids), the two settings and the buffers' addresses
+	bool moved = lm.L != count || lm.term_weight != term_weight || lm.cutoff != cutoff;
+	const size_t L = static_cast<size_t>(count);
+	nnrt_status st;
+	if ((st = ensure(lm.index, L, &moved)) || (st = ensure(lm.target, 3 * L, &moved)) || (st = ensure(lm.weight, L, &moved)) ||
+	    (st = ensure(lm.distances, L, &moved)) || (st = ensure(lm.cost, 1, &moved))) {
+		ft->drop_graphs();
+		lm.L = 0;
+		return st;
+	}
+	if (moved) ft->drop_graphs();
+	lm.L = count;
+	lm.term_weight = term_weight;
+	lm.cutoff = cutoff;
+	for (auto& v : lm.h_info) v = 0;
+	NNRT_HIP(hipMemcpyAsync(lm.index.ptr, d_vertex_indices, sizeof(int32_t) * L, hipMemcpyDeviceToDevice, us));
+	NNRT_HIP(hipMemcpyAsync(lm.target.ptr, d_targets, sizeof(float) * 3 * L, hipMemcpyDeviceToDevice, us));
+	if (d_weights) NNRT_HIP(hipMemcpyAsync(lm.weight.ptr, d_weights, sizeof(float) * L, hipMemcpyDeviceToDevice, us));
+	else NNRT_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(lm.weight.ptr), 0x3f800000, L, us));   // 1.0f
+	// what nnrt_fitter_get_landmark_distances reads before the first iteration: zeros
+	NNRT_HIP(hipMemsetAsync(lm.distances.ptr, 0, sizeof(float4) * L, us));
+	NNRT_HIP(hipMemsetAsync(lm.cost.ptr, 0, sizeof(double), us));
+	return NNRT_OK;
+}
+
+nnrt_status nnrt_fitter_get_landmark_distances(nnrt_fitter* ft, float* h_out, int64_t count, void* stream) {
+	NNRT_CHECK_ARG(ft && h_out, "null pointer");
+	NNRT_CHECK_ARG(ft->lm.L > 0 && ft->lm.distances.ptr, "no landmarks set");
+	// the host buffer holds 4 * count floats: a mismatch with the landmark count is refused, not written past
+	NNRT_CHECK_ARG(count == ft->lm.L, "count differs from the number of landmarks set");
+	DeviceGuard guard(ft->device);
+	NNRT_HIP(hipStreamSynchronize(static_cast<hipStream_t>(stream)));
+	NNRT_HIP(hipStreamSynchronize(ft->work));
+	NNRT_HIP(hipMemcpy(h_out, ft->lm.distances.ptr, sizeof(float4) * static_cast<size_t>(count), hipMemcpyDeviceToHost));
+	return NNRT_OK;
+}
+
+nnrt_status nnrt_fitter_landmark_info(const nnrt_fitter* ft, int64_t* h_out, int64_t out_count) {
+	NNRT_CHECK_ARG(ft && h_out, "null pointer");
+	NNRT_CHECK_ARG(out_count >= 4, "out_count must be at least 4");
+	const bool grouped = ft->prepared && ft->lm.L > 0;
+	h_out[0] = ft->lm.L;
+	h_out[1] = grouped ? ft->lm.h_info[LM_INFO_ASSOC] : 0;
+	h_out[2] = grouped ? ft->lm.h_info[LM_INFO_RUNS] : 0;
+	h_out[3] = grouped ? ft->lm.h_info[LM_INFO_PAIR_ASSOC] : 0;
 	return NNRT_OK;
 }
 

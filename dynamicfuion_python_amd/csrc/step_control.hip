@@ -45,6 +45,7 @@ __device__ __forceinline__ void step_cost_finish(const StepCostArgs& a, double s
 			StepState* st = a.st;
 			double c = 0.0;
 			for (int b = 0; b < a.blocks; b++) c += a.partials[b];
+			if (a.landmark_cost) c += *a.landmark_cost;   // the same in both objectives
 			float lambda = st->lambda;
 			double c_best = st->c_best;
 			int done = st->done, retry = st->retry, hold, decision, copy = 0;

@@ -43,6 +43,7 @@ struct StepCostArgs {
 	StepState* st;
 	const int* error_flag;
 	float increase, decrease, lambda_min, lambda_max, relative_cost_tolerance;
+	const double* landmark_cost;   // the landmark term's cost of the same state (k_fit_landmarks; null: no landmarks set)
 };
 
 // k_step_cost_robust (NNRT_STEP_OBJECTIVE_ROBUST): base.blocks / base.chunk are those of P + E items

@@ -223,6 +223,11 @@ class FrameResult:
     iterations_used: int = 0
     final_cost: float = 0.0
     rejected_step_count: int = 0
+    # FusionPipeline(landmark_provider=...) (0 without one): the landmarks the provider gave for this frame, those active
+    # at the state the fit's last iteration started from, and the RMS of their distances |warped vertex - target| (metres)
+    landmark_count: int = 0
+    landmark_active_count: int = 0
+    landmark_rmse: float = 0.0
 
 
 def remap_edges_to_node_order(edges, order) -> np.ndarray:
@@ -243,7 +248,12 @@ def remap_edges_to_node_order(edges, order) -> np.ndarray:
 
 class FusionPipeline:
     def __init__(self, sequence: FrameSequenceDataset, parameters: Optional[FusionParameters] = None, nodes=None,
-                 device: Optional[int] = None):
+                 device: Optional[int] = None, landmark_provider=None):
+        """landmark_provider: a callable (pipeline, frame, canonical_mesh, point_image) -> (vertex_indices, targets,
+        weights | None) | None, called for every tracked frame before its non-rigid fit: the sparse correspondences of the
+        fit's landmark term (nnrt.alignment.landmarks_from_pixel_matches makes the tuple from 2-D
+        matches). None: no landmark term."""
+        self.landmark_provider = landmark_provider
         self.parameters = p = parameters or FusionParameters()
         if p.tracking_method == TrackingMethod.NEURAL:
             raise NotImplementedError("TrackingMethod.NEURAL (DeformNet) is not part of this build; use TrackingMethod.RENDERING")
@@ -508,8 +518,16 @@ class FusionPipeline:
                 res.rigid_correspondence_count, res.rigid_inlier_rmse = rigid.correspondence_count, rigid.inlier_rmse
                 res.rigid_photometric_count, res.rigid_photometric_rmse = rigid.photometric_count, rigid.photometric_rmse
             if res.canonical_triangle_count > 0:
-                self.optimizer.optimize_graph(self.active_graph, canonical, points, extrinsics=self.extrinsics)
+                landmarks = self.landmark_provider(self, frame, canonical, points) if self.landmark_provider is not None else None
+                if landmarks is not None and len(landmarks[0]) == 0:
+                    landmarks = None
+                self.optimizer.optimize_graph(self.active_graph, canonical, points, extrinsics=self.extrinsics, landmarks=landmarks)
                 res.tracked = True
+                if landmarks is not None:
+                    distances, active = self.optimizer.fitter.landmark_distances()
+                    res.landmark_count, res.landmark_active_count = len(active), int(active.sum())
+                    if active.any():
+                        res.landmark_rmse = float(np.sqrt((distances[active].astype(np.float64) ** 2).sum(axis=1).mean()))
                 summary = self.optimizer.last_step_summary
                 if summary is not None:
                     res.iterations_used, res.final_cost = summary["iterations_used"], summary["final_cost"]

@@ -106,6 +106,48 @@ def summarize_step_history(history) -> dict:
     return dict(iterations_used=used, final_cost=float(final_cost), rejected_step_count=rejected, done=done)
 
 
+def landmarks_from_pixel_matches(pixel_face_indices, pixel_barycentric_coordinates, triangle_indices, source_uv, target_uv, target_point_image,
+                                 weights=None):
+    """2-D matches -> the (vertex_indices, targets, weights | None) tuple DeformableMeshToImageFitter.set_landmarks and
+    RenderingAlignmentOptimizer.optimize_graph(landmarks=...) take: the bridge from optical flow or keypoint matches.
+
+    pixel_face_indices [H, W] (or [H, W, 1]; < 0: background) and pixel_barycentric_coordinates [H, W, 3] (or
+    [H, W, 1, 3]) are a render of the warped model, triangle_indices [F, 3] its faces; source_uv / target_uv [M, 2] integer
+    pixel coordinates (u = column, v = row) in that render and in the live frame, target_point_image [H', W', 3] the live
+    frame's camera-space points. Each match takes, from its source pixel, the face vertex with the largest barycentric
+    weight as the vertex, and the target pixel's point as the target. A match whose source pixel is background (or off the
+    render), or whose target point is off the image, non-finite or has z <= 0, is dropped. Torch only; the results stay on
+    the inputs' device."""
+    faces = torch.as_tensor(pixel_face_indices)
+    dev = faces.device
+    faces = faces.reshape(faces.shape[0], faces.shape[1], -1)[..., 0].to(torch.int64)
+    H, W = faces.shape
+    bary = torch.as_tensor(pixel_barycentric_coordinates).to(dev).reshape(H, W, -1)[..., :3]
+    tri = torch.as_tensor(triangle_indices).to(dev).to(torch.int64).reshape(-1, 3)
+    src = torch.as_tensor(source_uv).to(dev).to(torch.int64).reshape(-1, 2)
+    tgt = torch.as_tensor(target_uv).to(dev).to(torch.int64).reshape(-1, 2)
+    points = torch.as_tensor(target_point_image).to(dev).to(torch.float32)
+    Ht, Wt = points.shape[0], points.shape[1]
+    points = points.reshape(Ht, Wt, 3)
+    if src.shape[0] != tgt.shape[0]:
+        raise ValueError(f"{src.shape[0]} source pixels but {tgt.shape[0]} target pixels")
+    w = None
+    if weights is not None:
+        w = torch.as_tensor(weights).to(dev).to(torch.float32).reshape(-1)
+        if w.shape[0] != src.shape[0]:
+            raise ValueError(f"{src.shape[0]} matches but {w.shape[0]} weights")
+    inside = (src[:, 0] >= 0) & (src[:, 0] < W) & (src[:, 1] >= 0) & (src[:, 1] < H) & (tgt[:, 0] >= 0) & (tgt[:, 0] < Wt) & (tgt[:, 1] >= 0) & \
+             (tgt[:, 1] < Ht)
+    su, sv = src[:, 0].clamp(0, W - 1), src[:, 1].clamp(0, H - 1)
+    tu, tv = tgt[:, 0].clamp(0, Wt - 1), tgt[:, 1].clamp(0, Ht - 1)
+    face = faces[sv, su]
+    q = points[tv, tu]
+    keep = inside & (face >= 0) & (face < tri.shape[0]) & torch.isfinite(q).all(dim=1) & (q[:, 2] > 0)
+    corner = bary[sv, su].argmax(dim=1)
+    vertex = tri[face.clamp(0, max(tri.shape[0] - 1, 0)), corner]
+    return vertex[keep].to(torch.int32), q[keep].contiguous(), (None if w is None else w[keep])
+
+
 NDC_REFERENCE = 0     # the reference's image -> NDC mapping (SURVEY A11)
 NDC_CONSISTENT = 1    # raster pixel (u, v) == pixel (u, v) of the intrinsics
 
@@ -333,6 +375,43 @@ class DeformableMeshToImageFitter:
         out = np.empty(H * W, np.float32)
         N.check(N.lib().nnrt_fitter_get_raw_residuals(self._h, N.ptr(out), H * W, N.stream_ptr(stream)))
         return out
+
+    def set_landmarks(self, vertex_indices, target_points, weights=None, term_weight: float = 1.0, cutoff: float = 0.0, stream=None):
+        """Sparse 3-D correspondences for the next fit (nnrt_fitter_set_landmarks): landmark l pulls
+        canonical vertex vertex_indices[l] towards the camera-space point target_points[l] with residual
+        term_weight * weights[l] * (warped vertex - target). weights None: all 1; cutoff > 0 (metres) drops a landmark
+        farther from its target than that. An empty set clears the landmarks. IterationMode.ALL only. Takes effect at
+        the next prepare() (fit_to_image), which raises for an index outside the mesh or a vertex without a face;
+        invalidates the prepared frame. The same count and settings keep the captured graphs. term_weight = 1 is untuned."""
+        idx = to_device(vertex_indices, torch.int32, self.device).reshape(-1).contiguous()
+        tgt = to_device(target_points, torch.float32, self.device).reshape(-1, 3).contiguous()
+        if tgt.shape[0] != idx.shape[0]:
+            raise ValueError(f"{idx.shape[0]} vertex indices but {tgt.shape[0]} target points")
+        w = None
+        if weights is not None:
+            w = to_device(weights, torch.float32, self.device).reshape(-1).contiguous()
+            if w.shape[0] != idx.shape[0]:
+                raise ValueError(f"{idx.shape[0]} vertex indices but {w.shape[0]} weights")
+        N.check(N.lib().nnrt_fitter_set_landmarks(self._h, N.ptr(idx), N.ptr(tgt), N.ptr(w), idx.shape[0], float(term_weight), float(cutoff),
+                                                  N.stream_ptr(stream)))
+
+    def clear_landmarks(self, stream=None):
+        """Back to a fitter without landmarks: every launch and output as if none had ever been set."""
+        N.check(N.lib().nnrt_fitter_set_landmarks(self._h, None, None, None, 0, 1.0, 0.0, N.stream_ptr(stream)))
+
+    def landmark_distances(self, stream=None):
+        """([L, 3] float32 warped vertex - target, [L] bool active) of every landmark as of the state the last iteration
+        started from (zeros before the first). Synchronizes."""
+        L = self.landmark_info()["count"]
+        out = np.zeros((L, 4), np.float32)
+        N.check(N.lib().nnrt_fitter_get_landmark_distances(self._h, N.ptr(out), L, N.stream_ptr(stream)))
+        return out[:, :3].copy(), out[:, 3] != 0
+
+    def landmark_info(self) -> dict:
+        """Landmarks set and, of the prepared frame, their node associations, node runs and pair associations."""
+        out = np.zeros(4, np.int64)
+        N.check(N.lib().nnrt_fitter_landmark_info(self._h, N.ptr(out), out.size))
+        return {k: int(v) for k, v in zip(("count", "associations", "node_runs", "pair_associations"), out)}
 
     def step_history(self, stream=None) -> list:
         """The StepRecords of the iterations since the fit started (iterate() from iteration 0), oldest first: at most

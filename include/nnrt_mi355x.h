@@ -333,6 +333,32 @@ nnrt_status nnrt_fitter_get_step_objective(const nnrt_fitter* fitter, int32_t* o
  * mask; zeros before the first iteration), h_out [count] floats on the host. count must equal the prepared image's H * W;
  * without such a prepared frame NNRT_ERROR_ARGUMENT. Synchronizes `stream`. */
 nnrt_status nnrt_fitter_get_raw_residuals(nnrt_fitter* fitter, float* h_out, int64_t count, void* stream);
+/* Landmark term: `count` sparse 3-D correspondences for the next fit. Landmark l ties canonical vertex
+ * d_vertex_indices[l] (int32, device) to the camera-space point d_targets[3 l .. 3 l + 2] (float, device) with weight
+ * d_weights[l] >= 0 (device; NULL: all 1). With v' the warped vertex, d = v' - q, the residual is
+ * r = term_weight * weight * d in R^3; the landmark is active iff weight > 0, q is finite and (cutoff <= 0 or |d| <= cutoff,
+ * metres); its cost is |r|^2 when active, (term_weight weight cutoff)^2 when the cutoff dropped it, 0 otherwise (a
+ * truncated quadratic, whose IRLS weight the gate is). Active landmarks add J^T J and J^T r to the blocks of the vertex's
+ * anchor nodes (and, under NNRT_DATA_COUPLED, J_a^T J_b to the blocks of their pairs) in every iteration, on all three
+ * solve paths, and their cost to what step control compares (both objectives). The arrays are copied on `stream`.
+ * count == 0 clears the landmarks (the pointers are then ignored). The ranges are checked before anything else:
+ * term_weight must be finite and > 0, cutoff finite. IterationMode ALL only (another mode in the fitter's list:
+ * NNRT_ERROR_ARGUMENT). The landmarks take effect at the next prepare(), which refuses (NNRT_ERROR_ARGUMENT, naming the
+ * landmark) a vertex index outside the mesh or a vertex no face references; the call invalidates the prepared frame.
+ * The same count, term_weight and cutoff as before keep the captured graphs; a change of any, or a clear, drops them.
+ * A fitter without landmarks launches what it launched before this term existed. term_weight's default of 1 is untuned.
+ * count < 2^24 is the addressing limit, not a tuned range: one wave writes the distances and sums the cost, 64 landmarks per
+ * pass, which suits the hundreds to few thousands of matches a frame yields; nothing larger has been measured. */
+nnrt_status nnrt_fitter_set_landmarks(nnrt_fitter* fitter, const int32_t* d_vertex_indices, const float* d_targets, const float* d_weights,
+                                      int64_t count, float term_weight, float cutoff, void* stream);
+/* h_out [4 * count] floats on the host: per landmark (d.x, d.y, d.z, active as 0 / 1) as of the state the last iteration
+ * started from (zeros before the first). count must equal the number of landmarks set (a mismatch is refused, not written
+ * past). Synchronizes `stream`. */
+nnrt_status nnrt_fitter_get_landmark_distances(nnrt_fitter* fitter, float* h_out, int64_t count, void* stream);
+/* h_out[0..3] = landmarks set, and of the prepared frame: their (node, landmark, slot) associations, the runs of equal
+ * nodes among them, and their (pair, landmark, slot, slot) associations (0 outside NNRT_DATA_COUPLED); zeros for a frame
+ * that is not prepared. out_count: the room in h_out, at least 4. */
+nnrt_status nnrt_fitter_landmark_info(const nnrt_fitter* fitter, int64_t* h_out, int64_t out_count);
 /* Anchor the canonical mesh along a motion graph's edges instead of by Euclidean distance (the reference's
  * AnchorComputationMethod::SHORTEST_PATH, PlanarGraphWarpField::PrecomputeAnchorsAndWeights; apps/fusion/pipeline.py:577-582):
  * d_edges [node_count, graph_degree] int32 rows in the warp field's virtual node order (entry < 0 = empty) are copied
