@@ -14,6 +14,7 @@
 // The seed scan runs wave-wide: 64 nodes per coalesced load, broadcast by readlane, entered whenever some lane needs a
 // seed; every lane of the wave takes part in the loads (lanes past the last point and lanes that are finished only
 // skip the comparison), and the walk's divergence closes before the next scan.
+#include "anchor_dispatch.hpp"
 #include "kernels.hpp"
 
 namespace nnrt {
@@ -185,21 +186,11 @@ nnrt_status launch_anchors_shortest_path(const float* points, int64_t V, const f
 	}
 	const dim3 grid(static_cast<unsigned>(ceil_div(V, SP_BLOCK)));
 	const float c2 = coverage * coverage;
-#define NNRT_SP_ANCHOR_CASE(KK)                                                                                                          \
-	case KK:                                                                                                                             \
-		k_anchors_shortest_path<KK><<<grid, SP_BLOCK, 0, stream>>>(points, V, nodes, N, edges, D, c2, node_weights, anchors, weights); \
-		break;
-	switch (K) {
-		NNRT_SP_ANCHOR_CASE(1)
-		NNRT_SP_ANCHOR_CASE(2)
-		NNRT_SP_ANCHOR_CASE(3)
-		NNRT_SP_ANCHOR_CASE(4)
-		NNRT_SP_ANCHOR_CASE(5)
-		NNRT_SP_ANCHOR_CASE(6)
-		NNRT_SP_ANCHOR_CASE(7)
-		NNRT_SP_ANCHOR_CASE(8)
-	}
-#undef NNRT_SP_ANCHOR_CASE
+	const nnrt_status st = dispatch_anchor_count(K, [&](auto kk) {
+		k_anchors_shortest_path<decltype(kk)::value><<<grid, SP_BLOCK, 0, stream>>>(points, V, nodes, N, edges, D, c2, node_weights, anchors, weights);
+		return NNRT_OK;
+	});
+	if (st) return st;
 	NNRT_LAUNCH_CHECK();
 	return NNRT_OK;
 }

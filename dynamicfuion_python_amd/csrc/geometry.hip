@@ -1,5 +1,6 @@
 // Geometry stages of the hot path on gfx950: anchors (once per frame), mesh warp (+ warped-surface Jacobians),
 // NDC face extraction, depth unprojection, attribute interpolation, Rodrigues.
+#include "anchor_dispatch.hpp"
 #include "kernels.hpp"
 
 #include <cstdlib>
@@ -169,21 +170,11 @@ nnrt_status launch_compute_anchors(const float* points, int64_t V, const float* 
 	if (V == 0) return NNRT_OK;
 	const dim3 grid(static_cast<unsigned>(ceil_div(V, ANCHOR_BLOCK)));
 	const float c2 = coverage * coverage;
-#define NNRT_ANCHOR_CASE(KK)                                                                                                 \
-	case KK:                                                                                                                 \
-		k_compute_anchors<KK><<<grid, ANCHOR_BLOCK, 0, stream>>>(points, V, nodes, N, c2, node_weights, threshold, minimum_valid, anchors, weights); \
-		break;
-	switch (K) {
-		NNRT_ANCHOR_CASE(1)
-		NNRT_ANCHOR_CASE(2)
-		NNRT_ANCHOR_CASE(3)
-		NNRT_ANCHOR_CASE(4)
-		NNRT_ANCHOR_CASE(5)
-		NNRT_ANCHOR_CASE(6)
-		NNRT_ANCHOR_CASE(7)
-		NNRT_ANCHOR_CASE(8)
-	}
-#undef NNRT_ANCHOR_CASE
+	const nnrt_status st = dispatch_anchor_count(K, [&](auto kk) {
+		k_compute_anchors<decltype(kk)::value><<<grid, ANCHOR_BLOCK, 0, stream>>>(points, V, nodes, N, c2, node_weights, threshold, minimum_valid, anchors, weights);
+		return NNRT_OK;
+	});
+	if (st) return st;
 	NNRT_LAUNCH_CHECK();
 	return NNRT_OK;
 }

@@ -1,4 +1,4 @@
-"""nnrt.geometry.VoxelBlockGrid / NonRigidSurfaceVoxelBlockGrid mirror over the HIP TSDF grid (csrc/tsdf.hip).
+"""nnrt.geometry.VoxelBlockGrid / NonRigidSurfaceVoxelBlockGrid mirror over the HIP TSDF grid (csrc/tsdf_grid.hpp and the tsdf_*.hip sources).
 
 Reference: cpp/geometry/VoxelBlockGrid.{h,cpp}, cpp/geometry/NonRigidSurfaceVoxelBlockGrid.{h,cpp}, Python binding
 cpp/pybind/geometry/geometry.cpp:61-275 (same method names, argument meaning and defaults). Images are [H,W] depth

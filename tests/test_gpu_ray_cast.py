@@ -1,4 +1,4 @@
-"""VoxelBlockGrid.ray_cast on the GPU (csrc/tsdf.hip: k_range_blocks, k_ray_cast) against the float32 numpy restatement
+"""VoxelBlockGrid.ray_cast on the GPU (csrc/tsdf_ray_cast.hip: k_range_blocks, k_ray_cast) against the float32 numpy restatement
 of DESIGN §19 (tests/_ray_cast_util.py), bit for bit. Every case fills a GPU grid, pulls its voxel rows and block
 coordinates back and runs the restatement on those, so the ray cast is compared apart from integration. Frames are the
 64 x 48 ones of _tsdf_util.small_tsdf_scene; every case also asserts that rays hit, so nothing passes on an empty image."""

@@ -1,4 +1,4 @@
-"""GPU parity of the TSDF voxel block grid (csrc/tsdf.hip) against the oracle restatement (oracle/tsdf_oracle.cpp):
+"""GPU parity of the TSDF voxel block grid (csrc/tsdf_grid.hpp and the tsdf_*.hip sources) against the oracle restatement (oracle/tsdf_oracle.cpp):
 the reference KAT scene (cpp/tests/test_non_rigid_surface_voxel_block_grid.cpp) and a 640x480 synthetic frame with the
 C1 / C2 warp graphs. Block order, voxel values, the cosine map, block sets and the extracted mesh (vertex and triangle
 order included) are deterministic on both sides and compared exactly (float values bit-identical: same expression

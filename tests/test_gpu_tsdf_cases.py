@@ -1,4 +1,4 @@
-"""GPU parity of the TSDF voxel block grid (csrc/tsdf.hip) beyond the two scenes of test_gpu_tsdf.py: every storage
+"""GPU parity of the TSDF voxel block grid (csrc/tsdf_grid.hpp and the tsdf_*.hip sources) beyond the two scenes of test_gpu_tsdf.py: every storage
 pair, block resolution 16, a real camera pose, a separate colour camera, anchor counts 1 ... 8 with every minimum, variable
 node coverage, the candidate-list limits, several frames, growth mode, the hash table under growth and after a refused
 call -- all bit for bit against the oracle restatement (oracle/tsdf_oracle.cpp) -- and marching cubes against plain numpy.
@@ -627,3 +627,152 @@ def test_marching_cubes_against_numpy(nn, res, threshold, oracle_mod):
     assert (dc == 1).all()
     _, uc = np.unique(np.sort(d, axis=1), axis=0, return_counts=True)
     assert uc.max() == 2 and (uc == 2).sum() > len(uc) // 2
+
+
+# ---- the grid's owners: reused scratch table and error word, the one compaction step, no per-call allocation ------------
+def bytes_in_use():
+    from dynamicfuion_python_amd import _native
+    return int(_native.lib().nnrt_device_bytes_in_use())
+
+
+def test_dedupe_table_is_reused_across_frames(nn, oracle_mod):
+    """unique_block_coordinates on one grid for a frame that touches many blocks, one that touches few, then the first
+    again: each result is a fresh grid's (and the oracle's) for that frame, in order, and the grid's own blocks and table
+    are as they were (the dedupe table is scratch of its own)."""
+    sc = TU.small_tsdf_scene(oracle_mod, 0)
+    few = np.zeros_like(sc.depth)
+    few[20:28, 28:36] = sc.depth[20:28, 28:36]
+    gpu = GpuSide(nn, sc.voxel_size, 8, "float32", "float32", None, capacity=64)
+    blocks = gpu.touch(sc.depth, sc.K, EYE, sc)
+    gpu.integrate(blocks, sc.depth, sc.color, sc.K, sc.K, EYE, sc)
+    coords0, values0 = gpu.coords(), gpu.values()
+    want = {}
+    for name, depth in (("many", sc.depth), ("few", few)):
+        want[name] = GpuSide(nn, sc.voxel_size, 8, "float32", "float32", None, capacity=64).touch(depth, sc.K, EYE, sc)
+        assert np.array_equal(want[name], OracleSide(oracle_mod, sc.voxel_size, 8, "float32", "float32", None).touch(depth, sc.K, EYE, sc))
+    assert len(want["many"]) == 43 and 0 < len(want["few"]) <= 8
+    for name, depth in (("many", sc.depth), ("few", few), ("many", sc.depth)):
+        assert np.array_equal(gpu.touch(depth, sc.K, EYE, sc), want[name]), name
+        assert np.array_equal(gpu.coords(), coords0) and np.array_equal(gpu.values(), values0), name
+    # the table still finds every block: one voxel row per block's first voxel
+    assert len(gpu.values_at(np.ascontiguousarray(coords0 * 8))) == len(coords0)
+
+
+def test_error_word_is_reused_across_refused_calls(nn):
+    """Two refused activations (a coordinate out of range, at either end) and then a valid one on the same grid: both
+    refusals leave the grid as it was, the valid call creates exactly its blocks, and the grid holds as much device memory
+    as a fresh one of equal capacity after the same valid calls (the error word is the handle's, allocated once)."""
+    base = np.array([(0, 0, 0), (1, 0, 0), (-3, 2, 5), (7, 7, 7), (0, -1, 0)], np.int32)
+    valid = np.array([(2, 0, 0), (1, 0, 0), (4, 4, 4), (-5, -5, -5), (2, 0, 0), (9, 1, 1), (0, 0, 1), (0, 1, 0), (3, 3, 3)], np.int32)
+    bad1, bad2 = valid.copy(), valid.copy()
+    bad1[3] = (0, 1 << 20, 0)
+    bad2[0] = (-(1 << 20) - 1, 0, 0)
+    expect = first_occurrence_unique(np.concatenate([base, valid]))
+    start = bytes_in_use()
+    gpu = GpuSide(nn, 0.01, 8, "float32", "none", None, capacity=64)
+    gpu.activate(base)
+    coords0, values0 = gpu.coords(), gpu.values()
+    for bad in (bad1, bad2):
+        with pytest.raises(RuntimeError):
+            gpu.activate(bad)
+        assert gpu.g.get_block_count() == len(base)
+        assert np.array_equal(gpu.coords(), coords0) and np.array_equal(gpu.values(), values0)
+        assert len(gpu.values_at(np.ascontiguousarray(valid * 8))) == 1   # (1, 0, 0) alone is active
+    gpu.activate(valid)
+    assert gpu.g.get_block_count() == len(expect) == 12 and np.array_equal(gpu.coords(), expect)
+    held = bytes_in_use() - start
+    # the same calls without the refusals on a second grid, so that its scratch and result buffers match too
+    start = bytes_in_use()
+    fresh = GpuSide(nn, 0.01, 8, "float32", "none", None, capacity=64)
+    fresh.activate(base)
+    fresh.values_at(np.ascontiguousarray(valid * 8))
+    fresh.activate(valid)
+    assert np.array_equal(fresh.coords(), expect)
+    assert bytes_in_use() - start == held
+
+
+@pytest.mark.parametrize("cdt", ["none", "float32"], ids=["width5", "width8"])
+def test_values_at_compaction_counts_and_patterns(nn, oracle_mod, cdt):
+    """extract_voxel_values_at against rows of extract_voxel_values_and_coordinates, for 1, 255, 256 and 257 queries
+    (either side of one workgroup) with none, all and every other one found, at row widths 5 and 8. A found query's row
+    is its coordinate and the stored values at the reference's index b res^3 + x + res (y + res z) (the global
+    coordinate), -2 throughout when that index leaves the active blocks' storage."""
+    sc = TU.small_tsdf_scene(oracle_mod, 0)
+    gpu = GpuSide(nn, sc.voxel_size, 8, "float32", cdt, None, capacity=64)
+    origin = np.array([(0, 0, 0), (1, 0, 0), (0, 1, 0), (1, 1, 0)], np.int32)
+    gpu.activate(origin)
+    blocks = gpu.touch(sc.depth, sc.K, EYE, sc)
+    gpu.integrate(blocks, sc.depth, sc.color if cdt != "none" else None, sc.K, sc.K, EYE, sc)
+    gpu.activate(np.array([(3, 3, 20)], np.int32))   # the last block, far out: the reference's index leaves the storage there
+    rows_all, coords = gpu.values(), gpu.coords()
+    C = 8 if cdt != "none" else 5
+    assert rows_all.shape == (len(coords) * 512, C) and np.array_equal(coords[:4], origin) and (rows_all[:, 4] > 0).any()
+    assert len(coords) == 4 + 43 + 1 and tuple(coords[-1]) == (3, 3, 20)
+    rng = np.random.default_rng(21)
+    vs = np.float32(sc.voxel_size)
+
+    def expected(q):
+        block_of = {tuple(c): b for b, c in enumerate(coords)}
+        out = []
+        for x, y, z in q:
+            b = block_of.get((int(x) // 8, int(y) // 8, int(z) // 8))   # queries are non-negative: // is the C++ division
+            if b is None:
+                continue
+            lin = b * 512 + int(x) + 8 * (int(y) + 8 * int(z))
+            row = np.full(C, -2, np.float32)
+            if lin < len(rows_all):   # never negative here
+                row[:3] = np.array([x, y, z], np.float32) * vs
+                row[3:] = rows_all[lin, 3:]
+            out.append(row)
+        return np.array(out, np.float32).reshape(-1, C)
+
+    last = coords[-1] * 8   # a found query whose row is -2 throughout
+    for n in (1, 255, 256, 257):
+        hit = np.stack([rng.integers(0, 16, n), rng.integers(0, 16, n), rng.integers(0, 8, n)], 1).astype(np.int32)
+        hit[n // 2] = last + (7, 7, 7)
+        miss = hit + np.int32(8000)
+        for name, q in (("none", miss), ("all", hit), ("alternating", np.where((np.arange(n) % 2 == 0)[:, None], hit, miss))):
+            q = np.ascontiguousarray(q, np.int32)
+            got, want = gpu.values_at(q), expected(q)
+            assert len(want) == {"none": 0, "all": n, "alternating": (n + 1) // 2}[name]
+            assert got.shape == want.shape and np.array_equal(got, want), (n, name)
+    assert (expected(np.ascontiguousarray([last + (7, 7, 7)], np.int32)) == -2).all()
+
+
+@pytest.mark.parametrize("active", [9, 10])
+def test_sleeve_compaction_either_side_of_one_workgroup(nn, oracle_mod, active):
+    """The inactive-neighbour compaction with 27 * active candidates either side of 256 (243 and 270): the sleeve count
+    (duplicates kept) and the blocks it activates against the oracle's."""
+    keys = np.array([(x, y, 0) for y in range(3) for x in range(3)] + [(5, 5, 5)], np.int32)[:active]
+    gpu, orc = GpuSide(nn, 0.01, 8, "float32", "none", None, capacity=16), OracleSide(oracle_mod, 0.01, 8, "float32", "none", None)
+    for side in (gpu, orc):
+        side.activate(keys)
+    n_gpu, n_orc = gpu.sleeve(), orc.sleeve()
+    # of a block's 27 neighbours (itself included) the active ones are dropped: 4 at a corner of the 3 x 3 plane, 6 at an
+    # edge, 9 at its centre; the tenth block stands alone
+    assert n_gpu == n_orc and n_orc == {9: 243 - (4 * 4 + 4 * 6 + 9), 10: 243 - (4 * 4 + 4 * 6 + 9) + 26}[active]
+    assert np.array_equal(gpu.coords(), orc.coords()) and len(gpu.coords()) == {9: 75, 10: 75 + 27}[active]
+
+
+def test_no_device_allocation_per_frame(nn, oracle_mod):
+    """After one warm-up frame the grid allocates nothing: nnrt_device_bytes_in_use is the same before and after
+    unique_block_coordinates, integrate and integrate_non_rigid, for three further frames of the same sizes."""
+    sc, sc2 = scenes(oracle_mod)
+    gpu = GpuSide(nn, sc.voxel_size, 8, "float32", "float32", scene_field(sc), growth=True, capacity=256)
+
+    def frame(check):
+        steps = []
+        before = bytes_in_use()
+        b = gpu.touch(sc.depth, sc.K, EYE, sc)
+        steps.append(bytes_in_use() - before)
+        gpu.integrate(b, sc.depth, sc.color, sc.K, sc.K, EYE, sc)
+        steps.append(bytes_in_use() - before)
+        cos = gpu.nonrigid(b, sc2.depth, sc2.color, sc2.normals, sc.K, sc.K, EYE, sc2)
+        steps.append(bytes_in_use() - before)
+        assert len(b) == 43 and (cos != 0).any()
+        if check:
+            assert steps == [0, 0, 0]
+    frame(False)
+    for _ in range(3):
+        frame(True)
+    assert gpu.g.get_block_count() == 43
