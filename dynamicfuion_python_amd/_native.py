@@ -133,6 +133,10 @@ _SIGNATURES = {
                                           c_void_p, c_int32, c_void_p, c_void_p]),
     "nnrt_intensity_from_rgb8": (c_int32, [c_void_p, c_int32, c_int32, c_void_p, c_void_p]),
     "nnrt_intensity_halve": (c_int32, [c_void_p, c_int32, c_int32, c_void_p, c_void_p]),
+    "nnrt_corner_scores": (c_int32, [c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p]),
+    "nnrt_select_features": (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_float, c_int32, c_int32, c_void_p, c_void_p, c_void_p]),
+    "nnrt_track_features": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_int64, c_int32, c_int32,
+                                      c_float, c_float, c_float, c_float, c_void_p, c_void_p, c_void_p, c_void_p]),
     "nnrt_warp_mesh": (c_int32, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_int32,
                                  c_void_p, c_void_p, c_void_p, c_void_p]),
     "nnrt_warp_points": (c_int32, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_int32, c_float,

@@ -405,6 +405,91 @@ nnrt_status nnrt_intensity_halve(const float* d_in, int32_t height, int32_t widt
 	return launch_intensity_halve(d_in, height, width, d_out, static_cast<hipStream_t>(stream));
 }
 
+nnrt_status nnrt_corner_scores(const float* d_intensity, int32_t height, int32_t width, int32_t window_radius, float* d_out_scores, void* stream) {
+	NNRT_CHECK_ARG(height >= 0 && width >= 0, "negative height or width");
+	NNRT_CHECK_ARG(window_radius >= 1 && window_radius <= NNRT_FEATURE_MAX_WINDOW_RADIUS, "window_radius must be in [1, 7]");
+	const size_t pixels = static_cast<size_t>(height) * static_cast<size_t>(width);
+	NNRT_CHECK_ARG(pixels < (size_t(1) << 31), "height * width must be below 2^31");
+	if (pixels == 0) return NNRT_OK;
+	NNRT_CHECK_ARG(d_intensity, "null d_intensity");
+	NNRT_CHECK_ARG(d_out_scores, "null d_out_scores");
+	NNRT_CHECK_ARG(!ranges_overlap(d_intensity, sizeof(float) * pixels, d_out_scores, sizeof(float) * pixels),
+	               "d_out_scores must not overlap d_intensity");
+	return launch_corner_scores(d_intensity, height, width, window_radius, d_out_scores, static_cast<hipStream_t>(stream));
+}
+
+nnrt_status nnrt_select_features(const float* d_scores, const uint8_t* d_mask, int32_t height, int32_t width, float quality, int32_t nms_radius,
+                                 int32_t max_count, float* d_out_points, int64_t* h_out_count, void* stream) {
+	NNRT_CHECK_ARG(h_out_count, "null h_out_count");
+	*h_out_count = 0;
+	NNRT_CHECK_ARG(height >= 0 && width >= 0, "negative height or width");
+	NNRT_CHECK_ARG(quality >= 0.f && quality <= 1.f, "quality must be in [0, 1]");   // refuses NaN
+	NNRT_CHECK_ARG(nms_radius >= 0 && nms_radius <= NNRT_FEATURE_MAX_NMS_RADIUS, "nms_radius must be in [0, 15]");
+	NNRT_CHECK_ARG(max_count >= 1 && max_count <= (1 << 20), "max_count must be in [1, 2^20]");
+	const size_t pixels = static_cast<size_t>(height) * static_cast<size_t>(width);
+	NNRT_CHECK_ARG(pixels < (size_t(1) << 31), "height * width must be below 2^31");
+	if (pixels == 0) return NNRT_OK;
+	NNRT_CHECK_ARG(d_scores, "null d_scores");
+	NNRT_CHECK_ARG(d_out_points, "null d_out_points");
+	const size_t out_bytes = sizeof(float) * 2 * static_cast<size_t>(max_count);
+	NNRT_CHECK_ARG(!ranges_overlap(d_scores, sizeof(float) * pixels, d_out_points, out_bytes) &&
+	                   !(d_mask && ranges_overlap(d_mask, pixels, d_out_points, out_bytes)),
+	               "d_out_points must not overlap d_scores or d_mask");
+	return launch_select_features(d_scores, d_mask, height, width, quality, nms_radius, max_count, d_out_points, h_out_count,
+	                              static_cast<hipStream_t>(stream));
+}
+
+nnrt_status nnrt_track_features(const float* const* h_pyramid_a, const float* const* h_pyramid_b, const int32_t* h_heights,
+                                const int32_t* h_widths, int32_t levels, const float* d_points, const float* d_initial_flow,
+                                const float* d_reference_points, int64_t count, int32_t window_radius, int32_t max_iterations, float epsilon,
+                                float min_eigen_threshold, float max_residual, float forward_backward_threshold, float* d_out_points,
+                                uint8_t* d_out_status, float* d_out_residual, void* stream) {
+	NNRT_CHECK_ARG(count >= 0 && count < (int64_t(1) << 29), "count must be in [0, 2^29)");
+	NNRT_CHECK_ARG(levels >= 1 && levels <= NNRT_FEATURE_MAX_LEVELS, "levels must be in [1, 4]");
+	NNRT_CHECK_ARG(window_radius >= 1 && window_radius <= NNRT_FEATURE_MAX_WINDOW_RADIUS, "window_radius must be in [1, 7]");
+	NNRT_CHECK_ARG(max_iterations >= 1 && max_iterations <= NNRT_FEATURE_MAX_ITERATIONS, "max_iterations must be in [1, 30]");
+	NNRT_CHECK_ARG(std::isfinite(epsilon) && epsilon >= 0.f, "epsilon must be finite and >= 0");
+	NNRT_CHECK_ARG(std::isfinite(min_eigen_threshold) && min_eigen_threshold >= 0.f, "min_eigen_threshold must be finite and >= 0");
+	NNRT_CHECK_ARG(!std::isnan(max_residual), "max_residual is NaN");
+	NNRT_CHECK_ARG(!std::isnan(forward_backward_threshold), "forward_backward_threshold is NaN");
+	NNRT_CHECK_ARG(!d_reference_points || (std::isfinite(forward_backward_threshold) && forward_backward_threshold >= 0.f),
+	               "forward_backward_threshold must be finite and >= 0 with reference points");
+	if (count == 0) return NNRT_OK;
+	NNRT_CHECK_ARG(h_pyramid_a && h_pyramid_b && h_heights && h_widths, "null pyramid arrays");
+	for (int l = 0; l < levels; l++) {
+		NNRT_CHECK_ARG(h_heights[l] >= 1 && h_widths[l] >= 1, "pyramid level " + std::to_string(l) + ": height and width must be positive");
+		NNRT_CHECK_ARG(static_cast<int64_t>(h_heights[l]) * h_widths[l] < (int64_t(1) << 31),
+		               "pyramid level " + std::to_string(l) + ": height * width must be below 2^31");
+		NNRT_CHECK_ARG(l == 0 || (h_heights[l] == (h_heights[l - 1] + 1) / 2 && h_widths[l] == (h_widths[l - 1] + 1) / 2),
+		               "pyramid level " + std::to_string(l) + ": its size is not ceil(half) of the level below");
+		NNRT_CHECK_ARG(h_pyramid_a[l] && h_pyramid_b[l], "pyramid level " + std::to_string(l) + ": null image");
+	}
+	NNRT_CHECK_ARG(d_points, "null d_points");
+	NNRT_CHECK_ARG(d_out_points && d_out_status && d_out_residual, "null output");
+	const size_t n = static_cast<size_t>(count), point_bytes = sizeof(float) * 2 * n;
+	const struct {
+		const void* p;
+		size_t bytes;
+	} outs[3] = {{d_out_points, point_bytes}, {d_out_status, n}, {d_out_residual, sizeof(float) * n}};
+	for (int i = 0; i < 3; i++) {
+		for (int j = i + 1; j < 3; j++)
+			NNRT_CHECK_ARG(!ranges_overlap(outs[i].p, outs[i].bytes, outs[j].p, outs[j].bytes), "the outputs must not overlap one another");
+		NNRT_CHECK_ARG(!ranges_overlap(outs[i].p, outs[i].bytes, d_points, point_bytes) &&
+		                   !(d_initial_flow && ranges_overlap(outs[i].p, outs[i].bytes, d_initial_flow, point_bytes)) &&
+		                   !(d_reference_points && ranges_overlap(outs[i].p, outs[i].bytes, d_reference_points, point_bytes)),
+		               "an output must not overlap d_points, d_initial_flow or d_reference_points");
+		for (int l = 0; l < levels; l++) {
+			const size_t level_bytes = sizeof(float) * static_cast<size_t>(h_heights[l]) * static_cast<size_t>(h_widths[l]);
+			NNRT_CHECK_ARG(!ranges_overlap(outs[i].p, outs[i].bytes, h_pyramid_a[l], level_bytes) &&
+			                   !ranges_overlap(outs[i].p, outs[i].bytes, h_pyramid_b[l], level_bytes),
+			               "an output must not overlap a pyramid level");
+		}
+	}
+	return launch_track_features(h_pyramid_a, h_pyramid_b, h_heights, h_widths, levels, d_points, d_initial_flow, d_reference_points,
+	                             static_cast<int>(count), window_radius, max_iterations, epsilon, min_eigen_threshold, max_residual,
+	                             forward_backward_threshold, d_out_points, d_out_status, d_out_residual, static_cast<hipStream_t>(stream));
+}
+
 nnrt_status nnrt_compute_anchors_and_weights(const float* d_points, int64_t V, const float* d_nodes, int32_t N, int32_t K, float coverage,
                                              const float* d_node_weights, int32_t minimum_valid, int32_t* d_anchors, float* d_weights,
                                              void* stream) {

@@ -105,6 +105,15 @@ nnrt_status launch_rigid_align(const float* points, const float* normals, int64_
 // binomial mean centred on (2 i, 2 j) (arguments checked by the caller, non-empty images)
 nnrt_status launch_intensity_rgb8(const uint8_t* rgb, int H, int W, float* out, hipStream_t stream);
 nnrt_status launch_intensity_halve(const float* in, int H, int W, float* out, hipStream_t stream);
+// feature_track.hip: Shi-Tomasi scores, corner selection and pyramidal Lucas-Kanade (arguments
+// checked by the caller, non-empty images, n >= 1). launch_select_features synchronizes `s` once, for the candidate count.
+nnrt_status launch_corner_scores(const float* intensity, int H, int W, int r, float* out, hipStream_t stream);
+nnrt_status launch_select_features(const float* scores, const uint8_t* mask, int H, int W, float quality, int nms_radius, int max_count,
+                                   float* out_points, int64_t* h_count, hipStream_t s);
+nnrt_status launch_track_features(const float* const* pyramid_a, const float* const* pyramid_b, const int* heights, const int* widths, int levels,
+                                  const float* points, const float* initial_flow, const float* reference, int n, int r, int max_iterations,
+                                  float epsilon, float min_eigen_threshold, float max_residual, float forward_backward_threshold,
+                                  float* out_points, uint8_t* out_status, float* out_residual, hipStream_t stream);
 // vertex_path: the lane-per-vertex kernels where K <= 4 and no rows are gathered (launch_plan.hpp choose_warp_vertex)
 nnrt_status launch_warp_mesh(const float* points, const float* normals, int64_t V, const float* node_state, const int32_t* anchors,
                              const float* weights, int K, const WarpExtrinsics& E, float4* out_p, float4* out_n, float2* jrows,

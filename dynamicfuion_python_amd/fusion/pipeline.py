@@ -67,7 +67,8 @@ from ..data.frame import FrameSequenceDataset
 from ..nnrt import geometry as G
 from ..nnrt import image_proc
 from ..nnrt import rendering
-from ..nnrt.alignment import NDC_CONSISTENT, DataCoupling, StepControl, StepObjective, align_rigid_hybrid, align_rigid_point_to_plane
+from ..nnrt.alignment import (NDC_CONSISTENT, DataCoupling, FeatureTracking, FeatureTrackLandmarks, StepControl, StepObjective,
+                              align_rigid_hybrid, align_rigid_point_to_plane)
 from ..warp_field.graph_warp_field import build_graph_nodes_from_depth_image, extend_warp_field, sample_graph_nodes_from_mesh
 
 
@@ -181,6 +182,10 @@ class FusionParameters:
     # the cost step control compares (StepObjective): SQUARE allows SQUARE penalties only (this loop's
     # default); ROBUST goes with the TUKEY / HUBER penalties in PenaltyForm.IRLS. Overrides alignment.step_objective when set.
     step_objective: Optional[StepObjective] = None
+    # landmarks from the colour frames (FeatureTracking): when set, and no landmark_provider is given, the
+    # pipeline tracks sparse features from each colour frame to the next and feeds them to the fit's landmark term. None
+    # (the default): nothing is launched or allocated for it.
+    landmark_tracking: Optional[FeatureTracking] = None
 
 
 def alignment_parameters(p: FusionParameters) -> RenderingAlignmentParameters:
@@ -228,6 +233,9 @@ class FrameResult:
     landmark_count: int = 0
     landmark_active_count: int = 0
     landmark_rmse: float = 0.0
+    # FusionParameters.landmark_tracking (0 without it): the features selected in the previous colour frame; landmark_count
+    # counts those that survived tracking and the match filter
+    tracked_feature_count: int = 0
 
 
 def remap_edges_to_node_order(edges, order) -> np.ndarray:
@@ -252,9 +260,14 @@ class FusionPipeline:
         """landmark_provider: a callable (pipeline, frame, canonical_mesh, point_image) -> (vertex_indices, targets,
         weights | None) | None, called for every tracked frame before its non-rigid fit: the sparse correspondences of the
         fit's landmark term (nnrt.alignment.landmarks_from_pixel_matches makes the tuple from 2-D
-        matches). None: no landmark term."""
-        self.landmark_provider = landmark_provider
+        matches). None: no landmark term, unless FusionParameters.landmark_tracking is set: the pipeline then owns a
+        FeatureTrackLandmarks, hands it every frame's colour image and uses it as the provider. Both given: refused."""
         self.parameters = p = parameters or FusionParameters()
+        if landmark_provider is not None and p.landmark_tracking is not None:
+            raise ValueError("both landmark_provider and FusionParameters.landmark_tracking are given: the pipeline takes landmarks from one "
+                             "source; drop one of the two")
+        self.feature_tracker = FeatureTrackLandmarks(p.landmark_tracking) if p.landmark_tracking is not None else None
+        self.landmark_provider = landmark_provider if self.feature_tracker is None else self.feature_tracker
         if p.tracking_method == TrackingMethod.NEURAL:
             raise NotImplementedError("TrackingMethod.NEURAL (DeformNet) is not part of this build; use TrackingMethod.RENDERING")
         if p.graph_generation_mode == GraphGenerationMode.FIRST_FRAME_DEPTH_IMAGE and not p.graph_from_depth_image:
@@ -479,6 +492,8 @@ class FusionPipeline:
         depth_np, depth, color = self._load_frame(frame)
         self.processed_frames += 1
         res = FrameResult(frame.frame_index)
+        if self.feature_tracker is not None:
+            self.feature_tracker.advance(color, self.extrinsics)   # the extrinsics are still the previous frame's here
         depth_max = self._depth_max()
         if self.active_graph is None:
             # canonical frame: rigid integration, then the motion graph (pipeline.py:224-248)
@@ -521,6 +536,8 @@ class FusionPipeline:
                 landmarks = self.landmark_provider(self, frame, canonical, points) if self.landmark_provider is not None else None
                 if landmarks is not None and len(landmarks[0]) == 0:
                     landmarks = None
+                if self.feature_tracker is not None:
+                    res.tracked_feature_count = self.feature_tracker.feature_count
                 self.optimizer.optimize_graph(self.active_graph, canonical, points, extrinsics=self.extrinsics, landmarks=landmarks)
                 res.tracked = True
                 if landmarks is not None:

@@ -148,6 +148,81 @@ def landmarks_from_pixel_matches(pixel_face_indices, pixel_barycentric_coordinat
     return vertex[keep].to(torch.int32), q[keep].contiguous(), (None if w is None else w[keep])
 
 
+@dataclasses.dataclass(frozen=True)
+class FeatureTracking:
+    """Parameters of the sparse feature tracker that feeds the landmark term from the colour frames (FeatureTrackLandmarks,
+    FusionParameters.landmark_tracking). Selection: at most max_features Shi-Tomasi corners (window
+    radius window_radius) with a score of at least quality times the best, no two within nms_radius pixels. Tracking:
+    pyramidal Lucas-Kanade over `levels` levels with the same window radius, max_iterations per level (epsilon > 0 stops a
+    level once a step is shorter, in pixels), levels and features flatter than min_eigen_threshold dropped, features
+    whose mean absolute intensity difference at the result exceeds max_residual dropped (<= 0: kept), and a round trip
+    that must close within forward_backward_threshold pixels (None: no backward pass). weight: the weight every landmark
+    carries into the fit. The defaults are conventional values for 8-bit images scaled to [0, 1]; none of them has been
+    tuned on any real sequence."""
+    max_features: int = 512
+    quality: float = 0.01
+    nms_radius: int = 5
+    window_radius: int = 7
+    levels: int = 3
+    max_iterations: int = 10
+    epsilon: float = 0.01
+    min_eigen_threshold: float = 1e-6
+    max_residual: float = 0.05
+    forward_backward_threshold: float | None = 0.5
+    weight: float = 1.0
+
+
+class FeatureTrackLandmarks:
+    """The built-in landmark provider (FusionPipeline(landmark_provider=...) signature): landmarks from features tracked
+    between the previous colour frame and the current one.
+
+    advance(color, extrinsics) takes every frame's uint8 [H, W, 3] colour image, the first included, with the world -> camera
+    matrix the previous frame was tracked with; it keeps the previous frame's intensity pyramid and builds the current
+    one. Called for a tracked frame, the provider rasterizes the canonical mesh, warped by the graph's current state (the
+    previous frame's fit), at those extrinsics with one face per pixel; selects features in the previous intensity under
+    the mask "pixel has a face"; tracks them into the current frame; rounds the tracked positions to the nearest pixel;
+    and returns landmarks_from_pixel_matches(...) with `weight` on every landmark. The rounding moves a target by up to
+    half a pixel's footprint on the surface (z / fx); a sub-pixel lookup of the target point is not done.
+    feature_count: the features selected by the last call."""
+
+    def __init__(self, parameters: FeatureTracking | None = None):
+        self.parameters = parameters or FeatureTracking()
+        self.previous_pyramid = None
+        self.current_pyramid = None
+        self.previous_extrinsics = None
+        self.feature_count = 0
+
+    def advance(self, color, extrinsics=None):
+        from .image_proc import intensity_from_rgb8, intensity_pyramid
+        self.previous_pyramid = self.current_pyramid
+        self.current_pyramid = intensity_pyramid(intensity_from_rgb8(color), self.parameters.levels)
+        self.previous_extrinsics = np.eye(4) if extrinsics is None else np.array(extrinsics, np.float64)
+
+    def __call__(self, pipeline, frame, canonical, point_image):
+        from . import rendering
+        from .image_proc import FEATURE_TRACKED, corner_scores, select_features, track_features
+        p = self.parameters
+        self.feature_count = 0
+        if self.previous_pyramid is None or self.current_pyramid is None:
+            return None
+        previous = self.previous_pyramid[0]
+        H, W = int(previous.shape[0]), int(previous.shape[1])
+        warped = pipeline.active_graph.warp_mesh(canonical, extrinsics=self.previous_extrinsics)
+        (faces, _, bary, _), _ = rendering.rasterize_meshes(warped, pipeline.K, (H, W), faces_per_pixel=1, ndc_convention=NDC_CONSISTENT)
+        faces = faces.reshape(H, W)
+        source = select_features(corner_scores(previous, p.window_radius), p.max_features, p.quality, p.nms_radius, mask=faces >= 0)
+        self.feature_count = int(source.shape[0])
+        if self.feature_count == 0:
+            return None
+        target, status, _ = track_features(self.previous_pyramid, self.current_pyramid, source, p.window_radius, p.max_iterations, p.epsilon,
+                                           p.min_eigen_threshold, p.max_residual, p.forward_backward_threshold)
+        kept = status == FEATURE_TRACKED
+        source_uv = source[kept].to(torch.int64)
+        target_uv = torch.floor(target[kept] + 0.5).to(torch.int64)
+        weights = torch.full((int(source_uv.shape[0]),), float(p.weight), dtype=torch.float32, device=source.device)
+        return landmarks_from_pixel_matches(faces, bary, canonical.triangle_indices, source_uv, target_uv, point_image, weights)
+
+
 NDC_REFERENCE = 0     # the reference's image -> NDC mapping (SURVEY A11)
 NDC_CONSISTENT = 1    # raster pixel (u, v) == pixel (u, v) of the intrinsics
 

@@ -3,6 +3,7 @@ ordered point image, and the depth filters ahead of it, on the GPU. Inputs may b
 tensors ([H, W, 3] float32 point images, [H, W] uint16 or float32 depth)."""
 from __future__ import annotations
 
+import ctypes
 import math
 
 import numpy as np
@@ -209,6 +210,126 @@ def halve_intensity(intensity) -> torch.Tensor:
     out = torch.empty(((H + 1) // 2, (W + 1) // 2), dtype=torch.float32, device=dev)
     N.check(N.lib().nnrt_intensity_halve(N.ptr(a), H, W, N.ptr(out), N.stream_ptr()))
     return out
+
+
+# include/nnrt_mi355x.h NNRT_FEATURE_*
+FEATURE_MAX_WINDOW_RADIUS, FEATURE_MAX_NMS_RADIUS, FEATURE_MAX_LEVELS, FEATURE_MAX_ITERATIONS = 7, 15, 4, 30
+FEATURE_TRACKED, FEATURE_OUT_OF_IMAGE, FEATURE_FLAT, FEATURE_RESIDUAL, FEATURE_NON_FINITE, FEATURE_FB_FAILED = range(6)
+
+
+def intensity_pyramid(intensity, levels: int) -> list:
+    """[level 0, .., level levels - 1] of a float32 [H, W] intensity image: level l is halve_intensity of level l - 1, so
+    level pixel (i, j) is image pixel (2^l i, 2^l j). The pyramid track_features takes."""
+    if not 1 <= int(levels) <= FEATURE_MAX_LEVELS:
+        raise ValueError(f"levels must be in [1, {FEATURE_MAX_LEVELS}], got {levels}")
+    dtype = intensity.dtype if isinstance(intensity, torch.Tensor) else np.asarray(intensity).dtype
+    if dtype not in (torch.float32, np.dtype(np.float32)) or len(intensity.shape) != 2:
+        raise ValueError(f"intensity must be a float32 [H, W] image, got {dtype} {tuple(intensity.shape)}")
+    N.require_gpu()
+    dev = device_of(N.current_device())
+    pyramid = [(intensity if isinstance(intensity, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(intensity))).to(dev).contiguous()]
+    for _ in range(int(levels) - 1):
+        pyramid.append(halve_intensity(pyramid[-1]))
+    return pyramid
+
+
+def _image_f32(image, name):
+    dtype = image.dtype if isinstance(image, torch.Tensor) else np.asarray(image).dtype
+    if dtype not in (torch.float32, np.dtype(np.float32)) or len(image.shape) != 2:
+        raise ValueError(f"{name} must be a float32 [H, W] image, got {dtype} {tuple(image.shape)}")
+    dev = device_of(N.current_device())
+    return (image if isinstance(image, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(image))).to(dev).contiguous()
+
+
+def _points_f32(points, name, dev):
+    t = torch.as_tensor(points).to(device=dev, dtype=torch.float32).contiguous()
+    if t.dim() != 2 or t.shape[1] != 2:
+        raise ValueError(f"{name} must be [n, 2] (u, v), got {tuple(t.shape)}")
+    return t
+
+
+def corner_scores(intensity, window_radius: int = 3) -> torch.Tensor:
+    """Shi-Tomasi score of every pixel of a float32 [H, W] image (nnrt_corner_scores): the smaller eigenvalue
+    of the gradient matrix summed over the (2 window_radius + 1)^2 window, divided by the window's pixel count; central
+    differences in float32, the sums in float64. Pixels whose window (with the gradients' taps) leaves the image score 0."""
+    N.require_gpu()
+    a = _image_f32(intensity, "intensity")
+    H, W = int(a.shape[0]), int(a.shape[1])
+    out = torch.empty((H, W), dtype=torch.float32, device=a.device)
+    N.check(N.lib().nnrt_corner_scores(N.ptr(a), H, W, int(window_radius), N.ptr(out), N.stream_ptr()))
+    return out
+
+
+def select_features(scores, max_count: int, quality: float = 0.01, nms_radius: int = 3, mask=None) -> torch.Tensor:
+    """The strongest separated corners of a score image as float32 [n, 2] (u, v) = (column, row), n <= max_count, by
+    descending score and ascending pixel index (nnrt_select_features). A pixel qualifies with a finite score
+    > 0 and >= quality times the largest, a non-zero `mask` (uint8 or bool [H, W], optional) and no stronger pixel (or
+    equal one of lower index) within nms_radius. Reads the count back once: synchronizes the stream."""
+    N.require_gpu()
+    s = _image_f32(scores, "scores")
+    H, W = int(s.shape[0]), int(s.shape[1])
+    m = None
+    if mask is not None:
+        m = torch.as_tensor(mask).to(s.device)
+        if tuple(m.shape) != (H, W) or m.dtype not in (torch.uint8, torch.bool):
+            raise ValueError(f"mask must be a uint8 or bool [{H}, {W}] image, got {m.dtype} {tuple(m.shape)}")
+        m = m.to(torch.uint8).contiguous()
+    out = torch.empty((int(max_count) if max_count >= 1 else 1, 2), dtype=torch.float32, device=s.device)
+    count = ctypes.c_int64(0)
+    N.check(N.lib().nnrt_select_features(N.ptr(s), N.ptr(m), H, W, float(quality), int(nms_radius), int(max_count), N.ptr(out),
+                                         ctypes.addressof(count), N.stream_ptr()))
+    return out[:count.value]
+
+
+def _track_pass(pyramid_a, pyramid_b, points, initial_flow, reference, window_radius, max_iterations, epsilon, min_eigen_threshold, max_residual,
+                forward_backward_threshold):
+    L, n, dev = len(pyramid_a), int(points.shape[0]), points.device
+    out_points = torch.empty((n, 2), dtype=torch.float32, device=dev)
+    status = torch.empty((n,), dtype=torch.uint8, device=dev)
+    residual = torch.empty((n,), dtype=torch.float32, device=dev)
+    pa = (N.c_void_p * L)(*[a.data_ptr() for a in pyramid_a])
+    pb = (N.c_void_p * L)(*[b.data_ptr() for b in pyramid_b])
+    hs = (N.c_int32 * L)(*[int(a.shape[0]) for a in pyramid_a])
+    ws = (N.c_int32 * L)(*[int(a.shape[1]) for a in pyramid_a])
+    N.check(N.lib().nnrt_track_features(pa, pb, hs, ws, L, N.ptr(points), N.ptr(initial_flow), N.ptr(reference), n, int(window_radius),
+                                        int(max_iterations), float(epsilon), float(min_eigen_threshold), float(max_residual),
+                                        float(forward_backward_threshold), N.ptr(out_points), N.ptr(status), N.ptr(residual), N.stream_ptr()))
+    return out_points, status, residual
+
+
+def track_features(pyramid_a, pyramid_b, points, window_radius: int = 7, max_iterations: int = 10, epsilon: float = 0.0,
+                   min_eigen_threshold: float = 1e-6, max_residual: float = 0.0, forward_backward_threshold=None, initial_flow=None):
+    """Pyramidal Lucas-Kanade tracking of `points` [n, 2] (u, v) from pyramid_a to pyramid_b, two intensity_pyramid lists of
+    equal sizes (nnrt_track_features): (points [n, 2] float32, status [n] uint8, residual [n] float32) on the
+    device. status 0 (FEATURE_TRACKED) or the cause a feature was lost for (FEATURE_*); a lost feature keeps its input
+    point. residual: the mean absolute intensity difference over the window at the result. epsilon 0 runs exactly
+    max_iterations per level; max_residual <= 0 keeps every residual. `initial_flow` [n, 2]: a first guess in level-0 pixels.
+
+    forward_backward_threshold (pixels, None: off): a second pass tracks the forward results back from pyramid_b to
+    pyramid_a; a feature the forward pass tracked whose way back fails, or ends farther than the threshold from where it
+    started, becomes FEATURE_FB_FAILED and keeps its input point. Nothing is read back: asynchronous on the stream."""
+    N.require_gpu()
+    if len(pyramid_a) != len(pyramid_b) or not 1 <= len(pyramid_a) <= FEATURE_MAX_LEVELS:
+        raise ValueError(f"the pyramids must have the same number of levels, 1 to {FEATURE_MAX_LEVELS}: got {len(pyramid_a)} and {len(pyramid_b)}")
+    pa = [_image_f32(a, "pyramid_a level") for a in pyramid_a]
+    pb = [_image_f32(b, "pyramid_b level") for b in pyramid_b]
+    for l, (a, b) in enumerate(zip(pa, pb)):
+        if a.shape != b.shape:
+            raise ValueError(f"level {l}: pyramid_a is {tuple(a.shape)}, pyramid_b {tuple(b.shape)}")
+    dev = pa[0].device
+    p = _points_f32(points, "points", dev)
+    flow = None if initial_flow is None else _points_f32(initial_flow, "initial_flow", dev)
+    if flow is not None and flow.shape != p.shape:
+        raise ValueError(f"{p.shape[0]} points but {flow.shape[0]} initial flows")
+    options = (window_radius, max_iterations, epsilon, min_eigen_threshold, max_residual)
+    forward = _track_pass(pa, pb, p, flow, None, *options, 0.0)
+    if forward_backward_threshold is None:
+        return forward
+    q, status, residual = forward
+    _, back_status, _ = _track_pass(pb, pa, q, None, p, *options, float(forward_backward_threshold))
+    failed = (status == FEATURE_TRACKED) & (back_status != FEATURE_TRACKED)
+    status = torch.where(failed, torch.full_like(status, FEATURE_FB_FAILED), status)
+    return torch.where(failed[:, None], p, q), status, residual
 
 
 def backproject_depth(depth_image, fx, fy, cx, cy, depth_scale: float = 1000.0) -> torch.Tensor:

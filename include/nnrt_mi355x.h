@@ -668,6 +668,77 @@ nnrt_status nnrt_rigid_align_hybrid(const float* d_points, const float* d_normal
                                     int32_t iterations, float distance_threshold, float normal_agreement_cos, int32_t cull_back_faces,
                                     int32_t minimum_correspondence_count, float photometric_weight, float photometric_residual_threshold,
                                     double* h_T_out, double* h_log, int32_t log_row_capacity, int32_t* h_status, void* stream);
+/* Sparse feature tracker over intensity images (no counterpart in the reference, whose matches come
+ * from PWC-Net / DeformNet): Shi-Tomasi scores, the selection of separated corners, pyramidal Lucas-Kanade. Images are
+ * float32 [height,width]; pyramid level l is l applications of nnrt_intensity_halve, so level pixel (i, j) is image pixel
+ * (2^l i, 2^l j) and a level-0 coordinate p is p / 2^l at level l. Points are (u, v) = (column, row). No float atomics,
+ * every sum in a fixed order: bit-reproducible.
+ *
+ * nnrt_corner_scores: d_out_scores [height,width] = the smaller eigenvalue of the gradient matrix over the
+ * (2 window_radius + 1)^2 window of each pixel, 1 <= window_radius <= NNRT_FEATURE_MAX_WINDOW_RADIUS. In float,
+ * Ix = 0.5 (I[y, x + 1] - I[y, x - 1]), Iy = 0.5 (I[y + 1, x] - I[y - 1, x]). In float64, over the window in row-major
+ * order, a = sum Ix Ix, b = sum Ix Iy, c = sum Iy Iy (each product of the two floats formed in float64, exact);
+ * lambda = 0.5 ((a + c) - sqrt((a - c)(a - c) + 4 b b)) / (2 r + 1)^2, rounded once to float. A pixel (x, y) whose window
+ * with its gradients' taps leaves the image (x - r - 1 < 0, x + r + 1 > width - 1, likewise y) scores 0, and so does a
+ * result that is not finite. NNRT_ERROR_ARGUMENT for a negative height or width, height * width >= 2^31, a radius out
+ * of range, nulls of a non-empty image and images that overlap. An empty image is no error. Asynchronous on `stream`.
+ *
+ * nnrt_select_features: at most max_count (1 .. 2^20) pixels of d_scores as d_out_points float32 [max_count,2], strongest
+ * first. The maximum M is taken over the finite scores > 0 (0 if there is none). A pixel is a candidate iff its score s is
+ * finite and > 0, s >= quality * M (a float product; 0 <= quality <= 1), d_mask (uint8 [height,width], nullable) is
+ * non-zero there, and no pixel of its (2 nms_radius + 1)^2 neighbourhood clipped to the image (0 <= nms_radius <=
+ * NNRT_FEATURE_MAX_NMS_RADIUS) has a larger score or an equal score and a lower pixel index y * width + x. Candidates
+ * are ordered by descending score, ties by ascending pixel index; the first min(count, max_count) are written and
+ * *h_out_count receives their number. Rows past it are not written. Synchronizes `stream` once (the candidate count).
+ *
+ * nnrt_track_features: Bouguet's pyramidal Lucas-Kanade from pyramid A to pyramid B, one feature per wavefront.
+ * h_pyramid_a / h_pyramid_b: host arrays of `levels` (1 .. NNRT_FEATURE_MAX_LEVELS) device pointers, level l of size
+ * h_heights[l] x h_widths[l] with h_heights[l] = ceil(h_heights[l - 1] / 2), likewise the widths. d_points [count,2];
+ * d_initial_flow [count,2] nullable (level-0 pixels); d_reference_points [count,2] nullable. Per feature p, with r =
+ * window_radius (1 .. NNRT_FEATURE_MAX_WINDOW_RADIUS), window offsets (i, j), |i|, |j| <= r, and S(I, x, y) the bilinear
+ * sample in float: x0 = floor(x) (at most width - 2), a = x - x0, likewise y0, b; top = I00 + a (I01 - I00),
+ * bot = I10 + a (I11 - I10), S = top + b (bot - top). "The window of margin m at (x, y) is inside" means, in float,
+ * x - m >= 0, x + m <= width - 1, y - m >= 0, y + m <= height - 1 of the level.
+ * g = initial flow / 2^(levels - 1), or 0. p, or g, not finite: NON_FINITE. For l = levels - 1 .. 0, in float unless said:
+ *   pl = p * 2^-l. If the window of margin r + 1 at pl is not inside A_l: l > 0 skips the level, g <- 2 g; l = 0 is
+ *   OUT_OF_IMAGE. T(i, j) = S(A_l, pl.x + i, pl.y + j), Tx = 0.5 (S(.., x + 1, y) - S(.., x - 1, y)), Ty likewise in y.
+ *   In float64, Gxx = sum Tx Tx, Gxy = sum Tx Ty, Gyy = sum Ty Ty (products of the floats formed in float64; per lane
+ *   over window pixels lane, lane + 64, .. in row-major numbering, then an xor butterfly over the 64 lanes);
+ *   e_min = 0.5 ((Gxx + Gyy) - sqrt((Gxx - Gyy)(Gxx - Gyy) + 4 Gxy Gxy)) / (2 r + 1)^2; not finite: NON_FINITE;
+ *   e_min < min_eigen_threshold: l > 0 skips the level (g <- 2 g), l = 0 is FLAT. v = 0; for k < max_iterations
+ *   (1 .. NNRT_FEATURE_MAX_ITERATIONS): q = (pl + g) + v; q not finite: NON_FINITE; the window of margin r at q not
+ *   inside B_l: OUT_OF_IMAGE; e = T - S(B_l, q.x + i, q.y + j); in float64 bx = sum e Tx, by = sum e Ty (summed as G),
+ *   D = Gxx Gyy - Gxy Gxy, dx = (Gyy bx - Gxy by) / D, dy = (Gxx by - Gxy bx) / D; not finite: NON_FINITE;
+ *   v <- v + (float) d; stop if epsilon > 0 and dx dx + dy dy < epsilon^2 (epsilon = 0: exactly max_iterations).
+ *   l > 0: g <- 2 (g + v). l = 0: result = (p + g) + v; not finite: NON_FINITE; the window of margin r at the result not
+ *   inside B_0: OUT_OF_IMAGE; residual = (float)(sum |e| in float64 at the result / (2 r + 1)^2); not finite:
+ *   NON_FINITE; max_residual > 0 and residual > max_residual: RESIDUAL; with d_reference_points, unless
+ *   |result - reference|^2 <= forward_backward_threshold^2 (float, dx dx + dy dy): FB_FAILED. Otherwise TRACKED.
+ * d_out_points [count,2] (a lost feature keeps its input point: never a NaN the input did not hold), d_out_status uint8
+ * [count] (NNRT_FEATURE_*), d_out_residual [count] (the level-0 residual for TRACKED, RESIDUAL and FB_FAILED, else 0).
+ * A round-trip check is two calls: A -> B, then B -> A from the results with the original points as reference.
+ * NNRT_ERROR_ARGUMENT for a negative count, nulls of non-empty inputs, outputs that overlap an input or one another,
+ * level sizes that are not a pyramid, ranges as above, a NaN parameter, a negative or infinite epsilon or
+ * min_eigen_threshold, and a reference without a finite forward_backward_threshold >= 0. count == 0 launches nothing.
+ * Asynchronous on `stream`. */
+#define NNRT_FEATURE_MAX_WINDOW_RADIUS 7
+#define NNRT_FEATURE_MAX_NMS_RADIUS 15
+#define NNRT_FEATURE_MAX_LEVELS 4
+#define NNRT_FEATURE_MAX_ITERATIONS 30
+#define NNRT_FEATURE_TRACKED 0
+#define NNRT_FEATURE_OUT_OF_IMAGE 1
+#define NNRT_FEATURE_FLAT 2
+#define NNRT_FEATURE_RESIDUAL 3
+#define NNRT_FEATURE_NON_FINITE 4
+#define NNRT_FEATURE_FB_FAILED 5
+nnrt_status nnrt_corner_scores(const float* d_intensity, int32_t height, int32_t width, int32_t window_radius, float* d_out_scores, void* stream);
+nnrt_status nnrt_select_features(const float* d_scores, const uint8_t* d_mask, int32_t height, int32_t width, float quality, int32_t nms_radius,
+                                 int32_t max_count, float* d_out_points, int64_t* h_out_count, void* stream);
+nnrt_status nnrt_track_features(const float* const* h_pyramid_a, const float* const* h_pyramid_b, const int32_t* h_heights,
+                                const int32_t* h_widths, int32_t levels, const float* d_points, const float* d_initial_flow,
+                                const float* d_reference_points, int64_t count, int32_t window_radius, int32_t max_iterations, float epsilon,
+                                float min_eigen_threshold, float max_residual, float forward_backward_threshold, float* d_out_points,
+                                uint8_t* d_out_status, float* d_out_residual, void* stream);
 /* nnrt.core.matmul3d(array_of_matrices_a, array_of_matrices_b) (cpp/pybind/core/core.cpp:32 -> cpp/core/linalg/Matmul3D.cpp:25-83):
  * d_c [batch, m, n] = d_a [batch, m, k] x d_b [batch, k, n] per batch entry, float32 row-major (n = 1: array of vectors). */
 nnrt_status nnrt_matmul3d(const float* d_a, const float* d_b, int64_t batch, int32_t m, int32_t k, int32_t n, float* d_c, void* stream);
