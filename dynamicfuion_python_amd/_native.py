@@ -165,6 +165,9 @@ _SIGNATURES = {
                                     c_int64, c_void_p, c_float, c_float, c_void_p, c_void_p]),
     "nnrt_compare_depth_to_raster": (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p, c_int32, c_float, c_float, c_float,
                                                c_void_p, c_void_p, c_void_p]),
+    "nnrt_motion_pixels": (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_float,
+                                     c_float, c_float, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "nnrt_flow_error": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_float, c_void_p, c_void_p, c_void_p]),
     "nnrt_matmul3d": (c_int32, [c_void_p, c_void_p, c_int64, c_int32, c_int32, c_int32, c_void_p, c_void_p]),
     "nnrt_median_grid_subsample_3d_points": (c_int32, [c_void_p, c_int64, c_float, c_void_p, c_void_p, c_void_p]),
     "nnrt_mean_grid_downsample_3d_points": (c_int32, [c_void_p, c_int64, c_float, c_float, c_float, c_float, c_void_p, c_void_p, c_void_p]),

@@ -791,6 +791,77 @@ nnrt_status nnrt_compare_depth_to_raster(const int64_t* d_pixel_face_indices, co
 	return NNRT_OK;
 }
 
+nnrt_status nnrt_motion_pixels(const int64_t* d_pixel_face_indices, const float* d_pixel_barycentric_coordinates, int32_t height,
+                               int32_t width, int32_t faces_per_pixel, const int64_t* d_triangle_indices, int64_t face_count,
+                               const float* d_source_positions, const float* d_target_positions, int64_t vertex_count, float fx, float fy,
+                               float cx, float cy, float* d_out_source_points, float* d_out_scene_flow, float* d_out_optical_flow,
+                               uint8_t* d_out_mask, void* stream) {
+	NNRT_CHECK_ARG(height >= 0 && width >= 0, "negative height or width");
+	NNRT_CHECK_ARG(faces_per_pixel >= 1, "faces_per_pixel must be at least 1");
+	NNRT_CHECK_ARG(face_count >= 0, "negative face_count");
+	NNRT_CHECK_ARG(vertex_count >= 0, "negative vertex_count");
+	NNRT_CHECK_ARG(std::isfinite(fx) && std::isfinite(fy) && std::isfinite(cx) && std::isfinite(cy), "fx, fy, cx and cy must be finite");
+	NNRT_CHECK_ARG(d_triangle_indices || face_count == 0, "null d_triangle_indices");
+	NNRT_CHECK_ARG(d_source_positions || vertex_count == 0, "null d_source_positions");
+	NNRT_CHECK_ARG(d_target_positions || vertex_count == 0, "null d_target_positions");
+	const size_t pixels = static_cast<size_t>(height) * static_cast<size_t>(width);
+	if (pixels == 0) return NNRT_OK;
+	NNRT_CHECK_ARG(d_pixel_face_indices, "null d_pixel_face_indices");
+	NNRT_CHECK_ARG(d_pixel_barycentric_coordinates, "null d_pixel_barycentric_coordinates");
+	NNRT_CHECK_ARG(d_out_source_points, "null d_out_source_points");
+	NNRT_CHECK_ARG(d_out_scene_flow, "null d_out_scene_flow");
+	NNRT_CHECK_ARG(d_out_optical_flow, "null d_out_optical_flow");
+	NNRT_CHECK_ARG(d_out_mask, "null d_out_mask");
+	const size_t fragments = pixels * static_cast<size_t>(faces_per_pixel);
+	const size_t nf = static_cast<size_t>(face_count), nv = static_cast<size_t>(vertex_count);
+	const void* outputs[4] = {d_out_source_points, d_out_scene_flow, d_out_optical_flow, d_out_mask};
+	const size_t output_bytes[4] = {sizeof(float) * 3 * pixels, sizeof(float) * 3 * pixels, sizeof(float) * 2 * pixels, pixels};
+	for (int i = 0; i < 4; i++) {
+		NNRT_CHECK_ARG(!(ranges_overlap(outputs[i], output_bytes[i], d_pixel_face_indices, sizeof(int64_t) * fragments) ||
+		                 ranges_overlap(outputs[i], output_bytes[i], d_pixel_barycentric_coordinates, sizeof(float) * 3 * fragments) ||
+		                 ranges_overlap(outputs[i], output_bytes[i], d_triangle_indices, sizeof(int64_t) * 3 * nf) ||
+		                 ranges_overlap(outputs[i], output_bytes[i], d_source_positions, sizeof(float) * 3 * nv) ||
+		                 ranges_overlap(outputs[i], output_bytes[i], d_target_positions, sizeof(float) * 3 * nv)),
+		               "an output must not overlap an input");
+		for (int j = 0; j < i; j++)
+			NNRT_CHECK_ARG(!ranges_overlap(outputs[i], output_bytes[i], outputs[j], output_bytes[j]), "the outputs must not overlap each other");
+	}
+	return launch_motion_pixels(d_pixel_face_indices, d_pixel_barycentric_coordinates, height, width, faces_per_pixel, d_triangle_indices,
+	                            face_count, d_source_positions, d_target_positions, vertex_count, fx, fy, cx, cy, d_out_source_points,
+	                            d_out_scene_flow, d_out_optical_flow, d_out_mask, static_cast<hipStream_t>(stream));
+}
+
+nnrt_status nnrt_flow_error(const float* d_predicted, const uint8_t* d_predicted_mask, const float* d_truth, const uint8_t* d_truth_mask,
+                            int32_t height, int32_t width, int32_t channels, float inlier_threshold, float* d_out_error,
+                            nnrt_flow_agreement* h_out_statistics, void* stream) {
+	NNRT_CHECK_ARG(h_out_statistics, "null h_out_statistics");
+	NNRT_CHECK_ARG(height >= 0 && width >= 0, "negative height or width");
+	NNRT_CHECK_ARG(channels == 2 || channels == 3, "channels must be 2 or 3");
+	NNRT_CHECK_ARG(inlier_threshold >= 0.f, "inlier_threshold must not be negative or NaN");
+	std::memset(h_out_statistics, 0, sizeof(*h_out_statistics));
+	const size_t pixels = static_cast<size_t>(height) * static_cast<size_t>(width);
+	if (pixels == 0) return NNRT_OK;
+	NNRT_CHECK_ARG(d_predicted, "null d_predicted");
+	NNRT_CHECK_ARG(d_predicted_mask, "null d_predicted_mask");
+	NNRT_CHECK_ARG(d_truth, "null d_truth");
+	NNRT_CHECK_ARG(d_out_error, "null d_out_error");
+	const size_t out_bytes = sizeof(float) * pixels, flow_bytes = sizeof(float) * channels * pixels;
+	NNRT_CHECK_ARG(!(ranges_overlap(d_out_error, out_bytes, d_predicted, flow_bytes) || ranges_overlap(d_out_error, out_bytes, d_truth, flow_bytes) ||
+	                 ranges_overlap(d_out_error, out_bytes, d_predicted_mask, pixels) ||
+	                 (d_truth_mask && ranges_overlap(d_out_error, out_bytes, d_truth_mask, pixels))),
+	               "d_out_error must not overlap an input");
+	hipStream_t s = static_cast<hipStream_t>(stream);
+	const size_t groups = static_cast<size_t>(flow_error_partial_count(height, width));
+	StreamScratch<nnrt_flow_agreement> records;   // one per workgroup, then the total
+	if (nnrt_status st = records.alloc(groups + 1, s)) return st;
+	if (nnrt_status st = launch_flow_error(d_predicted, d_predicted_mask, d_truth, d_truth_mask, height, width, channels, inlier_threshold,
+	                                       d_out_error, records.ptr, records.ptr + groups, s))
+		return st;
+	NNRT_HIP(hipMemcpyAsync(h_out_statistics, records.ptr + groups, sizeof(*h_out_statistics), hipMemcpyDeviceToHost, s));
+	NNRT_HIP(hipStreamSynchronize(s));
+	return NNRT_OK;
+}
+
 nnrt_status nnrt_matmul3d(const float* d_a,const float* d_b, int64_t batch, int32_t m, int32_t k, int32_t n, float* d_c, void* stream) {
 	NNRT_CHECK_ARG(batch >= 0 && m >= 0 && k >= 0 && n >= 0, "negative dimension");
 	NNRT_CHECK_ARG((d_a && d_b && d_c) || batch * m * n == 0, "null pointer");

@@ -144,6 +144,16 @@ int64_t depth_agreement_partial_count(int H, int W);
 nnrt_status launch_depth_agreement(const int64_t* pixel_faces, const float* pixel_depths, int H, int W, int K, const void* frame, int frame_dtype,
                                    float depth_scale, float depth_max, float inlier_threshold, float* difference,
                                    nnrt_depth_agreement* partials, nnrt_depth_agreement* result, hipStream_t stream);
+// motion.hip: the motion field of a mesh between two states on the source state's pixel grid, and a flow image against a
+// truth image (arguments checked by the caller; launch_flow_error: H * W > 0, partials holds flow_error_partial_count(H, W)
+// records, result one, both on the device; truth_mask may be null)
+nnrt_status launch_motion_pixels(const int64_t* pixel_faces, const float* barycentrics, int H, int W, int K, const int64_t* triangles,
+                                 int64_t face_count, const float* source, const float* target, int64_t vertex_count, float fx, float fy, float cx,
+                                 float cy, float* source_points, float* scene_flow, float* optical_flow, uint8_t* mask, hipStream_t stream);
+int64_t flow_error_partial_count(int H, int W);
+nnrt_status launch_flow_error(const float* predicted, const uint8_t* predicted_mask, const float* truth, const uint8_t* truth_mask, int H, int W,
+                              int C, float inlier_threshold, float* error, nnrt_flow_agreement* partials, nnrt_flow_agreement* result,
+                              hipStream_t stream);
 nnrt_status launch_unproject(const void* depth, int depth_dtype, int H, int W, const Camera& K, const WarpExtrinsics& pose, float scale,
                              float depth_max, float* pts, uint8_t* mask, hipStream_t stream);
 nnrt_status launch_warp_points(const float* points, const float* normals, int64_t V, const float* node_state, const int32_t* anchors,

@@ -16,6 +16,7 @@
 //
 // Float arithmetic is unfused and in the order written (the build's -ffp-contract=off; the pragmas keep it so), divides
 // are correctly rounded (-fhip-fp32-correctly-rounded-divide-sqrt), so a float32 restatement equals both bit for bit.
+#include "agreement_sums.hpp"
 #include "kernels.hpp"
 
 namespace nnrt {
@@ -104,42 +105,14 @@ __global__ void __launch_bounds__(SB) k_shade_pixels(ShadeArguments a, uint8_t* 
 }
 
 // ------------------------------------------------------------------------------------------------- depth agreement ----
-struct AgreementSums {
-	long long both, model_only, frame_only, inliers;
-	double sum_abs, sum_sq;
-	float max_abs;
-
-	__device__ void add(const AgreementSums& o) {
-		both += o.both;
-		model_only += o.model_only;
-		frame_only += o.frame_only;
-		inliers += o.inliers;
-		sum_abs = sum_abs + o.sum_abs;
-		sum_sq = sum_sq + o.sum_sq;
-		max_abs = fmaxf(max_abs, o.max_abs);
-	}
-};
-
-__device__ inline AgreementSums shuffled_down(const AgreementSums& s, int offset) {
-	AgreementSums o;
-	o.both = __shfl_down(s.both, offset, 64);
-	o.model_only = __shfl_down(s.model_only, offset, 64);
-	o.frame_only = __shfl_down(s.frame_only, offset, 64);
-	o.inliers = __shfl_down(s.inliers, offset, 64);
-	o.sum_abs = __shfl_down(s.sum_abs, offset, 64);
-	o.sum_sq = __shfl_down(s.sum_sq, offset, 64);
-	o.max_abs = __shfl_down(s.max_abs, offset, 64);
-	return o;
-}
-
 __device__ inline void store_record(nnrt_depth_agreement* record, const AgreementSums& s) {
 	record->both = s.both;
-	record->model_only = s.model_only;
-	record->frame_only = s.frame_only;
+	record->model_only = s.first_only;
+	record->frame_only = s.second_only;
 	record->inliers = s.inliers;
-	record->sum_abs = s.sum_abs;
+	record->sum_abs = s.sum;
 	record->sum_sq = s.sum_sq;
-	record->max_abs = s.max_abs;
+	record->max_abs = s.max;
 	record->reserved = 0;
 }
 
@@ -167,13 +140,13 @@ __global__ void __launch_bounds__(SB) k_depth_agreement(const int64_t* __restric
 			const double wide = static_cast<double>(magnitude);
 			sums.both += 1;
 			sums.inliers += magnitude <= inlier_threshold ? 1 : 0;
-			sums.sum_abs = sums.sum_abs + wide;
+			sums.sum = sums.sum + wide;
 			sums.sum_sq = sums.sum_sq + wide * wide;
-			sums.max_abs = fmaxf(sums.max_abs, magnitude);
+			sums.max = fmaxf(sums.max, magnitude);
 		} else if (model) {
-			sums.model_only += 1;
+			sums.first_only += 1;
 		} else if (seen) {
-			sums.frame_only += 1;
+			sums.second_only += 1;
 		}
 		difference[p] = d;
 	}

@@ -287,6 +287,23 @@ def load_flow(filename):
     return _FLOW_LOADERS[ext](filename)
 
 
+def load_flow_with_mask(filename):
+    """(flow float32 [H, W, C], mask bool [H, W]) of a flow file load_flow reads, channel-last: DeepDeform's .oflow (C = 2,
+    pixels) and .sflow (C = 3, metres) mark pixels without ground truth with non-finite values; those pixels are masked
+    out and zeroed in every channel (data/deform_dataset.py:175-210). One divergence: the reference's scene-flow mask is
+    np.logical_and(a, b, c), whose third argument is `out=`, so it never tests the z channel; here a pixel is valid iff all
+    of its channels are finite."""
+    flow = np.asarray(load_flow(filename), np.float32)
+    if flow.ndim != 3:
+        raise ValueError(f"{filename}: a flow image must have three dimensions, got shape {flow.shape}")
+    if os.path.splitext(filename)[1].lower() in (".oflow", ".sflow"):
+        flow = np.moveaxis(flow, 0, -1)   # stored [C, H, W]
+    flow = np.array(flow, np.float32, order="C")   # a writable copy: load_flow may hand out a view of the file's bytes
+    mask = np.isfinite(flow).all(axis=2)
+    flow[~mask] = 0.0
+    return flow, mask
+
+
 def save_flow(filename, flow):
     """data/io.py:186-197"""
     ext = os.path.splitext(filename)[1].lower()

@@ -186,6 +186,12 @@ class FusionParameters:
     # pipeline tracks sparse features from each colour frame to the next and feeds them to the fit's landmark term. None
     # (the default): nothing is launched or allocated for it.
     landmark_tracking: Optional[FeatureTracking] = None
+    # the tracked model's own motion field: after every tracked frame's fit, the canonical mesh warped by the
+    # graph as it was before the fit, in the previous frame's camera, and by the fitted graph in the new camera are
+    # rendered to scene-flow and optical-flow images on the previous frame's pixel grid (FusionPipeline.last_motion), which
+    # a flow_truth_provider's ground truth is scored against. Reads the graph and the canonical mesh only. Off (the
+    # default): nothing is launched or allocated for it. No default of this project has been tuned with it yet.
+    motion_images: bool = False
 
 
 def alignment_parameters(p: FusionParameters) -> RenderingAlignmentParameters:
@@ -236,6 +242,16 @@ class FrameResult:
     # FusionParameters.landmark_tracking (0 without it): the features selected in the previous colour frame; landmark_count
     # counts those that survived tracking and the match filter
     tracked_feature_count: int = 0
+    # FusionParameters.motion_images (0 without it): the pixels of the model's motion field that are valid; with a
+    # FusionPipeline(flow_truth_provider=...) that gave scene flow (metres) / optical flow (pixels) for this frame, the
+    # pixels valid in both the field and the truth and, over them, the mean and the RMS end-point error
+    motion_pixel_count: int = 0
+    scene_flow_count: int = 0
+    scene_flow_epe_mean: float = 0.0
+    scene_flow_rmse: float = 0.0
+    optical_flow_count: int = 0
+    optical_flow_epe_mean: float = 0.0
+    optical_flow_rmse: float = 0.0
 
 
 def remap_edges_to_node_order(edges, order) -> np.ndarray:
@@ -256,13 +272,23 @@ def remap_edges_to_node_order(edges, order) -> np.ndarray:
 
 class FusionPipeline:
     def __init__(self, sequence: FrameSequenceDataset, parameters: Optional[FusionParameters] = None, nodes=None,
-                 device: Optional[int] = None, landmark_provider=None):
+                 device: Optional[int] = None, landmark_provider=None, flow_truth_provider=None):
         """landmark_provider: a callable (pipeline, frame, canonical_mesh, point_image) -> (vertex_indices, targets,
         weights | None) | None, called for every tracked frame before its non-rigid fit: the sparse correspondences of the
         fit's landmark term (nnrt.alignment.landmarks_from_pixel_matches makes the tuple from 2-D
         matches). None: no landmark term, unless FusionParameters.landmark_tracking is set: the pipeline then owns a
-        FeatureTrackLandmarks, hands it every frame's colour image and uses it as the provider. Both given: refused."""
+        FeatureTrackLandmarks, hands it every frame's colour image and uses it as the provider. Both given: refused.
+
+        flow_truth_provider: a callable (pipeline, frame) -> dict | None, called for every tracked frame after its motion
+        field was rendered (FusionParameters.motion_images, which it needs): ground-truth flow from the previous frame to
+        this one on the previous frame's pixel grid, under any of the keys "scene_flow" [H, W, 3] (metres),
+        "scene_flow_mask" [H, W], "optical_flow" [H, W, 2] (pixels), "optical_flow_mask" [H, W]
+        (data.io.load_flow_with_mask gives such pairs). The end-point errors go to the frame's FrameResult."""
         self.parameters = p = parameters or FusionParameters()
+        if flow_truth_provider is not None and not p.motion_images:
+            raise ValueError("flow_truth_provider needs FusionParameters.motion_images=True: the truth is scored against the rendered "
+                             "motion field")
+        self.flow_truth_provider = flow_truth_provider
         if landmark_provider is not None and p.landmark_tracking is not None:
             raise ValueError("both landmark_provider and FusionParameters.landmark_tracking are given: the pipeline takes landmarks from one "
                              "source; drop one of the two")
@@ -322,6 +348,8 @@ class FusionPipeline:
         self.warped_mesh = None
         # the point image the last tracked frame was aligned and fitted to, and whose normals gated its integration
         self.tracking_point_image = None
+        # FusionParameters.motion_images: the MotionImages of the last tracked frame, on the previous frame's pixel grid
+        self.last_motion = None
         self.processed_frames = 0
         self.results: List[FrameResult] = []
 
@@ -472,6 +500,37 @@ class FusionPipeline:
         return rendering.compare_depth_to_raster(fragments[0], fragments[1], depth, p.depth_scale, self._depth_max(),
                                                  p.model_agreement_inlier_threshold)
 
+    def render_model_motion(self, source_graph, source_extrinsics, target_graph=None, target_extrinsics=None):
+        """(MotionImages, fragments) of the current canonical mesh between two states of the warp field: warped
+        by `source_graph` and seen by the camera `source_extrinsics`, against warped by `target_graph` and seen by
+        `target_extrinsics`, which default to the loop's current graph and camera. The images are on the source camera's
+        pixel grid, raster pixel (u, v) being pixel (u, v) of the depth frames. Both graphs must be over the node set the
+        canonical mesh is anchored to."""
+        if self.active_graph is None or self.canonical_mesh is None or self.canonical_mesh.triangle_indices.shape[0] == 0:
+            raise RuntimeError("there is no canonical mesh to warp yet: process a frame first")
+        target_graph = self.active_graph if target_graph is None else target_graph
+        target_extrinsics = self.extrinsics if target_extrinsics is None else target_extrinsics
+        source = source_graph.warp_mesh(self.canonical_mesh, extrinsics=source_extrinsics)
+        target = target_graph.warp_mesh(self.canonical_mesh, extrinsics=target_extrinsics)
+        return rendering.render_motion(source, target.vertex_positions, self.K, (self.intrinsics.height, self.intrinsics.width),
+                                       ndc_convention=rendering.NDC_CONSISTENT)
+
+    def _score_motion(self, frame, res):
+        """FrameResult's flow fields from last_motion and, if there is a provider with truth for this frame, its truth."""
+        motion = self.last_motion
+        res.motion_pixel_count = int(motion.mask.sum())
+        truth = self.flow_truth_provider(self, frame) if self.flow_truth_provider is not None else None
+        if not truth:
+            return
+        # the inlier count is not reported, so the threshold only has to be legal
+        if truth.get("scene_flow") is not None:
+            a, _ = rendering.compare_flow(motion.scene_flow, motion.mask, truth["scene_flow"], truth.get("scene_flow_mask"), inlier_threshold=0.0)
+            res.scene_flow_count, res.scene_flow_epe_mean, res.scene_flow_rmse = a.both, a.mean_epe, a.rmse
+        if truth.get("optical_flow") is not None:
+            a, _ = rendering.compare_flow(motion.optical_flow, motion.mask, truth["optical_flow"], truth.get("optical_flow_mask"),
+                                          inlier_threshold=0.0)
+            res.optical_flow_count, res.optical_flow_epe_mean, res.optical_flow_rmse = a.both, a.mean_epe, a.rmse
+
     def filtered_point_image(self, depth):
         """The point image tracked frames use when a depth filter is on: the median with holes kept, then the bilateral
         smoother on its result, back-projected. `depth`: the frame's uint16 depth on the device, which is
@@ -507,6 +566,9 @@ class FusionPipeline:
             # track: fit the canonical mesh extracted at the end of the previous frame to this frame's depth (the
             # tracking-method switch, pipeline.py:356-365)
             canonical = self.canonical_mesh
+            if p.motion_images:
+                # the state the fit starts from and the camera it was seen by: the previous frame's
+                graph_before, extrinsics_before = self.active_graph.clone(), np.array(self.extrinsics, np.float64)
             if p.depth_median_radius > 0 or p.depth_bilateral_radius > 0:
                 points = self.filtered_point_image(depth)
                 res.depth_filtered = True
@@ -554,6 +616,9 @@ class FusionPipeline:
                     res.model_overlap_count, res.model_only_count, res.frame_only_count = agreement.both, agreement.model_only, agreement.frame_only
                     res.model_depth_mean_abs, res.model_depth_rmse = agreement.mean_abs, agreement.rmse
                     res.model_inlier_ratio = agreement.inlier_ratio
+                if p.motion_images:
+                    self.last_motion, _ = self.render_model_motion(graph_before, extrinsics_before)
+                    self._score_motion(frame, res)
             # fuse: blocks the warped surface's truncation band touches, then non-rigid integration (:371-417)
             blocks = self.volume.find_blocks_intersecting_truncation_region(depth, self.active_graph, self.K, self.extrinsics,
                                                                             p.depth_scale, depth_max, self.truncation_voxel_multiplier)

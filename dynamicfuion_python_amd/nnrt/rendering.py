@@ -325,3 +325,127 @@ def compare_depth_to_raster(pixel_face_indices, pixel_depths, depth, depth_scale
                                                  float(inlier_threshold), N.ptr(difference), ctypes.byref(record), N.stream_ptr()))
     return DepthAgreement(int(record.both), int(record.model_only), int(record.frame_only), int(record.inliers), float(record.sum_abs),
                           float(record.sum_sq), float(record.max_abs)), difference
+
+
+# ---- the model's motion field and its score against a flow image (csrc/motion.hip) -------------------------
+@dataclass
+class MotionImages:
+    """The motion of a mesh between two states on the source state's pixel grid, device tensors: `source_points` [H, W, 3]
+    (source camera space, metres), `scene_flow` [H, W, 3] (target point in the target camera minus source point in the
+    source camera), `optical_flow` [H, W, 2] (pixels: the projection of the target point minus that of the source point)
+    and `mask` [H, W] bool. Where the mask is False the three images are zero (DeepDeform's convention)."""
+    source_points: torch.Tensor
+    scene_flow: torch.Tensor
+    optical_flow: torch.Tensor
+    mask: torch.Tensor
+
+
+def motion_from_fragments(pixel_face_indices, pixel_barycentric_coordinates, triangle_indices, source_positions, target_positions,
+                          intrinsic_matrix):
+    """MotionImages from slot 0 of a rasterization of the source state: per pixel with a face, the barycentric blend of the
+    face's vertices in `source_positions` [V, 3] (source camera space) and in `target_positions` [V, 3] (target camera
+    space), their difference and the difference of their projections by `intrinsic_matrix`. Valid iff the pixel has a face
+    and both blended points have z > 0. The barycentrics refer to the rows of `triangle_indices` as given."""
+    dev = _dev()
+    pf = to_device(pixel_face_indices, torch.int64, dev)
+    if pf.dim() != 3:
+        raise ValueError(f"pixel_face_indices must be [H, W, K], got {tuple(pf.shape)}")
+    H, W, K = pf.shape
+    bary = to_device(pixel_barycentric_coordinates, torch.float32, dev)
+    if tuple(bary.shape) != (H, W, K, 3):
+        raise ValueError(f"pixel_barycentric_coordinates must be [{H}, {W}, {K}, 3] like the faces, got {tuple(bary.shape)}")
+    tri = to_device(triangle_indices, torch.int64, dev).reshape(-1, 3)
+    source = to_device(source_positions, torch.float32, dev)
+    target = to_device(target_positions, torch.float32, dev)
+    if source.dim() != 2 or source.shape[1] != 3 or target.shape != source.shape:
+        raise ValueError(f"source_positions and target_positions must both be [V, 3], got {tuple(source.shape)} and {tuple(target.shape)}")
+    Km = to_host_f64(intrinsic_matrix)
+    points = torch.empty((H, W, 3), dtype=torch.float32, device=dev)
+    scene = torch.empty((H, W, 3), dtype=torch.float32, device=dev)
+    optical = torch.empty((H, W, 2), dtype=torch.float32, device=dev)
+    mask = torch.empty((H, W), dtype=torch.uint8, device=dev)
+    N.check(N.lib().nnrt_motion_pixels(N.ptr(pf), N.ptr(bary), H, W, K, N.ptr(tri), tri.shape[0], N.ptr(source), N.ptr(target), source.shape[0],
+                                       float(Km[0, 0]), float(Km[1, 1]), float(Km[0, 2]), float(Km[1, 2]), N.ptr(points), N.ptr(scene),
+                                       N.ptr(optical), N.ptr(mask), N.stream_ptr()))
+    return MotionImages(points, scene, optical, mask.bool())
+
+
+def render_motion(source_mesh, target_vertex_positions, intrinsic_matrix, image_size, source_extrinsics=np.eye(4), target_extrinsics=np.eye(4),
+                  ndc_convention=NDC_CONSISTENT):
+    """(MotionImages, fragments) of a world-space mesh that moves from `source_mesh`'s vertex positions, seen by the camera
+    `source_extrinsics` (world -> camera), to `target_vertex_positions` [V, 3], seen by `target_extrinsics`: both sides to
+    their camera spaces, the source rasterized at one face per pixel, motion_from_fragments. The images are on the source
+    camera's pixel grid; with NDC_CONSISTENT (the default) raster pixel (u, v) is pixel (u, v) of the intrinsics, which a
+    comparison with a flow image of the source frame needs."""
+    dev = _dev()
+    source = _to_camera_space(source_mesh, source_extrinsics, dev)
+    moved = to_device(target_vertex_positions, torch.float32, dev)
+    if tuple(moved.shape) != tuple(source.vertex_positions.shape):
+        raise ValueError(f"target_vertex_positions must be {tuple(source.vertex_positions.shape)} like the source mesh's vertices, "
+                         f"got {tuple(moved.shape)}")
+    target = _to_camera_space(_geometry.TriangleMesh(moved, None, source.triangle_indices), target_extrinsics, dev)
+    fragments, _ = rasterize_meshes(source, intrinsic_matrix, image_size, faces_per_pixel=1, ndc_convention=ndc_convention)
+    images = motion_from_fragments(fragments[0], fragments[2], source.triangle_indices, source.vertex_positions, target.vertex_positions,
+                                   intrinsic_matrix)
+    return images, fragments
+
+
+@dataclass
+class FlowAgreement:
+    """Statistics of the end-point error of a predicted flow image against a truth image over the pixels valid on both sides
+    (`both`); `predicted_only` and `truth_only` count the pixels valid on one side; `inliers` those of `both` with an error
+    <= the inlier threshold. `sum_epe` and `sum_sq` are the float64 sums of the error and of its square."""
+    both: int = 0
+    predicted_only: int = 0
+    truth_only: int = 0
+    inliers: int = 0
+    sum_epe: float = 0.0
+    sum_sq: float = 0.0
+    max_epe: float = 0.0
+
+    @property
+    def mean_epe(self) -> float:
+        return self.sum_epe / self.both if self.both else 0.0
+
+    @property
+    def rmse(self) -> float:
+        return math.sqrt(self.sum_sq / self.both) if self.both else 0.0
+
+    @property
+    def inlier_ratio(self) -> float:
+        return self.inliers / self.both if self.both else 0.0
+
+
+class _FlowAgreementRecord(ctypes.Structure):   # nnrt_flow_agreement
+    _fields_ = [("both", ctypes.c_int64), ("predicted_only", ctypes.c_int64), ("truth_only", ctypes.c_int64), ("inliers", ctypes.c_int64),
+                ("sum_epe", ctypes.c_double), ("sum_sq", ctypes.c_double), ("max_epe", ctypes.c_float), ("reserved", ctypes.c_int32)]
+
+
+def compare_flow(predicted, predicted_mask, truth, truth_mask=None, *, inlier_threshold):
+    """A predicted flow image [H, W, C] with its mask [H, W] against a truth image [H, W, C], C = 2 (optical flow, pixels) or
+    3 (scene flow, metres): (FlowAgreement, error image [H, W] float32 on the device, NaN where either side is invalid). A
+    truth pixel is valid iff `truth_mask`, if given, is non-zero there and all its channels are finite. `inlier_threshold`
+    is in the flow's own unit and has no default. The sums are reproducible (csrc/motion.hip)."""
+    dev = _dev()
+    flow = to_device(predicted, torch.float32, dev)
+    if flow.dim() != 3 or flow.shape[2] not in (2, 3):
+        raise ValueError(f"predicted must be [H, W, 2] or [H, W, 3], got {tuple(flow.shape)}")
+    H, W, C = flow.shape
+    true_flow = to_device(truth, torch.float32, dev)
+    if tuple(true_flow.shape) != (H, W, C):
+        raise ValueError(f"truth must be [{H}, {W}, {C}] like predicted, got {tuple(true_flow.shape)}")
+
+    def mask_on_device(mask, name):
+        m = mask if isinstance(mask, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(mask))
+        if tuple(m.shape) != (H, W):
+            raise ValueError(f"{name} must be [{H}, {W}], got {tuple(m.shape)}")
+        return (m != 0).to(device=dev, dtype=torch.uint8).contiguous()
+
+    flow_mask = mask_on_device(predicted_mask, "predicted_mask")
+    true_mask = None if truth_mask is None else mask_on_device(truth_mask, "truth_mask")
+    error = torch.empty((H, W), dtype=torch.float32, device=dev)
+    record = _FlowAgreementRecord()
+    N.check(N.lib().nnrt_flow_error(N.ptr(flow), N.ptr(flow_mask), N.ptr(true_flow), N.ptr(true_mask), H, W, C, float(inlier_threshold),
+                                    N.ptr(error), ctypes.byref(record), N.stream_ptr()))
+    return FlowAgreement(int(record.both), int(record.predicted_only), int(record.truth_only), int(record.inliers), float(record.sum_epe),
+                         float(record.sum_sq), float(record.max_epe)), error

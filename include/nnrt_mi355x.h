@@ -598,6 +598,47 @@ nnrt_status nnrt_compare_depth_to_raster(const int64_t* d_pixel_face_indices, co
                                          int32_t faces_per_pixel, const void* d_depth, int32_t depth_dtype, float depth_scale,
                                          float depth_max, float inlier_threshold, float* d_out_difference,
                                          nnrt_depth_agreement* h_out_statistics, void* stream);
+/* The motion field of a mesh between two states, as images on the source state's pixel grid. Slot 0
+ * of the source state's fragments (d_pixel_face_indices [H,W,K] int64, d_pixel_barycentric_coordinates [H,W,K,3], the
+ * barycentrics over the rows of d_triangle_indices [face_count,3] as given) selects, per pixel with face f >= 0, the
+ * vertices (i0, i1, i2) and weights b. With S = d_source_positions [vertex_count,3] in the source camera's space and
+ * T = d_target_positions [vertex_count,3] in the target camera's space, in float32, every product and sum rounded on its
+ * own and in this order:
+ *   p_s = (b0 S[i0] + b1 S[i1]) + b2 S[i2], p_t the same blend of T, pi(p) = ((fx x) / z + cx, (fy y) / z + cy)
+ *   d_out_source_points [H,W,3] = p_s, d_out_scene_flow [H,W,3] = p_t - p_s, d_out_optical_flow [H,W,2] = pi(p_t) - pi(p_s)
+ * A pixel is valid iff f >= 0, p_s.z > 0 and p_t.z > 0 (NaN fails); d_out_mask [H,W] is 1 there. Every other pixel gets
+ * zeros in the three images and mask 0; so does a pixel whose face is >= face_count or has a vertex outside
+ * [0, vertex_count). Every pixel is written. Asynchronous on `stream`. Refused on the host with NNRT_ERROR_ARGUMENT before
+ * any device work, naming the argument: a negative height or width, faces_per_pixel < 1, a negative face_count or
+ * vertex_count, an intrinsic that is not finite, null d_triangle_indices with face_count > 0, null d_source_positions or
+ * d_target_positions with vertex_count > 0, and, for a non-empty image, a null fragment array or output, or an output
+ * overlapping an input or another output. height == 0 or width == 0 is no error and launches nothing. */
+nnrt_status nnrt_motion_pixels(const int64_t* d_pixel_face_indices, const float* d_pixel_barycentric_coordinates, int32_t height,
+                               int32_t width, int32_t faces_per_pixel, const int64_t* d_triangle_indices, int64_t face_count,
+                               const float* d_source_positions, const float* d_target_positions, int64_t vertex_count, float fx, float fy,
+                               float cx, float cy, float* d_out_source_points, float* d_out_scene_flow, float* d_out_optical_flow,
+                               uint8_t* d_out_mask, void* stream);
+/* A predicted flow image d_predicted [H,W,C] with its mask d_predicted_mask [H,W] (valid where non-zero) against a truth
+ * image d_truth [H,W,C], C = channels = 2 (optical flow, pixels) or 3 (scene flow, metres). A truth pixel is valid iff
+ * d_truth_mask [H,W], which may be null, is non-zero there and all C channels are finite. Per pixel valid on both sides the
+ * end-point error is e = sqrt(sum_c d_c^2) in float64 over the float32 differences d_c = predicted_c - truth_c, summed in
+ * channel order. d_out_error [H,W] float32 receives e, NaN where either side is invalid. *h_out_statistics receives the
+ * counts of pixels valid on both sides, on the prediction's only and on the truth's only, and over the pixels valid on
+ * both sides: the count of e <= inlier_threshold, the float64 sums of e and of e e and the largest e as float32. The sums
+ * are reproducible (fixed order, no atomics: DESIGN.md section 32). Synchronizes `stream`. Refused on the host with
+ * NNRT_ERROR_ARGUMENT before any device work, naming the argument: a null h_out_statistics, a negative height or width,
+ * channels other than 2 or 3, a negative or NaN inlier_threshold, and, for a non-empty image, a null array other than
+ * d_truth_mask or d_out_error overlapping an input. height == 0 or width == 0 is no error and launches nothing; the
+ * statistics are then all zero. */
+typedef struct nnrt_flow_agreement {
+	int64_t both, predicted_only, truth_only, inliers;
+	double sum_epe, sum_sq;
+	float max_epe;
+	int32_t reserved;   /* 0 */
+} nnrt_flow_agreement;
+nnrt_status nnrt_flow_error(const float* d_predicted, const uint8_t* d_predicted_mask, const float* d_truth, const uint8_t* d_truth_mask,
+                            int32_t height, int32_t width, int32_t channels, float inlier_threshold, float* d_out_error,
+                            nnrt_flow_agreement* h_out_statistics, void* stream);
 /* nnrt.geometry.functional.compute_triangle_normals(mesh, normalized=True) (cpp/geometry/functional/NormalsOperations.cpp:36-46,
  * kernel NormalsOperationsImpl.h:39-68): d_out [F,3] = (v1 - v0) x (v2 - v0), optionally normalized (zero stays zero,
  * NaN -> (0,0,1)) */
