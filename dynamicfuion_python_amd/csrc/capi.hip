@@ -1276,7 +1276,9 @@ extern "C" {
 
 nnrt_status nnrt_solve_block_sparse_arrowhead_cholesky(const float* d_diag, const float* d_wing, const int32_t* d_coords, int32_t E, int32_t N,
                                                        int32_t n0, const float* d_b, float* d_x, void* stream) {
+	NNRT_CHECK_ARG(E >= 0 && N >= 0, "negative block count");
 	NNRT_CHECK_ARG(n0 >= 0 && n0 <= N, "arrow_base_block_index out of range");
+	NNRT_CHECK_ARG((N == 0 || (d_diag && d_b && d_x)) && (E == 0 || (d_wing && d_coords)), "null pointer");
 	NNRT_CHECK_ARG((reinterpret_cast<uintptr_t>(d_diag) & 15) == 0 && (reinterpret_cast<uintptr_t>(d_wing) & 15) == 0,
 	               "diagonal and wing blocks must be 16-byte aligned (the stem reads 6x6 blocks as float4)");
 	NNRT_CHECK_ARG((reinterpret_cast<uintptr_t>(d_x) & 7) == 0, "x must be 8-byte aligned");
@@ -1292,6 +1294,7 @@ nnrt_status nnrt_solve_block_sparse_arrowhead_cholesky(const float* d_diag, cons
 		NNRT_CHECK_ARG(i != j, "wing block on the block diagonal");
 		NNRT_CHECK_ARG(j >= n0, "wing block column inside the arrow stem (the stem is block-diagonal)");
 	}
+	if (N == 0) return NNRT_OK;   // the empty system: x is empty too, nothing is launched and no plan is kept
 	int device = 0;
 	NNRT_HIP(hipGetDevice(&device));
 	std::unique_ptr<ArrowheadPlan> plan;

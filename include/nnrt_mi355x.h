@@ -982,7 +982,12 @@ nnrt_status nnrt_invert_triangular_blocks(const float* d_blocks, int32_t block_c
  * d_diagonal_blocks [N,6,6], d_wing_blocks [E,6,6] at block coordinates d_wing_coordinates [E,2] (row < arrow_base
  * <= column for stem-to-corner blocks; row >= arrow_base for corner off-diagonal blocks), b [6N]. Coordinates outside
  * [0, N), a diagonal coordinate (row == column) or a column inside the stem (column < arrow_base) give
- * NNRT_ERROR_ARGUMENT, checked before any allocation. The Schur corner is factored tile-sparse (nested-dissection order
+ * NNRT_ERROR_ARGUMENT, checked before any allocation; so do a negative block count and a NULL pointer to a non-empty
+ * array. Every split is solved: arrow_base == N (no corner: a block-diagonal solve), arrow_base == 0 (corner only),
+ * wing_block_count == 0 (the array pointers may then be NULL), corner off-diagonal blocks without any stem-to-corner
+ * block. diagonal_block_count == 0 is the empty system: NNRT_OK, nothing is read, written or launched (all pointers may
+ * be NULL). A stem block or a Schur complement that is not positive definite (a NaN pivot included) gives
+ * NNRT_ERROR_NOT_POSITIVE_DEFINITE; x is then unspecified, and the structure's plan stays valid. The Schur corner is factored tile-sparse (nested-dissection order
  * of the corner blocks); its size is bounded by device memory only. The structure-derived plan (stem lists, corner plan,
  * scratch) of the 4 most recently solved wing structures is kept per process and reused by a later call with the same
  * device, block count, arrow base and coordinates (one call owns a plan at a time; calls synchronise their stream

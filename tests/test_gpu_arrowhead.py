@@ -13,6 +13,7 @@ pytestmark = pytest.mark.gpu
 
 torch = pytest.importorskip("torch")
 
+from _arrowhead_util import fp64_solution  # noqa: E402
 from _util import rel_err  # noqa: E402
 
 
@@ -60,19 +61,6 @@ def grid_arrowhead(cx, cy, stem_per_corner, corner_edges, seed):
     diag += (6.0 * deg)[:, None, None].astype(np.float32) * np.eye(6, dtype=np.float32)
     b = rng.normal(size=6 * N).astype(np.float32)
     return diag, wing, edges, n0, b
-
-
-def fp64_solution(diag, wing, edges, b):
-    import scipy.sparse as sp
-    import scipy.sparse.linalg as spl
-    N = len(diag)
-    bi, bj = np.meshgrid(np.arange(6), np.arange(6), indexing="ij")
-    rows = [6 * np.arange(N)[:, None] + bi.ravel()[None], 6 * edges[:, :1] + bi.ravel()[None], 6 * edges[:, 1:] + bi.ravel()[None]]
-    cols = [6 * np.arange(N)[:, None] + bj.ravel()[None], 6 * edges[:, 1:] + bj.ravel()[None], 6 * edges[:, :1] + bj.ravel()[None]]
-    vals = [diag.reshape(N, 36), wing.reshape(-1, 36), wing.transpose(0, 2, 1).reshape(-1, 36)]
-    A = sp.csc_matrix((np.concatenate([v.ravel() for v in vals]).astype(np.float64),
-                       (np.concatenate([r.ravel() for r in rows]), np.concatenate([c.ravel() for c in cols]))), shape=(6 * N, 6 * N))
-    return spl.spsolve(A, b.astype(np.float64)), A
 
 
 @pytest.mark.parametrize("cx,cy,corner_edges", [(12, 8, False), (12, 8, True), (3, 2, True), (1, 1, False), (30, 3, True)])
